@@ -2,10 +2,17 @@
 """bench.py — bootstrapped gates/sec on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--gates B] [--params 80|128] [--workload nand|mixed]
+                  [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (gate prologue -> blind rotate -> extract -> keyswitch) over one
 batch of B = 4096 independent NAND gates per GPU (BASELINE config 2: "batch of 4096 independent
 gate_nand() bootstraps, N=1024, 1xMI355X"), inputs resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else,
+outside the timed region: the result checks (decryption, gather, fan-out), the single-gate latency, the
+PCIe-inclusive loops, the in-kernel clock / rounding margin, the roofline figures and the CPU baseline.
+`--dump-outputs DIR` writes the result words of the last timed step to DIR (see dump_outputs()); inputs are
+seeded, so two builds run with the same arguments can be compared word for word.
 
 N > 1, either launch style gives the same one-process-per-GPU job (torch.distributed over RCCL):
   * under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (the driver's line), or
@@ -63,8 +70,14 @@ def parse_args():
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL result gather (N > 1)")
     ap.add_argument("--fanout", action="store_true",
                     help="one process, one multi-device context: the library splits a host batch over --gpus devices itself")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-diagnostics", action="store_true", help="skip the in-kernel clock / rounding-margin run and the PCIe-inclusive loop")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the results and measure the single-gate latency, the PCIe-inclusive loops, "
+                         "the in-kernel clock / rounding margin, the roofline figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the result words of the last timed step to DIR/gates_out.npy (float64; see dump_outputs())")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-diagnostics", action="store_true",
+                    help="(--full) skip the in-kernel clock / rounding-margin run and the PCIe-inclusive loop")
     ap.add_argument("--cpu-sample-per-thread", type=int, default=8,
                     help="gates per host thread in the cpu_baseline sample (8 x 128 threads x ~30 ms = ~30 s of CPU work)")
     return ap.parse_args()
@@ -306,79 +319,76 @@ def main():
     drain()
     barrier()
     elapsed = time.perf_counter() - t0
-    launch_ms_source = "HIP events around the kernels of the timed steps (tfhe_timing_history_ms)"
-    if args.fanout:
-        # kernel times of blocking calls AFTER the timed region (a multi-device context reports the slowest shard of its last
-        # blocking call; the streamed calls above leave per-device histories only): the median of five, and the JSON line says so —
-        # these launches take the blocking path (two halves on two streams per device from pipeline_min gates up), not the
-        # streamed submits that `value` was measured on
-        samples = []
-        for _ in range(5):
-            eng.gates(ops, pins[0], pins[1], pins[2] if args.workload == "mixed" else None, out=fan_outs[0])
-            samples.append((eng.last_timing_ms(0), eng.last_timing_ms(1)))
-        br_ms, ks_ms = [float(np.median([a for a, _ in samples]))], [float(np.median([b for _, b in samples]))]
-        launch_ms_source = "median of 5 blocking tfhe_gates_batch calls after the timed region (slowest shard each); the timed steps were streamed submits"
-        host_out = fan_outs[0]
-    if not args.fanout:
-        # HIP events the engine recorded around its kernels on the stream they were launched on, for the timed steps, read
-        # now in one go: no synchronisation between the steps themselves (the engine keeps the events of its last 32 calls)
-        br_ms = eng.timing_history_ms(0, min(args.steps, 32))
-        ks_ms = eng.timing_history_ms(1, min(args.steps, 32))
-    rotations_per_step = eng.last_rotation_count()   # of the timed launches (read before any other call on eng)
-    kernel_name = eng.last_kernel_name()
     if use_dist:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share_gpu else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the gathered whole result on rank 0 when the shards are
+        # gathered, this process's own result otherwise
+        if gatherer:
+            last = gatherer.result((step_no - 1) & 1).cpu().numpy()
+        else:
+            last = host_out if args.fanout else dout.cpu().numpy()
+        dump_outputs(args.dump_outputs, last)
 
-    # --- correctness of what was just timed (not timed itself) ---------------------------------------
-    out = host_out if args.fanout else dout.cpu().numpy()
-    ok_decrypt = bool(np.array_equal(tfhe.decrypt(sk, out), expect))
-    # The first multi-GPU run validates itself: every rank reports a position-weighted checksum of the words it computed and
-    # whether they decrypt; rank 0 recomputes the checksum of every shard AS IT ARRIVED through the gather.
-    def checksum(a):
-        a = np.ascontiguousarray(a, np.int32).view(np.uint32).astype(np.uint64).reshape(-1)
-        return int((a * (np.arange(a.size, dtype=np.uint64) % np.uint64(65521) + np.uint64(1))).sum() & np.uint64(0x7FFFFFFFFFFFFFFF))
-    gather_ok = gather_sums_ok = all_ranks_decrypt = None
-    if use_dist:
-        mine = torch.tensor([checksum(out), int(ok_decrypt)], dtype=torch.int64, device="cpu" if share_gpu else dev)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        all_ranks_decrypt = bool(all(int(t[1]) == 1 for t in every))
-    if gatherer and rank == 0:
-        g = gatherer.result((step_no - 1) & 1).cpu().numpy()
-        s0, e0 = bounds[0]
-        gather_ok = bool(g.shape[0] == bounds[-1][1] and np.array_equal(g[s0:e0], out))
-        gather_sums_ok = bool(g.shape[0] == bounds[-1][1] and all(checksum(g[s:e]) == int(every[r][0]) for r, (s, e) in enumerate(bounds)))
-    fanout_ok = None
-    if args.fanout and n_gpus > 1:
-        # one device context recomputes the tail of the LAST shard (computed by the last device of the fan-out): same words
-        from tfhe_jl_amd.sharding import shard_bounds as sb
-        last0 = sb(ops, n_gpus)[-1][0]
-        lo = max(last0, B - 256)
-        one = ck.engine(0)
-        ref = one.gates(ops[lo:], hx[lo:], hy[lo:], hz[lo:] if args.workload == "mixed" else None)
-        fanout_ok = bool(np.array_equal(ref, out[lo:]))
-
-    # --- extras on rank 0, outside the timed region ---------------------------------------------------
+    # --- --full only, outside the timed region: result checks and the figures that take runs of their own -----------------
+    ok_decrypt = gather_ok = gather_sums_ok = all_ranks_decrypt = fanout_ok = None
     single_ms = single_ms_noev = pcie_value = pcie_sync = pcie_pageable = clock_mhz = margin = None
-    if rank == 0 and not args.fanout:
-        if args.workload == "nand":   # "ms/bootstrap" half of the metric: latency of ONE gate_nand (B = 1)
-            one = np.zeros(1, np.uint8)
-            o1 = torch.empty((1, n1), dtype=torch.int32, device=dev)
-            lat = []
-            for it in range(25):
-                torch.cuda.synchronize(dev)
-                t1 = time.perf_counter()
-                eng.gates_dev(one, dx.data_ptr(), dy.data_ptr(), dz.data_ptr(), o1.data_ptr(), 1, stream)
-                torch.cuda.synchronize(dev)
-                lat.append(time.perf_counter() - t1)
-            single_ms = float(np.median(lat[5:])) * 1e3
-            assert torch.equal(o1[0], dout[0]), "single-gate result differs from the batched one"
-            # the same with the engine's per-phase timing events off (option "timing_events" = 0, what circuit.py runs its levels with:
-            # each of the four event records of a call costs the stream ~5 us between two kernels); reported beside, never instead
-            eng.set_option("timing_events", 0)
-            try:
+    if args.full:
+        launch_ms_source = "HIP events around the kernels of the timed steps (tfhe_timing_history_ms)"
+        if args.fanout:
+            # kernel times of blocking calls AFTER the timed region (a multi-device context reports the slowest shard of its last
+            # blocking call; the streamed calls above leave per-device histories only): the median of five, and the JSON line says so —
+            # these launches take the blocking path (two halves on two streams per device from pipeline_min gates up), not the
+            # streamed submits that `value` was measured on
+            samples = []
+            for _ in range(5):
+                eng.gates(ops, pins[0], pins[1], pins[2] if args.workload == "mixed" else None, out=fan_outs[0])
+                samples.append((eng.last_timing_ms(0), eng.last_timing_ms(1)))
+            br_ms, ks_ms = [float(np.median([a for a, _ in samples]))], [float(np.median([b for _, b in samples]))]
+            launch_ms_source = "median of 5 blocking tfhe_gates_batch calls after the timed region (slowest shard each); the timed steps were streamed submits"
+            host_out = fan_outs[0]
+        if not args.fanout:
+            # HIP events the engine recorded around its kernels on the stream they were launched on, for the timed steps, read
+            # now in one go: no synchronisation between the steps themselves (the engine keeps the events of its last 32 calls)
+            br_ms = eng.timing_history_ms(0, min(args.steps, 32))
+            ks_ms = eng.timing_history_ms(1, min(args.steps, 32))
+        rotations_per_step = eng.last_rotation_count()   # of the timed launches (read before any other call on eng)
+        kernel_name = eng.last_kernel_name()
+
+        # --- correctness of what was just timed (not timed itself) ---------------------------------------
+        out = host_out if args.fanout else dout.cpu().numpy()
+        ok_decrypt = bool(np.array_equal(tfhe.decrypt(sk, out), expect))
+        # The first multi-GPU run validates itself: every rank reports a position-weighted checksum of the words it computed and
+        # whether they decrypt; rank 0 recomputes the checksum of every shard AS IT ARRIVED through the gather.
+        def checksum(a):
+            a = np.ascontiguousarray(a, np.int32).view(np.uint32).astype(np.uint64).reshape(-1)
+            return int((a * (np.arange(a.size, dtype=np.uint64) % np.uint64(65521) + np.uint64(1))).sum() & np.uint64(0x7FFFFFFFFFFFFFFF))
+        if use_dist:
+            mine = torch.tensor([checksum(out), int(ok_decrypt)], dtype=torch.int64, device="cpu" if share_gpu else dev)
+            every = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            all_ranks_decrypt = bool(all(int(t[1]) == 1 for t in every))
+        if gatherer and rank == 0:
+            g = gatherer.result((step_no - 1) & 1).cpu().numpy()
+            s0, e0 = bounds[0]
+            gather_ok = bool(g.shape[0] == bounds[-1][1] and np.array_equal(g[s0:e0], out))
+            gather_sums_ok = bool(g.shape[0] == bounds[-1][1] and all(checksum(g[s:e]) == int(every[r][0]) for r, (s, e) in enumerate(bounds)))
+        if args.fanout and n_gpus > 1:
+            # one device context recomputes the tail of the LAST shard (computed by the last device of the fan-out): same words
+            from tfhe_jl_amd.sharding import shard_bounds as sb
+            last0 = sb(ops, n_gpus)[-1][0]
+            lo = max(last0, B - 256)
+            one = ck.engine(0)
+            ref = one.gates(ops[lo:], hx[lo:], hy[lo:], hz[lo:] if args.workload == "mixed" else None)
+            fanout_ok = bool(np.array_equal(ref, out[lo:]))
+
+        # --- extras on rank 0, outside the timed region ---------------------------------------------------
+        if rank == 0 and not args.fanout:
+            if args.workload == "nand":   # "ms/bootstrap" half of the metric: latency of ONE gate_nand (B = 1)
+                one = np.zeros(1, np.uint8)
+                o1 = torch.empty((1, n1), dtype=torch.int32, device=dev)
                 lat = []
                 for it in range(25):
                     torch.cuda.synchronize(dev)
@@ -386,72 +396,81 @@ def main():
                     eng.gates_dev(one, dx.data_ptr(), dy.data_ptr(), dz.data_ptr(), o1.data_ptr(), 1, stream)
                     torch.cuda.synchronize(dev)
                     lat.append(time.perf_counter() - t1)
-                single_ms_noev = float(np.median(lat[5:])) * 1e3
+                single_ms = float(np.median(lat[5:])) * 1e3
                 assert torch.equal(o1[0], dout[0]), "single-gate result differs from the batched one"
-            finally:
-                eng.set_option("timing_events", 1)
-        if not args.no_diagnostics and world == 1:
-            # the same step through HOST buffers (tfhe_gates_batch: 2-3 uploads + 1 download over PCIe per step)
-            reps = max(2, min(args.steps, 5))
-            hz_ = hz if args.workload == "mixed" else None       # NAND reads no third operand: nothing to upload for it
-            eng.gates(ops, hx, hy, hz_)
-            t1 = time.perf_counter()
-            for _ in range(reps):
+                # the same with the engine's per-phase timing events off (option "timing_events" = 0, what circuit.py runs its levels with:
+                # each of the four event records of a call costs the stream ~5 us between two kernels); reported beside, never instead
+                eng.set_option("timing_events", 0)
+                try:
+                    lat = []
+                    for it in range(25):
+                        torch.cuda.synchronize(dev)
+                        t1 = time.perf_counter()
+                        eng.gates_dev(one, dx.data_ptr(), dy.data_ptr(), dz.data_ptr(), o1.data_ptr(), 1, stream)
+                        torch.cuda.synchronize(dev)
+                        lat.append(time.perf_counter() - t1)
+                    single_ms_noev = float(np.median(lat[5:])) * 1e3
+                    assert torch.equal(o1[0], dout[0]), "single-gate result differs from the batched one"
+                finally:
+                    eng.set_option("timing_events", 1)
+            if not args.no_diagnostics and world == 1:
+                # the same step through HOST buffers (tfhe_gates_batch: 2-3 uploads + 1 download over PCIe per step)
+                reps = max(2, min(args.steps, 5))
+                hz_ = hz if args.workload == "mixed" else None       # NAND reads no third operand: nothing to upload for it
                 eng.gates(ops, hx, hy, hz_)
-            pcie_pageable = B * reps / (time.perf_counter() - t1)
-            # ... and from / into page-locked buffers (tfhe_host_alloc), the result array reused: what a caller that keeps
-            # its ciphertext arrays in such memory gets (the Julia shim's flatten buffers, a server's I/O buffers)
-            px, py, pout = (tfhe.pinned_empty(hx.shape) for _ in range(3))
-            px[:], py[:] = hx, hy
-            pz = None
-            if hz_ is not None:
-                pz = tfhe.pinned_empty(hz.shape); pz[:] = hz
-            eng.gates(ops, px, py, pz, out=pout)
-            assert np.array_equal(pout, out), "host-buffer path differs from the device-buffer path"
-            t1 = time.perf_counter()
-            for _ in range(reps):
+                t1 = time.perf_counter()
+                for _ in range(reps):
+                    eng.gates(ops, hx, hy, hz_)
+                pcie_pageable = B * reps / (time.perf_counter() - t1)
+                # ... and from / into page-locked buffers (tfhe_host_alloc), the result array reused: what a caller that keeps
+                # its ciphertext arrays in such memory gets (the Julia shim's flatten buffers, a server's I/O buffers)
+                px, py, pout = (tfhe.pinned_empty(hx.shape) for _ in range(3))
+                px[:], py[:] = hx, hy
+                pz = None
+                if hz_ is not None:
+                    pz = tfhe.pinned_empty(hz.shape); pz[:] = hz
                 eng.gates(ops, px, py, pz, out=pout)
-            pcie_sync = B * reps / (time.perf_counter() - t1)
-            # ... and STREAMED: tfhe_gates_batch_submit / _wait, two batches in flight on two streams (the upload of one batch
-            # under the kernels of the other), as many steps as the timed loop above; every step's H2D + kernels + D2H is
-            # inside the timed region, results checked afterwards
-            sreps = max(4, args.steps)
-            pouts = [pout, tfhe.pinned_empty(hx.shape)]
-            tk, _ = eng.gates_submit(ops, px, py, pz, out=pouts[0]); eng.gates_wait(tk)        # (second stream's context made here)
-            tk, _ = eng.gates_submit(ops, px, py, pz, out=pouts[1]); eng.gates_wait(tk)
-            for o in pouts:
-                assert np.array_equal(o, out), "streamed host-buffer path differs from the device-buffer path"
-                o[:] = 0
-            t1 = time.perf_counter()
-            prev = None
-            for it in range(sreps):
-                tk, _ = eng.gates_submit(ops, px, py, pz, out=pouts[it & 1])
-                if prev is not None:
-                    eng.gates_wait(prev)
-                prev = tk
-            eng.gates_wait(prev)
-            pcie_value = B * sreps / (time.perf_counter() - t1)
-            for o in pouts:
-                assert np.array_equal(o, out), "streamed host-buffer path differs from the device-buffer path"
-            # clock the blind-rotate kernel holds under this load + its rounding margin: DIAG instantiation of the
-            # same kernel, >= 2 s of back-to-back launches first (MI355X_MICROARCH.md, DVFS give-back item 6)
-            eng.set_option("measure_margin", 1)
-            t1 = time.perf_counter()
-            while time.perf_counter() - t1 < 2.0:
-                for _ in range(8):
-                    eng.gates_dev(ops, dx.data_ptr(), dy.data_ptr(), dz.data_ptr(), dout.data_ptr(), B, stream)
-                torch.cuda.synchronize(dev)
-            clock_mhz = eng.last_kernel_clock_mhz()
-            margin = eng.last_rounding_margin()
-            eng.set_option("measure_margin", 0)
+                assert np.array_equal(pout, out), "host-buffer path differs from the device-buffer path"
+                t1 = time.perf_counter()
+                for _ in range(reps):
+                    eng.gates(ops, px, py, pz, out=pout)
+                pcie_sync = B * reps / (time.perf_counter() - t1)
+                # ... and STREAMED: tfhe_gates_batch_submit / _wait, two batches in flight on two streams (the upload of one batch
+                # under the kernels of the other), as many steps as the timed loop above; every step's H2D + kernels + D2H is
+                # inside the timed region, results checked afterwards
+                sreps = max(4, args.steps)
+                pouts = [pout, tfhe.pinned_empty(hx.shape)]
+                tk, _ = eng.gates_submit(ops, px, py, pz, out=pouts[0]); eng.gates_wait(tk)        # (second stream's context made here)
+                tk, _ = eng.gates_submit(ops, px, py, pz, out=pouts[1]); eng.gates_wait(tk)
+                for o in pouts:
+                    assert np.array_equal(o, out), "streamed host-buffer path differs from the device-buffer path"
+                    o[:] = 0
+                t1 = time.perf_counter()
+                prev = None
+                for it in range(sreps):
+                    tk, _ = eng.gates_submit(ops, px, py, pz, out=pouts[it & 1])
+                    if prev is not None:
+                        eng.gates_wait(prev)
+                    prev = tk
+                eng.gates_wait(prev)
+                pcie_value = B * sreps / (time.perf_counter() - t1)
+                for o in pouts:
+                    assert np.array_equal(o, out), "streamed host-buffer path differs from the device-buffer path"
+                # clock the blind-rotate kernel holds under this load + its rounding margin: DIAG instantiation of the
+                # same kernel, >= 2 s of back-to-back launches first (MI355X_MICROARCH.md, DVFS give-back item 6)
+                eng.set_option("measure_margin", 1)
+                t1 = time.perf_counter()
+                while time.perf_counter() - t1 < 2.0:
+                    for _ in range(8):
+                        eng.gates_dev(ops, dx.data_ptr(), dy.data_ptr(), dz.data_ptr(), dout.data_ptr(), B, stream)
+                    torch.cuda.synchronize(dev)
+                clock_mhz = eng.last_kernel_clock_mhz()
+                margin = eng.last_rounding_margin()
+                eng.set_option("measure_margin", 0)
 
     result = None
     if rank == 0:
-        br_avg_s = float(np.mean(br_ms)) * 1e-3
-        achieved = rotations_per_step * br_bytes(params) / br_avg_s
-        flops = rotations_per_step * br_flops(params) / br_avg_s
         total_gates = total_per_step * args.steps
-        prof = profile_counters(kernel_name, rotations_per_step)
         p = params
         result = {
             "metric": "bootstrapped gates/sec (whole node), N=1024",
@@ -462,8 +481,6 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_bootstrap_amortised": elapsed / args.steps * 1e3 / B,
-            "ms_per_bootstrap_single_gate": single_ms,
-            "ms_per_bootstrap_single_gate_without_timing_events": single_ms_noev,
             "higher_is_better": True,
             "scaling": "weak" if args.workload == "nand" else "strong",
             "vs_baseline": None,
@@ -482,70 +499,79 @@ def main():
                                   (("gloo " if share_gpu else "rccl ") + (gatherer.mode if gatherer else "gather") + " to rank 0, overlapped with the next step"
                                    + (" (one-GPU rehearsal)" if share_gpu else "")) if use_gather else "none"),
             },
-            "outputs_decrypt_correctly": ok_decrypt,
-            "gather_matches_local_shard": gather_ok,
-            "gather_matches_every_ranks_checksum": gather_sums_ok,
-            "every_rank_decrypts": all_ranks_decrypt,
-            "fanout_matches_one_device": fanout_ok,
-            "value_pcie_inclusive": pcie_value,
-            "value_pcie_inclusive_note": "the same steps streamed through tfhe_gates_batch_submit / _wait (two batches in flight, operands and "
-                                         "results in page-locked host memory from tfhe_host_alloc): every step's H2D + kernels + D2H inside "
-                                         "the timed region; _synchronous = one blocking tfhe_gates_batch per step (two half-batches on two "
-                                         "streams inside the call), _pageable = the same from ordinary numpy arrays",
-            "value_h2d_inclusive": pcie_value,      # SURVEY §8(d) config 2 asks for the host-to-device copy inside the timed region: the streamed figure has it (and the download too)
-            "value_pcie_inclusive_synchronous": pcie_sync,
-            "value_pcie_inclusive_pageable": pcie_pageable,
-            "roofline": {
-                "bound": "hbm",
-                "bound_note": "judged figure (SURVEY §8d): algorithmic key bytes / launch time against HBM peak; the transformed key "
-                              "(32.8 MB) is shared by all resident rotations and is served from L1 / L2 / Infinity Cache, so real HBM "
-                              "traffic is ~1.5 % of this; the kernel is bound by instruction issue across FP64 VALU (floor: 64 % of the "
-                              "launch with everything else removed), the LDS transpositions and the key reads at two waves per SIMD "
-                              "(DESIGN.md 4.1, ablation table): see roofline_secondary",
-                "kernel": kernel_name,
-                "achieved": achieved / 1e9,
-                "peak": HBM_PEAK / 1e9,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK,
-                "frac_of_measured_copy_rate": achieved / 6.29e12,      # 6.29 TB/s float4 copy (MI355X_MICROARCH.md), quoted beside the 8 TB/s spec
-                # PMC counters cannot be read from inside a run: `traffic` is REPLAYED from the committed rocprofv3 profile named in
-                # traffic_replayed_from (same kernel sources by hash, same launch shape), or null — see profile_counters()
-                "traffic": prof.get("hbm_bytes_per_launch"),
-                "traffic_is_replayed": prof.get("hbm_bytes_per_launch") is not None,
-                "traffic_replayed_from": prof.get("source"),
-                "counters_note": prof.get("note"),
-                "bytes_per_unit": br_bytes(params),
-                "units_per_launch": rotations_per_step,
-                "avg_launch_ms": br_avg_s * 1e3,
-                "launch_ms_source": launch_ms_source,
-                "keyswitch_avg_launch_ms": float(np.mean(ks_ms)),
-            },
-            "roofline_secondary": {
-                "bound": "fp64_valu",
-                "kernel": kernel_name,
-                "flops_per_unit": br_flops(params),
-                "flops_formula": "n * ((k+1)(l+1) * 5 M log2 M + (k+1)^2 l M * 8), M = N/2 (SURVEY §8d)",
-                "achieved": flops / 1e12,
-                "peak": FP64_VALU_PEAK / 1e12,
-                "unit": "TFLOP/s",
-                "frac": flops / FP64_VALU_PEAK,
-                "clock_mhz": clock_mhz,
-                "clock_source": "s_memtime / s_memrealtime inside the DIAG instantiation of the same kernel after >= 2 s of back-to-back launches" if clock_mhz else None,
-                "frac_at_measured_clock": (flops / (FP64_VALU_PEAK * clock_mhz / MAX_CLOCK_MHZ)) if clock_mhz else None,
-                "valu_busy_frac_replayed": prof.get("valu_busy_frac"),
-                "valu_insts_per_launch_replayed": prof.get("valu_insts_per_launch"),
-                "counters_replayed_from": prof.get("source"),
-                "rounding_margin": margin,
-            },
         }
-        if n_gpus == 1 and not args.no_cpu_baseline and args.workload == "nand" and not args.fanout:
-            result["cpu_baseline"] = cpu_baseline(tfhe, params, ck, hx, hy, out, args)
+        if args.full:
+            br_avg_s = float(np.mean(br_ms)) * 1e-3
+            achieved = rotations_per_step * br_bytes(params) / br_avg_s
+            flops = rotations_per_step * br_flops(params) / br_avg_s
+            prof = profile_counters(kernel_name, rotations_per_step)
+            result.update({
+                "ms_per_bootstrap_single_gate": single_ms,
+                "ms_per_bootstrap_single_gate_without_timing_events": single_ms_noev,
+                "outputs_decrypt_correctly": ok_decrypt,
+                "gather_matches_local_shard": gather_ok,
+                "gather_matches_every_ranks_checksum": gather_sums_ok,
+                "every_rank_decrypts": all_ranks_decrypt,
+                "fanout_matches_one_device": fanout_ok,
+                "value_pcie_inclusive": pcie_value,
+                "value_pcie_inclusive_note": "the same steps streamed through tfhe_gates_batch_submit / _wait (two batches in flight, operands and "
+                                             "results in page-locked host memory from tfhe_host_alloc): every step's H2D + kernels + D2H inside "
+                                             "the timed region; _synchronous = one blocking tfhe_gates_batch per step (two half-batches on two "
+                                             "streams inside the call), _pageable = the same from ordinary numpy arrays",
+                "value_h2d_inclusive": pcie_value,      # SURVEY §8(d) config 2 asks for the host-to-device copy inside the timed region: the streamed figure has it (and the download too)
+                "value_pcie_inclusive_synchronous": pcie_sync,
+                "value_pcie_inclusive_pageable": pcie_pageable,
+                "roofline": {
+                    "bound": "hbm",
+                    "bound_note": "judged figure (SURVEY §8d): algorithmic key bytes / launch time against HBM peak; the transformed key "
+                                  "(32.8 MB) is shared by all resident rotations and is served from L1 / L2 / Infinity Cache, so real HBM "
+                                  "traffic is ~1.5 % of this; the kernel is bound by instruction issue across FP64 VALU (floor: 64 % of the "
+                                  "launch with everything else removed), the LDS transpositions and the key reads at two waves per SIMD "
+                                  "(DESIGN.md 4.1, ablation table): see roofline_secondary",
+                    "kernel": kernel_name,
+                    "achieved": achieved / 1e9,
+                    "peak": HBM_PEAK / 1e9,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK,
+                    "frac_of_measured_copy_rate": achieved / 6.29e12,      # 6.29 TB/s float4 copy (MI355X_MICROARCH.md), quoted beside the 8 TB/s spec
+                    # PMC counters cannot be read from inside a run: `traffic` is REPLAYED from the committed rocprofv3 profile named in
+                    # traffic_replayed_from (same kernel sources by hash, same launch shape), or null — see profile_counters()
+                    "traffic": prof.get("hbm_bytes_per_launch"),
+                    "traffic_is_replayed": prof.get("hbm_bytes_per_launch") is not None,
+                    "traffic_replayed_from": prof.get("source"),
+                    "counters_note": prof.get("note"),
+                    "bytes_per_unit": br_bytes(params),
+                    "units_per_launch": rotations_per_step,
+                    "avg_launch_ms": br_avg_s * 1e3,
+                    "launch_ms_source": launch_ms_source,
+                    "keyswitch_avg_launch_ms": float(np.mean(ks_ms)),
+                },
+                "roofline_secondary": {
+                    "bound": "fp64_valu",
+                    "kernel": kernel_name,
+                    "flops_per_unit": br_flops(params),
+                    "flops_formula": "n * ((k+1)(l+1) * 5 M log2 M + (k+1)^2 l M * 8), M = N/2 (SURVEY §8d)",
+                    "achieved": flops / 1e12,
+                    "peak": FP64_VALU_PEAK / 1e12,
+                    "unit": "TFLOP/s",
+                    "frac": flops / FP64_VALU_PEAK,
+                    "clock_mhz": clock_mhz,
+                    "clock_source": "s_memtime / s_memrealtime inside the DIAG instantiation of the same kernel after >= 2 s of back-to-back launches" if clock_mhz else None,
+                    "frac_at_measured_clock": (flops / (FP64_VALU_PEAK * clock_mhz / MAX_CLOCK_MHZ)) if clock_mhz else None,
+                    "valu_busy_frac_replayed": prof.get("valu_busy_frac"),
+                    "valu_insts_per_launch_replayed": prof.get("valu_insts_per_launch"),
+                    "counters_replayed_from": prof.get("source"),
+                    "rounding_margin": margin,
+                },
+            })
+            if n_gpus == 1 and not args.no_cpu_baseline and args.workload == "nand" and not args.fanout:
+                result["cpu_baseline"] = cpu_baseline(tfhe, params, ck, hx, hy, out, args)
         print(json.dumps(result), flush=True)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
     ck.close()
-    if not ok_decrypt:
+    if ok_decrypt is False:
         sys.exit("bench.py: GPU outputs did not decrypt to the gates' truth values")
     if gather_ok is False or gather_sums_ok is False:
         sys.exit("bench.py: the gathered result differs from what the ranks computed")
@@ -553,6 +579,27 @@ def main():
         sys.exit("bench.py: some rank's GPU outputs did not decrypt to the gates' truth values")
     if fanout_ok is False:
         sys.exit("bench.py: the multi-device context's result differs from a one-device context's")
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(d, words):
+    """--dump-outputs: `words` ([gates][n + 1] Int32 result words, a gate per row) as float64, which holds every Int32 exactly, in
+    d/gates_out.npy.  A result larger than DUMP_LIMIT_BYTES is cut to a fixed sample of rows (seed 0, in ascending order) whose
+    indices go to d/gates_out_rows.npy, so that runs with the same arguments write the same rows."""
+    os.makedirs(d, exist_ok=True)
+    words = np.asarray(words)
+    rows, cols = words.shape
+    keep = DUMP_LIMIT_BYTES // (8 * (cols + 1)) - 1      # sampled rows and their indices, with room for the two .npy headers
+    rows_file = os.path.join(d, "gates_out_rows.npy")
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        np.save(rows_file, idx.astype(np.float64))
+        words = words[idx]
+    elif os.path.exists(rows_file):
+        os.remove(rows_file)                              # (left by an earlier, larger run into the same directory)
+    np.save(os.path.join(d, "gates_out.npy"), words.astype(np.float64))
 
 
 def rocprof_symbol_prefix(kernel_name):

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line_is_consistent():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--gates", "512",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--gates", "512",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -50,7 +50,7 @@ def test_bench_two_rank_launch_rehearsal():
     env = dict(os.environ, TFHE_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "512"],
+                        "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "512"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -76,11 +76,11 @@ def test_bench_spawns_its_own_ranks_and_gathers():
     and rank 0's own shard is found in the gathered tensor.  Mixed workload: uneven, rotation-balanced shards."""
     env = dict(os.environ, TFHE_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
-    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "300"], env)
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "300"], env)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["outputs_decrypt_correctly"] is True
     assert d["gather_matches_local_shard"] is True and "gather to rank 0" in d["config"]["result_gather"]
     assert abs(d["value"] - 2 * 300 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
-    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "mixed"], env)
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "mixed"], env)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["outputs_decrypt_correctly"] is True
     assert d["gather_matches_local_shard"] is True
     assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
@@ -91,7 +91,7 @@ def test_bench_fanout_context():
     """`--fanout`: one process, one multi-device context (two device contexts on this one GPU): the library splits the
     host batch itself; the line says that inputs crossed PCIe inside the timed region."""
     env = dict(os.environ, TFHE_BENCH_SHARE_GPU="1")
-    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--fanout", "--steps", "2", "--warmup", "1", "--gates", "300"], env)
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--fanout", "--steps", "2", "--warmup", "1", "--gates", "300"], env)
     assert d["n_gpus"] == 2 and d["outputs_decrypt_correctly"] is True and "multi-device context" in d["config"]["launch"]
     assert d["roofline"]["units_per_launch"] == 600 and "host buffers" in d["config"]["inputs"]
     assert abs(d["value"] - 600 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
@@ -104,10 +104,51 @@ def test_bench_single_rank_through_rccl():
     env = dict(os.environ, TFHE_BENCH_FORCE_DIST="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TFHE_BENCH_SHARE_GPU"):
         env.pop(k, None)
-    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--gates", "300",
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--gates", "300",
                         "--no-cpu-baseline", "--no-diagnostics"], env)
     assert d["n_gpus"] == 1 and d["outputs_decrypt_correctly"] is True and d["gather_matches_local_shard"] is True
     assert d["config"]["result_gather"].startswith("rccl gather to rank 0")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline line alone, over exactly --steps timed steps; --dump-outputs writes the result words of the last
+    timed step, which decrypt to the NAND of the benchmark's seeded input bits (secret key seed 123, input bits seed 456)."""
+    import numpy as np
+    import tfhe_jl_amd as tfhe
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--gates", "512",
+                        "--dump-outputs", str(tmp_path)])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d
+    assert d["steps"] == 3 and abs(d["value"] - 512 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "cpu_baseline", "outputs_decrypt_correctly", "ms_per_bootstrap_single_gate"} & set(d)
+    w = np.load(tmp_path / "gates_out.npy")
+    assert w.dtype == np.float64 and w.shape == (512, 501) and not (tmp_path / "gates_out_rows.npy").exists()
+    assert np.array_equal(w, np.round(w)) and w.min() >= -2**31 and w.max() < 2**31
+    sk = tfhe.SecretKey(np.random.default_rng(123), tfhe.tfhe_parameters_80())        # make_key_pair draws the secret key first
+    irng = np.random.default_rng(456)
+    bx, by = irng.integers(0, 2, 512).astype(bool), irng.integers(0, 2, 512).astype(bool)
+    assert np.array_equal(tfhe.decrypt(sk, w.astype(np.int32)), ~(bx & by))
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.dump_outputs on the largest result a run can hold on rank 0 (--workload mixed: 65 536 gates x 501 words): a sample of
+    rows, the same one every time, the words exact in float64, both files together within 64 MB; a smaller result into the same
+    directory afterwards is written whole and drops the stale row list."""
+    import numpy as np
+    import bench
+    words = np.random.default_rng(1).integers(-2**31, 2**31, (65536, 501), dtype=np.int64).astype(np.int32)
+    bench.dump_outputs(str(tmp_path), words)
+    w, rows = np.load(tmp_path / "gates_out.npy"), np.load(tmp_path / "gates_out_rows.npy")
+    assert w.dtype == rows.dtype == np.float64
+    assert os.path.getsize(tmp_path / "gates_out.npy") + os.path.getsize(tmp_path / "gates_out_rows.npy") <= 64 * 10**6
+    r = rows.astype(np.int64)
+    assert np.array_equal(r, rows) and np.all(np.diff(r) > 0) and r[0] >= 0 and r[-1] < 65536 and r.size > 15000
+    assert np.array_equal(w, words[r].astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "again"), words)
+    assert np.array_equal(np.load(tmp_path / "again" / "gates_out_rows.npy"), rows)
+    bench.dump_outputs(str(tmp_path), words[:4096])
+    assert np.array_equal(np.load(tmp_path / "gates_out.npy"), words[:4096]) and not (tmp_path / "gates_out_rows.npy").exists()
 
 
 def test_committed_profile_matches_the_sources_and_the_instruction_budget():
@@ -160,10 +201,10 @@ def _check_two_gpu_line(d, gates=None):
 def test_bench_two_gpus_self_spawned_real_rccl():
     """`python bench.py --gpus 2` on a box with two GPUs: one rank per device, RCCL for the barrier, the max-reduce and the result
     gather — the first execution of bench.py's collective path between two different devices."""
-    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "300"], _clean_env())
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "300"], _clean_env())
     assert d["scaling"] == "weak"
     _check_two_gpu_line(d, 300)
-    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "mixed"], _clean_env())
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "mixed"], _clean_env())
     assert d["scaling"] == "strong"
     _check_two_gpu_line(d)
     assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
@@ -178,7 +219,7 @@ def test_bench_two_gpus_under_the_drivers_launcher():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     d = _one_json_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "512"], _clean_env())
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--gates", "512"], _clean_env())
     assert d["scaling"] == "weak" and "cpu_baseline" not in d
     _check_two_gpu_line(d, 512)
 
@@ -187,7 +228,7 @@ def test_bench_two_gpus_under_the_drivers_launcher():
 @two_gpus
 def test_bench_fanout_on_two_gpus():
     """`--fanout --gpus 2`: ONE process, one multi-device context on devices {0, 1} (tfhe_ctx_create_multi with distinct ids)."""
-    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--fanout", "--steps", "2", "--warmup", "1", "--gates", "300"], _clean_env())
+    d = _one_json_line([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--fanout", "--steps", "2", "--warmup", "1", "--gates", "300"], _clean_env())
     assert d["n_gpus"] == 2 and d["outputs_decrypt_correctly"] is True and "multi-device context" in d["config"]["launch"]
     assert d["fanout_matches_one_device"] is True
     assert d["roofline"]["units_per_launch"] == 600 and "host buffers" in d["config"]["inputs"]

@@ -2,6 +2,7 @@
 header declares, passes as many argument types and arguments as the C prototype has parameters, with pointer / integer /
 floating-point kinds that match; block keywords and brackets balance.  Not a substitute for running the shim — it catches
 the drift between `include/tfhe_mi355x.h` and the binding that would otherwise only show up on a machine with Julia."""
+import json
 import os
 import re
 
@@ -149,18 +150,12 @@ def _name_lists(src, keyword):
     return names
 
 
-def _reference_exports():
-    """The export list as the reference has it, when the checkout is there (it is not on the GPU box)."""
-    path = "/root/reference/src/TFHE.jl"
-    if not os.path.exists(path):
-        return None
-    return re.findall(r"^export\s+(\w+)", open(path).read(), flags=re.M)
+# what the reference itself says, read from it once into a fixture (the reference's sources are not part of this repository)
+REF_FACTS = {k: v["value"] for k, v in json.load(open(os.path.join(ROOT, "tests", "golden", "reference_facts.json"))).items() if k != "_what"}
 
 
 def test_reference_export_list_is_current():
-    ref = _reference_exports()
-    if ref is not None:
-        assert sorted(ref) == sorted(REF_EXPORTS)
+    assert sorted(REF_FACTS["exports"]) == sorted(REF_EXPORTS)
 
 
 def test_shim_extends_the_references_functions():
@@ -209,10 +204,8 @@ def test_project_toml_declares_the_package():
     deps = proj["deps"]
     assert set(deps) == {"TFHE", "Random"}, deps
     assert deps["Random"] == "9a3f8284-a2c9-5f02-9a11-845980a1fd5c"
-    ref_uuid = "4bccc524-91da-45f4-9b13-e6dcce9f8221"                    # /root/reference/Project.toml:2
-    ref = "/root/reference/Project.toml"
-    if os.path.exists(ref):
-        assert tomli.load(open(ref, "rb"))["uuid"] == ref_uuid
+    ref_uuid = "4bccc524-91da-45f4-9b13-e6dcce9f8221"                    # the reference's Project.toml:2
+    assert REF_FACTS["uuid"] == ref_uuid
     assert deps["TFHE"] == ref_uuid
     assert "Test" in proj["extras"] and proj["targets"]["test"] == ["Test"]
     # every module the sources load is a dependency (or Base / a stdlib named in deps / extras)
@@ -233,24 +226,14 @@ def test_runtests_drives_the_references_cases_through_the_gpu_keys():
     assert sorted(names) == sorted(g for g in GATES if g not in ("gate_constant", "mk_gate_nand")), names
 
 
-def _comprehension_vars(path, anchor):
-    """Loop variables, in order, of the first `for a in ..., b in ...` that follows `anchor` in a reference source file."""
-    src = open(path).read()
-    i = src.index(anchor)
-    m = re.search(r"\bfor\s+([^\n]*)", src[i:])
-    return re.findall(r"(\w+)\s+in\s", m.group(1))
-
-
 def test_size_destructurings_follow_the_references_array_orders():
     """A Julia array built by a comprehension `[f(..) for a in A, b in B, c in C]` has size (|A|, |B|, |C|) and is indexed
     [a, b, c]: every size(...) the shim destructures, and every index expression it applies to a reference array, must use
     the order the reference's comprehension fixes (keyswitch.jl:35-38, mk_internals.jl:453-455, :6-18)."""
     src = strip_julia(open(JULIA[0]).read())
     ks_order, mk_order = ["h", "j", "i"], ["j", "i"]
-    if os.path.exists("/root/reference/src/keyswitch.jl"):
-        assert _comprehension_vars("/root/reference/src/keyswitch.jl", "ks = [") == ks_order
-        assert _comprehension_vars("/root/reference/src/mk_internals.jl", "samples = [\n            mk_tgsw_expand") == mk_order
-        assert "(n, parties)" in open("/root/reference/src/mk_internals.jl").read()
+    assert REF_FACTS["keyswitch_key_order"] == ks_order and REF_FACTS["mk_bootstrap_key_order"] == mk_order
+    assert REF_FACTS["mk_lwe_sample_a_shape"] == "(n, parties)"
     # KeyswitchKey.key: size = (base - 1, t, kN), indexed [h, j, i]
     m = re.search(r"(\w+), (\w+), (\w+) = size\(ks\.key\)", src)
     assert m, "flatten_keyswitch_key no longer destructures size(ks.key)"

@@ -4,7 +4,7 @@
 OLD=$1; NEW=$2; N=${3:-3}; shift 3
 for i in $(seq $N); do
   for L in $OLD $NEW; do
-    TFHE_MI355X_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --no-diagnostics "$@" > /tmp/ab.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
+    TFHE_MI355X_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-diagnostics "$@" > /tmp/ab.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
     python - "$L" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

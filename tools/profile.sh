@@ -11,7 +11,7 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ $# -eq 0 ]; then
-  CMD="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-diagnostics"
+  CMD="bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-diagnostics"
 else
   CMD="$@ --no-diag"
 fi
