@@ -149,8 +149,8 @@ void tfhe_ctx_destroy(tfhe_ctx *ctx);
  * `gate_xor.(cloud_key, c1, c2)` broadcast (docs/src/manual.md:28-35) spread over all the GPUs of a node.
  * One device context per entry of device_ids[] (an id may repeat: two contexts then share that GPU on separate
  * streams).  tfhe_load_* / tfhe_mk_load_* replicate the key to every device; tfhe_gates_batch,
- * tfhe_bootstrap_batch, tfhe_keyswitch_batch and tfhe_mk_gate_nand_batch split the batch into contiguous shards
- * (gates: balanced by blind-rotation count, MUX = 2) that run concurrently and write into the caller's buffers.
+ * tfhe_bootstrap_batch, tfhe_keyswitch_batch, tfhe_mk_gate_nand_batch and tfhe_mk_gates_batch split the batch into contiguous
+ * shards (gates: balanced by blind-rotation count, MUX = 2) that run concurrently and write into the caller's buffers.
  * There is no communication between devices: the gates of a batch are independent (gates.jl).
  * tfhe_gates_batch_dev needs n_dev == 1 (a device pointer belongs to one device).  tfhe_gates_batch_submit gives every
  * device its shard as a submit of its own, so each keeps two batches in flight.  The wire table (tfhe_wires_*) is
@@ -266,7 +266,8 @@ int32_t tfhe_gates_batch_dev(tfhe_ctx *ctx, const uint8_t *opcodes, const int32_
  * parallel MUXes): ciphertexts stay in a device-resident table of `num_wires` LWE samples and each call
  * runs ONE level of independent gates addressed by wire index, so nothing crosses PCIe between levels. */
 
-/* (Re)allocates the context's wire table: int32 [num_wires][n+1] on the device (0 frees it). */
+/* (Re)allocates the context's wire table: int32 [num_wires][n+1] on the device (0 frees it); multi-key rows:
+ * tfhe_mk_wires_alloc.  Upload, download and gather move rows of the width the table was allocated with. */
 int32_t tfhe_wires_alloc(tfhe_ctx *ctx, int64_t num_wires);
 /* Copies `count` samples (host int32 [count][n+1]) into / out of wires [first, first+count). */
 int32_t tfhe_wires_upload(tfhe_ctx *ctx, int64_t first, int64_t count, const int32_t *host);
@@ -312,6 +313,26 @@ int32_t tfhe_mk_load_keyswitch_key(tfhe_ctx *ctx, const int32_t *ks, int32_t par
 /* out[g] = mk_gate_nand(ck, in0[g], in1[g]); all host int32 [B][P*n+1]. */
 int32_t tfhe_mk_gate_nand_batch(tfhe_ctx *ctx, const int32_t *in0, const int32_t *in1, int32_t *out,
                                 int64_t B);
+
+/* Multi-key gate set and multi-key circuits: additions within ABI v7 (a library that exports them still reports 7).
+ * Every opcode of tfhe_gates_batch over multi-key samples (gates.jl's formulas, the constants as mk_lwe_noiseless_trivial,
+ * mk_gates.jl:8-10 for NAND): each bootstrapped gate is ONE multi-key blind rotation with mu = 1/8 and one multi-key
+ * keyswitch; MUX is two rotations whose extracted samples are summed, (0, 1/8) added once, then one keyswitch; NOT / COPY /
+ * CONST0 / CONST1 bootstrap nothing (constants: all-zero masks, b = +-1/8).
+ * out[g] = gate_<opcodes[g]>(in0[g], in1[g], in2[g]); host int32 [B][P*n+1], P = the parties of the loaded multi-key keys.
+ * TFHE_ERR_STATE on a single-key context, TFHE_ERR_NO_KEY without multi-key keys.  A multi-device context splits the batch
+ * by rotations (tfhe_shard_bounds; MUX counts two). */
+int32_t tfhe_mk_gates_batch(tfhe_ctx *ctx, const uint8_t *opcodes, const int32_t *in0, const int32_t *in1,
+                            const int32_t *in2, int32_t *out, int64_t B);
+/* (Re)allocates the context's wire table with multi-key rows: int32 [num_wires][P*n+1], P = the parties of the loaded
+ * multi-key bootstrapping key, fixed for the table's lifetime.  tfhe_wires_upload / _download / _gather then move rows of
+ * that width; tfhe_wires_alloc makes a single-key table again.  TFHE_ERR_NO_KEY without a multi-key bootstrapping key;
+ * TFHE_ERR_STATE on a single-key or a multi-device context (multi-key tables are single-device). */
+int32_t tfhe_mk_wires_alloc(tfhe_ctx *ctx, int64_t num_wires);
+/* tfhe_gates_level on the multi-key wire table: same index arrays, checks and asynchrony.  TFHE_ERR_STATE on a single-key
+ * table, or when the keys now loaded are for a party count other than the table's. */
+int32_t tfhe_mk_gates_level(tfhe_ctx *ctx, const uint8_t *opcodes, const int32_t *a, const int32_t *b,
+                            const int32_t *c, const int32_t *out, int64_t B);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

@@ -11,6 +11,8 @@ from .keys import SecretKey, CloudKey, make_key_pair, encrypt, decrypt
 from .gates import (gate_nand, gate_or, gate_and, gate_xor, gate_xnor, gate_not, gate_constant, gate_nor,
                     gate_andny, gate_andyn, gate_orny, gate_oryn, gate_mux, gates_batch)
 from .mk_keys import SharedKey, CloudKeyPart, MKCloudKey, MKLweSample, mk_encrypt, mk_decrypt, mk_gate_nand
+from .mk_gates import (mk_gate_or, mk_gate_and, mk_gate_xor, mk_gate_xnor, mk_gate_nor, mk_gate_andny, mk_gate_andyn,
+                       mk_gate_orny, mk_gate_oryn, mk_gate_mux, mk_gate_not, mk_gate_constant, mk_gates_batch)
 from .circuit import Circuit
 from .serialize import save_cloud_key, load_cloud_key
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
@@ -22,5 +24,7 @@ __all__ = [
     "gate_andny", "gate_andyn", "gate_orny", "gate_oryn", "gate_mux", "gates_batch",
     "mktfhe_parameters_2party", "mktfhe_parameters_4party", "mktfhe_parameters_8party",
     "SharedKey", "CloudKeyPart", "MKCloudKey", "MKLweSample", "mk_encrypt", "mk_decrypt", "mk_gate_nand",
+    "mk_gate_or", "mk_gate_and", "mk_gate_xor", "mk_gate_xnor", "mk_gate_nor", "mk_gate_andny", "mk_gate_andyn",
+    "mk_gate_orny", "mk_gate_oryn", "mk_gate_mux", "mk_gate_not", "mk_gate_constant", "mk_gates_batch",
     "Circuit", "save_cloud_key", "load_cloud_key", "Engine", "EngineError", "OPCODES", "LIB_PATH", "pinned_empty",
 ]

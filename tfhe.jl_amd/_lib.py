@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "tfhe_last_kernel_name", "tfhe_last_kernel_clock_mhz", "tfhe_mk_load_bootstrap_key_c128",
     "tfhe_mk_expand_load_bootstrap_key", "tfhe_keygen_cloud_key", "tfhe_host_alloc", "tfhe_host_free",
     "tfhe_timing_history_ms", "tfhe_gates_batch_submit", "tfhe_gates_batch_wait", "tfhe_last_device_count",
-    "tfhe_get_option", "tfhe_ctx_synchronize",
+    "tfhe_get_option", "tfhe_ctx_synchronize", "tfhe_mk_gates_batch", "tfhe_mk_wires_alloc", "tfhe_mk_gates_level",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -115,6 +115,10 @@ def load():
     lib.tfhe_mk_load_bootstrap_key_c128.argtypes = [vp, vp, i32]
     lib.tfhe_mk_expand_load_bootstrap_key.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tfhe_mk_gate_nand_batch.argtypes = [vp, vp, vp, vp, i64]
+    if hasattr(lib, "tfhe_mk_gates_batch"):
+        lib.tfhe_mk_gates_batch.argtypes = [vp, vp, vp, vp, vp, vp, i64]
+        lib.tfhe_mk_wires_alloc.argtypes = [vp, i64]
+        lib.tfhe_mk_gates_level.argtypes = [vp, vp, vp, vp, vp, vp, i64]
     lib.tfhe_last_timing_ms.argtypes = [vp, i32, C.POINTER(C.c_float)]
     if hasattr(lib, "tfhe_timing_history_ms"):
         lib.tfhe_timing_history_ms.argtypes = [vp, i32, C.POINTER(C.c_float), i32, C.POINTER(i32)]
@@ -190,6 +194,7 @@ class Engine:
             raise EngineError(rc, self._lib.tfhe_last_error(None).decode())
         self._h = h
         self._in_flight = {}
+        self._wire_width = n + 1          # row width of the wire table (multi-key table: P n + 1, mk_wires_alloc)
         self.device = self.devices[0]
         # is this parameter set inside what a Float64 transform computes exactly?  (decided by tfhe_ctx_create from the parameters
         # alone; the reference warns about the same thing, polynomials.jl:135-144)
@@ -334,22 +339,30 @@ class Engine:
     # ---- levelised circuits on the device-resident wire table ----
     def wires_alloc(self, num_wires):
         self._check(self._lib.tfhe_wires_alloc(self._h, int(num_wires)))
+        self._wire_width = self.n + 1
+
+    def mk_wires_alloc(self, num_wires):
+        """A wire table of multi-key rows [num_wires][P*n+1] for the parties of the loaded multi-key keys (tfhe_mk_wires_alloc);
+        wires_upload / _download / _gather then move rows of that width."""
+        self._check(self._lib.tfhe_mk_wires_alloc(self._h, int(num_wires)))
+        self._wire_width = self._mk_parties * self.n + 1
 
     def wires_upload(self, first, samples):
         m = _i32c(samples)
-        if m.ndim != 2 or m.shape[1] != self.n + 1:
-            raise ValueError("samples must be [count][n+1]")
+        if m.ndim != 2 or m.shape[1] != self._wire_width:
+            raise ValueError("samples must be [count][n+1]" if self._wire_width == self.n + 1 else
+                             f"samples must be [count][{self._wire_width}] (multi-key wire table)")
         self._check(self._lib.tfhe_wires_upload(self._h, int(first), m.shape[0], _ptr(m)))
 
     def wires_download(self, first, count):
-        out = np.empty((int(count), self.n + 1), np.int32)
+        out = np.empty((int(count), self._wire_width), np.int32)
         self._check(self._lib.tfhe_wires_download(self._h, int(first), int(count), _ptr(out)))
         return out
 
     def wires_gather(self, wires):
         """Rows of the given wire indices, in one device gather + one copy."""
         idx = np.ascontiguousarray(wires, dtype=np.int32).reshape(-1)
-        out = np.empty((idx.size, self.n + 1), np.int32)
+        out = np.empty((idx.size, self._wire_width), np.int32)
         self._check(self._lib.tfhe_wires_gather(self._h, _ptr(idx), idx.size, _ptr(out)))
         return out
 
@@ -415,6 +428,36 @@ class Engine:
         out = np.empty_like(in0)
         self._check(self._lib.tfhe_mk_gate_nand_batch(self._h, _ptr(in0), _ptr(in1), _ptr(out), in0.shape[0]))
         return out
+
+    def mk_gates_batch(self, opcodes, in0, in1=None, in2=None, out=None):
+        """Mixed batch of multi-key gates (tfhe_mk_gates_batch): operands and result int32 [B][P*n+1]; an operand no opcode
+        reads may be None."""
+        ops = np.ascontiguousarray(opcodes, dtype=np.uint8)
+        B = ops.size
+        P = getattr(self, "_mk_parties", None)
+        if P is None:
+            raise EngineError(3, "mk_gates_batch: multi-key keys not loaded")
+        w = P * self.n + 1
+        in0, in1, in2 = _i32c(in0), _i32c(in1), _i32c(in2)
+        for a in (in0, in1, in2):
+            if a is not None and a.shape != (B, w):
+                raise ValueError(f"multi-key operand shape {a.shape}, expected {(B, w)}")
+        if out is None:
+            out = np.empty((B, w), np.int32)
+        elif out.dtype != np.int32 or out.shape != (B, w) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous int32 array of shape {(B, w)}")
+        self._check(self._lib.tfhe_mk_gates_batch(self._h, _ptr(ops), _ptr(in0), _ptr(in1), _ptr(in2), _ptr(out), B))
+        return out
+
+    def mk_gates_level(self, opcodes, a, b, c, out):
+        """One level on the multi-key wire table (tfhe_mk_gates_level): the index arrays of gates_level."""
+        ops = np.ascontiguousarray(opcodes, dtype=np.uint8)
+        arrs = [None if v is None else _i32c(v) for v in (a, b, c, out)]
+        for v in arrs:
+            if v is not None and v.shape != (ops.size,):
+                raise ValueError("index arrays must have one entry per gate")
+        self._check(self._lib.tfhe_mk_gates_level(self._h, _ptr(ops), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
+                                                  _ptr(arrs[3]), ops.size))
 
     # ---- measurement ----
     def last_timing_ms(self, which):

@@ -9,6 +9,7 @@ import numpy as np
 
 from ._lib import OPCODES
 from .lwe import LweSample, LweSampleArray
+from .mk_keys import MKCloudKey, MKLweSample
 
 _ARITY = {"NOT": 1, "COPY": 1, "CONST0": 0, "CONST1": 0, "MUX": 3}
 
@@ -69,6 +70,10 @@ class Circuit:
     def num_wires(self):
         return len(self._level)
 
+    @property
+    def outputs(self):
+        return list(self._outputs)
+
     def levels(self):
         """List of levels; each level is a list of gate indices (gate g drives wire n_inputs + g)."""
         depth = max(self._level, default=0)
@@ -92,27 +97,32 @@ class Circuit:
     # ---- execution ----------------------------------------------------------------------------------
     def run(self, ck, inputs, device=0):
         """inputs: LweSampleArray / list of LweSample / int32 [n_inputs][n+1].  Returns an LweSampleArray
-        of the output wires.  Everything between upload and download runs on the GPU."""
+        of the output wires.  Everything between upload and download runs on the GPU.
+        Under an MKCloudKey: inputs int32 [n_inputs][P*n+1] (or a list of flat samples / MKLweSample), result int32
+        [n_outputs][P*n+1]; the levels run on a multi-key wire table (tfhe_mk_wires_alloc, tfhe_mk_gates_level)."""
         eng = ck.engine(device)
+        mk = isinstance(ck, MKCloudKey)
         if isinstance(inputs, LweSampleArray):
             m = inputs.data
         elif isinstance(inputs, (list, tuple)):
-            m = np.stack([s.flat() if isinstance(s, LweSample) else np.asarray(s, np.int32) for s in inputs])
+            m = np.stack([s.flat() if isinstance(s, (LweSample, MKLweSample)) else np.asarray(s, np.int32) for s in inputs])
         else:
             m = np.asarray(inputs, np.int32)
         if m.shape[0] != self._n_inputs:
             raise ValueError(f"circuit has {self._n_inputs} inputs, got {m.shape[0]}")
-        eng.wires_alloc(self.num_wires)
+        (eng.mk_wires_alloc if mk else eng.wires_alloc)(self.num_wires)
         if self._n_inputs:
             eng.wires_upload(0, m)
+        level = eng.mk_gates_level if mk else eng.gates_level
         # no per-phase timing events while the levels run: each record keeps the stream's next kernel waiting ~5 us, and a level
         # of a narrow circuit is six short operations around one single-rotation kernel (tutorial circuit: 30.5 -> 30.1 ms)
         timing_before = eng.get_option("timing_events")              # (the engine is shared through ck.engine(): put the caller's setting back)
         eng.set_option("timing_events", 0)
         try:
             for ops, a, b, c, out in self.level_arrays():
-                eng.gates_level(ops, a, b, c, out)
-            return LweSampleArray(eng.wires_gather(self._outputs))     # one device gather + one copy for all outputs
+                level(ops, a, b, c, out)
+            rows = eng.wires_gather(self._outputs)                    # one device gather + one copy for all outputs
+            return rows if mk else LweSampleArray(rows)
         finally:
             eng.set_option("timing_events", timing_before)
 
@@ -121,17 +131,20 @@ class Circuit:
         result int32 [M][n_outputs][n+1].  Every level becomes ONE tfhe_gates_level call over the M instances' gates — a level of
         a narrow circuit costs one single-rotation latency whether it holds 1 gate or 256 (one blind rotation per CU), so M <= 256 /
         (rotations of the widest level) instances cost what one does; beyond that the levels run at batch throughput.
-        Wire w of instance i is row w * M + i of the wire table: the inputs go up as one block, the outputs come down as one gather."""
+        Wire w of instance i is row w * M + i of the wire table: the inputs go up as one block, the outputs come down as one gather.
+        Under an MKCloudKey the rows are multi-key samples: inputs [M][n_inputs][P*n+1], result [M][n_outputs][P*n+1]."""
         eng = ck.engine(device)
+        mk = isinstance(ck, MKCloudKey)
         if isinstance(inputs, (list, tuple)):
             inputs = np.stack([x.data if isinstance(x, LweSampleArray) else np.asarray(x, np.int32) for x in inputs])
         m = np.ascontiguousarray(inputs, dtype=np.int32)
         if m.ndim != 3 or m.shape[1] != self._n_inputs:
-            raise ValueError(f"inputs must be [M][{self._n_inputs}][n+1], got {m.shape}")
+            raise ValueError(f"inputs must be [M][{self._n_inputs}][{'P*n+1' if mk else 'n+1'}], got {m.shape}")
         M = m.shape[0]
         if M == 0:
             return np.zeros((0, len(self._outputs), m.shape[2]), np.int32)
-        eng.wires_alloc(self.num_wires * M)
+        (eng.mk_wires_alloc if mk else eng.wires_alloc)(self.num_wires * M)
+        level = eng.mk_gates_level if mk else eng.gates_level
         if self._n_inputs:
             eng.wires_upload(0, np.ascontiguousarray(m.transpose(1, 0, 2)).reshape(self._n_inputs * M, -1))
         inst = np.arange(M, dtype=np.int32)
@@ -140,7 +153,7 @@ class Circuit:
         eng.set_option("timing_events", 0)
         try:
             for ops, a, b, c, out in self.level_arrays():
-                eng.gates_level(np.repeat(ops, M), spread(a), spread(b), spread(c), spread(out))
+                level(np.repeat(ops, M), spread(a), spread(b), spread(c), spread(out))
             rows = eng.wires_gather(spread(np.asarray(self._outputs, np.int32)))
         finally:
             eng.set_option("timing_events", timing_before)

@@ -6,7 +6,7 @@
 //   engine_dispatch.hip   which blind-rotate / keyswitch kernel a batch takes, and its launch          ("dispatch")
 //   engine_gates.hip      tfhe_gates_batch*, tfhe_bootstrap_batch, tfhe_keyswitch_batch, streaming     ("gates")
 //   engine_circuits.hip   wire table, tfhe_gates_level, rows between the devices of a context         ("circuits")
-//   engine_multikey.hip   tfhe_mk_gate_nand_batch and its kernels                                     ("multi-key")
+//   engine_multikey.hip   tfhe_mk_gate_nand_batch, tfhe_mk_gates_batch and their kernels              ("multi-key")
 //   engine_diag.hip       timing, rounding margin, in-kernel clock, options                           ("diagnostics")
 //   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit
 //
@@ -172,8 +172,11 @@ struct tfhe_ctx {
     int mk_ks_parties = 0;         // ... and of the loaded multi-key keyswitch key (tfhe_mk_gate_nand_batch needs them equal)
     bool have_mk_bk = false, have_mk_ks = false;
 
-    // device-resident wire table for levelised circuits: int32 [num_wires][n+1]
+    // device-resident wire table for levelised circuits: int32 [num_wires][n+1], or [num_wires][P n+1] for a multi-key table
+    // (tfhe_mk_wires_alloc: wires_parties = P, fixed when the table is allocated; 0 = single-key rows)
     int32_t *d_wires = nullptr; int64_t num_wires = 0;
+    int wires_parties = 0;
+    size_t wire_words() const { return wires_parties ? (size_t)wires_parties * P.n + 1 : (size_t)P.n + 1; }
 
     // workspaces
     DevBuf bara, ext, map, io[4], diag, abar, mk_acc, spec;
@@ -404,7 +407,7 @@ int32_t prepare_diag(tfhe_ctx *c, size_t R, hipStream_t s, DiagArgs &d);
 void name_kernel(tfhe_ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s);
 int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out, hipStream_t s);
-int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t B, const int32_t *d_gate, int32_t *out, hipStream_t s);
+int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, int32_t *out, hipStream_t s);
 // engine_gates.hip
 int32_t enter_stream(tfhe_ctx *c, hipStream_t s);
 int32_t leave_stream(tfhe_ctx *c, hipStream_t s);
@@ -415,5 +418,11 @@ int32_t launch_prologue(tfhe_ctx *c, size_t R, const int32_t *d_in0, const int32
                         const uint8_t *d_kind, int words, hipStream_t s);
 int32_t run_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t B, const int32_t *d_in0, const int32_t *d_in1, const int32_t *d_in2,
                   int32_t *d_out, const int32_t *ia, const int32_t *ib, const int32_t *ic, const int32_t *io, hipStream_t s);
+int32_t launch_trivial(tfhe_ctx *c, size_t T, const int32_t *d_in0, const int32_t *d_ts, const int32_t *d_td, const uint8_t *d_top, int32_t *d_out,
+                       int words, hipStream_t s);
+// engine_multikey.hip
+int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s);
+int32_t run_mk_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t B, const int32_t *d_in0, const int32_t *d_in1, const int32_t *d_in2,
+                     int32_t *d_out, const int32_t *ia, const int32_t *ib, const int32_t *ic, const int32_t *io, hipStream_t s);
 // engine_circuits.hip
 int32_t pull_wires(tfhe_ctx *c, int dst, const int32_t *wires, int64_t count);

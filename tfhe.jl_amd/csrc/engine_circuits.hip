@@ -1,4 +1,5 @@
-// engine_circuits.hip — circuits: the device-resident wire table, one level of gates per call, rows travelling between the devices of a context
+// engine_circuits.hip — circuits: the device-resident wire table (single- or multi-key rows), one level of gates per call, rows
+// travelling between the devices of a context
 #include "engine.hpp"
 #include <unordered_set>
 
@@ -18,6 +19,21 @@ __global__ void scatter_rows_kernel(const int32_t *__restrict__ rows, const int3
 // On a multi-device context every device holds a replica of the wire table; the context tracks which replicas hold each
 // wire's current value (wire_valid / wire_owner) and pull_wires brings a device up to date, device to device, for exactly the
 // rows it is about to read.
+// the table of a one-device context for `parties` (0: single-key rows of n + 1 words, else P n + 1)
+static int32_t alloc_wire_table(tfhe_ctx *c, const char *who, int64_t num_wires, int parties)
+{
+    if (num_wires < 0 || num_wires > ((int64_t)1 << 30)) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: bad wire count", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->d_wires) { (void)hipFree(c->d_wires); c->d_wires = nullptr; c->num_wires = 0; c->wires_parties = 0; }
+    if (num_wires == 0) return TFHE_OK;
+    const size_t row_words = parties ? (size_t)parties * c->P.n + 1 : (size_t)c->P.n + 1;
+    HIP_TRY(c, hipMalloc((void **)&c->d_wires, (size_t)num_wires * row_words * 4));
+    c->num_wires = num_wires;
+    c->wires_parties = parties;
+    return TFHE_OK;
+}
+
 int32_t tfhe_wires_alloc(tfhe_ctx *c, int64_t num_wires) try
 {
     ENTER_CTX(c);
@@ -32,16 +48,21 @@ int32_t tfhe_wires_alloc(tfhe_ctx *c, int64_t num_wires) try
         }
         return rc;
     }
-    if (num_wires < 0 || num_wires > ((int64_t)1 << 30)) return c->set_err(TFHE_ERR_INVALID_ARG, "wires_alloc: bad wire count");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_wires) { (void)hipFree(c->d_wires); c->d_wires = nullptr; c->num_wires = 0; }
-    if (num_wires == 0) return TFHE_OK;
-    HIP_TRY(c, hipMalloc((void **)&c->d_wires, (size_t)num_wires * (c->P.n + 1) * 4));
-    c->num_wires = num_wires;
-    return TFHE_OK;
+    return alloc_wire_table(c, "wires_alloc", num_wires, 0);
 }
 ABI_CATCH(c, "tfhe_wires_alloc")
+
+// multi-key rows for the parties of the loaded multi-key bootstrapping key; one-device contexts only (pull_wires moves
+// single-key rows)
+int32_t tfhe_mk_wires_alloc(tfhe_ctx *c, int64_t num_wires) try
+{
+    ENTER_CTX(c);
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "mk_wires_alloc: multi-key wire tables exist on one-device contexts only");
+    if (c->P.parties == 1) return c->set_err(TFHE_ERR_STATE, "mk_wires_alloc: context is single-key");
+    if (!c->have_mk_bk) return c->set_err(TFHE_ERR_NO_KEY, "mk_wires_alloc: multi-key bootstrapping key not loaded (it fixes the row width)");
+    return alloc_wire_table(c, "mk_wires_alloc", num_wires, c->mk_parties);
+}
+ABI_CATCH(c, "tfhe_mk_wires_alloc")
 
 static int32_t wires_range_ok(tfhe_ctx *c, const char *who, int64_t first, int64_t count, const void *host)
 {
@@ -68,7 +89,7 @@ int32_t tfhe_wires_upload(tfhe_ctx *c, int64_t first, int64_t count, const int32
     int32_t rc = wires_range_ok(c, "wires_upload", first, count, host);
     if (rc || count == 0) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t row = (size_t)(c->P.n + 1) * 4;
+    const size_t row = c->wire_words() * 4;      // (the width the table was allocated with)
     HIP_TRY(c, hipMemcpyAsync((char *)c->d_wires + (size_t)first * row, host, (size_t)count * row, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return TFHE_OK;
@@ -93,7 +114,7 @@ int32_t tfhe_wires_download(tfhe_ctx *c, int64_t first, int64_t count, int32_t *
     int32_t rc = wires_range_ok(c, "wires_download", first, count, host);
     if (rc || count == 0) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t row = (size_t)(c->P.n + 1) * 4;
+    const size_t row = c->wire_words() * 4;
     HIP_TRY(c, hipMemcpyAsync(host, (const char *)c->d_wires + (size_t)first * row, (size_t)count * row, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return TFHE_OK;
@@ -123,7 +144,7 @@ int32_t tfhe_wires_gather(tfhe_ctx *c, const int32_t *wires, int64_t count, int3
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }
-    const int n1 = c->P.n + 1;
+    const int n1 = (int)c->wire_words();
     int32_t rc = ensure_host_map(c, (size_t)count * 4);
     if (rc) return rc;
     memcpy(c->h_map, wires, (size_t)count * 4);
@@ -331,3 +352,25 @@ int32_t tfhe_gates_level(tfhe_ctx *c, const uint8_t *opcodes, const int32_t *a, 
                      c->stream);
 }
 ABI_CATCH(c, "tfhe_gates_level")
+
+// One level on the multi-key wire table (tfhe_mk_wires_alloc): tfhe_gates_level's contract, run_mk_gates' arithmetic.
+int32_t tfhe_mk_gates_level(tfhe_ctx *c, const uint8_t *opcodes, const int32_t *a, const int32_t *b, const int32_t *cc,
+                            const int32_t *out, int64_t B) try
+{
+    ENTER_CTX(c);
+    if (B < 0 || (B > 0 && (!opcodes || !out))) return c->set_err(TFHE_ERR_INVALID_ARG, "mk_gates_level: NULL argument or negative B");
+    if (B == 0) return TFHE_OK;
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "mk_gates_level: multi-key levels run on one-device contexts only");
+    if (c->P.parties == 1) return c->set_err(TFHE_ERR_STATE, "mk_gates_level: context is single-key");
+    if (!c->d_wires) return c->set_err(TFHE_ERR_STATE, "mk_gates_level: no wire table allocated");
+    if (!c->wires_parties) return c->set_err(TFHE_ERR_STATE, "mk_gates_level: the wire table has single-key rows (tfhe_wires_alloc): allocate it with tfhe_mk_wires_alloc");
+    if (!c->have_mk_bk || !c->have_mk_ks) return c->set_err(TFHE_ERR_NO_KEY, "mk_gates_level: multi-key keys not loaded");
+    if (c->mk_parties != c->wires_parties || c->mk_ks_parties != c->mk_parties)
+        return c->set_err(TFHE_ERR_STATE, "mk_gates_level: the wire table has rows for %d parties, the keys loaded now are for %d (bootstrapping) / %d (keyswitch)",
+                          c->wires_parties, c->mk_parties, c->mk_ks_parties);
+    { const int32_t rcv = validate_level(c, c->num_wires, opcodes, a, b, cc, out, B); if (rcv) return rcv; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_mk_gates(c, "mk_gates_level", opcodes, B, c->d_wires, c->d_wires, c->d_wires, c->d_wires, a ? a : out, b ? b : out, cc ? cc : out, out,
+                        c->stream);
+}
+ABI_CATCH(c, "tfhe_mk_gates_level")

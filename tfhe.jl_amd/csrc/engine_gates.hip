@@ -197,6 +197,15 @@ int32_t launch_prologue(tfhe_ctx *c, size_t R, const int32_t *d_in0, const int32
     return TFHE_OK;
 }
 
+// NOT / COPY / CONST0 / CONST1 of T gates (multi-key: `words` = P n mask words per sample; run_gates launches the kernel itself)
+int32_t launch_trivial(tfhe_ctx *c, size_t T, const int32_t *d_in0, const int32_t *d_ts, const int32_t *d_td, const uint8_t *d_top, int32_t *d_out,
+                       int words, hipStream_t s)
+{
+    hipLaunchKernelGGL(trivial_gates_kernel, dim3((unsigned)T), dim3(256), 0, s, d_in0, d_ts, d_td, d_top, d_out, words);
+    HIP_TRY(c, hipGetLastError());
+    return TFHE_OK;
+}
+
 int32_t tfhe_gates_batch_dev(tfhe_ctx *c, const uint8_t *opcodes, const int32_t *d_in0, const int32_t *d_in1,
                              const int32_t *d_in2, int32_t *d_out, int64_t B, void *stream) try
 {
