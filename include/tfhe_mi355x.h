@@ -287,6 +287,18 @@ int32_t tfhe_gates_level(tfhe_ctx *ctx, const uint8_t *opcodes, const int32_t *a
 int32_t tfhe_bootstrap_batch(tfhe_ctx *ctx, int32_t mu, const int32_t *in, int32_t *out, int64_t B,
                              int32_t with_keyswitch);
 
+/* Programmable bootstrapping (addition within ABI v7).
+ * blind_rotate_and_extract(v, bk, barb, bara) (bootstrap.jl:50-59) after the modulus switch of bootstrap_wo_keyswitch
+ * (bootstrap.jl:69-82) with testvect = tv[tv_index[g]] instead of repeat([mu], N); keyswitched (bootstrap.jl:92-95)
+ * if with_keyswitch != 0.  tv: host int32 [n_tv][N]; tv_index: host int32 [B] in [0, n_tv), or NULL = table 0 for every row.
+ * in: host int32 [B][n+1]; out: host int32 [B][n+1] or [B][k*N+1].
+ * Row g's body is v[phi] for phi in [0, N) and -v[phi - N] for phi in [N, 2N), phi = barb - sum(bara_i s_i) mod 2N.
+ * TFHE_ERR_INVALID_ARG: a NULL buffer, n_tv < 1 or an index outside [0, n_tv) (checked before anything is uploaded; the message
+ * names the first bad row); TFHE_ERR_STATE: a multi-key context, or measure_margin on (no DIAG form of these kernels);
+ * TFHE_ERR_NO_KEY: keys not loaded.  A multi-device context splits the rows; every device receives all tables. */
+int32_t tfhe_bootstrap_tv_batch(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const int32_t *tv_index,
+                                const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch);
+
 /* keyswitch(ks, sample) (keyswitch.jl:45-80). in: host int32 [B][k*N+1]; out: host int32 [B][n+1]. */
 int32_t tfhe_keyswitch_batch(tfhe_ctx *ctx, const int32_t *in, int32_t *out, int64_t B);
 

@@ -370,6 +370,30 @@ function gates_batch(gck::GpuCloudKey, opcodes::Vector{UInt8}, xs, ys=nothing, z
     unflatten(out, params)
 end
 
+"""
+    bootstrap_tv(gck, tables, xs, index=nothing; with_keyswitch=true)  ->  Vector{LweSample}
+
+Programmable bootstrapping (tfhe_bootstrap_tv_batch): `blind_rotate_and_extract(v, bk, barb, bara)` (bootstrap.jl:50-59) of every
+sample with the test polynomial `v = tables[:, index[g]]` (`tables`: Int32 N x n_tv, one table per column; `index`: 1-based, or
+`nothing` for the first table) instead of `repeat([mu], N)`, keyswitched (bootstrap.jl:92-95) unless `with_keyswitch = false`
+(then the extracted samples of size k N).
+"""
+function bootstrap_tv(gck::GpuCloudKey, tables::AbstractMatrix{Int32}, xs, index=nothing; with_keyswitch::Bool=true)
+    B = length(xs)
+    B == 0 && return LweSample[]
+    N = gck.params.tlwe_polynomial_degree
+    size(tables, 1) == N || error("tfhe_mi355x: test polynomials must have N = ", N, " rows")
+    tv = Matrix{Int32}(tables)
+    idx = index === nothing ? nothing : Int32.(collect(index) .- 1)
+    fx = flatten(xs)
+    n_out = with_keyswitch ? gck.params.lwe_size : gck.params.tlwe_mask_size * N
+    out = Array{Int32}(undef, n_out + 1, B)
+    GC.@preserve tv idx fx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_bootstrap_tv_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Int32),
+        gck.ctx, tv, Int32(size(tv, 2)), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), fx, out, B, Int32(with_keyswitch)))
+    unflatten(out, LweParams(n_out))
+end
+
 # page-locked Int32 matrix (tfhe_host_alloc): the copies of a streamed batch are then single DMA transfers that overlap kernels
 function pinned_matrix(rows::Int, cols::Int)
     p = Ref{Ptr{Cvoid}}(C_NULL)

@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "tfhe_mk_expand_load_bootstrap_key", "tfhe_keygen_cloud_key", "tfhe_host_alloc", "tfhe_host_free",
     "tfhe_timing_history_ms", "tfhe_gates_batch_submit", "tfhe_gates_batch_wait", "tfhe_last_device_count",
     "tfhe_get_option", "tfhe_ctx_synchronize", "tfhe_mk_gates_batch", "tfhe_mk_wires_alloc", "tfhe_mk_gates_level",
+    "tfhe_bootstrap_tv_batch",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -109,6 +110,7 @@ def load():
         lib.tfhe_gates_batch_submit.argtypes = [vp, vp, vp, vp, vp, vp, i64, C.POINTER(i32)]
         lib.tfhe_gates_batch_wait.argtypes = [vp, i32]
     lib.tfhe_bootstrap_batch.argtypes = [vp, i32, vp, vp, i64, i32]
+    lib.tfhe_bootstrap_tv_batch.argtypes = [vp, vp, i32, vp, vp, vp, i64, i32]
     lib.tfhe_keyswitch_batch.argtypes = [vp, vp, vp, i64]
     lib.tfhe_mk_load_bootstrap_key_i32.argtypes = [vp, vp, i32]
     lib.tfhe_mk_load_keyswitch_key.argtypes = [vp, vp, i32]
@@ -325,6 +327,28 @@ class Engine:
         width = self.n + 1 if with_keyswitch else self.k * self.N + 1
         out = np.empty((B, width), np.int32)
         self._check(self._lib.tfhe_bootstrap_batch(self._h, int(mu), _ptr(x), _ptr(out), B, 1 if with_keyswitch else 0))
+        return out
+
+    def bootstrap_tv(self, tables, x, index=None, with_keyswitch=True):
+        """Programmable bootstrapping (tfhe_bootstrap_tv_batch): `bootstrap` with row g's test polynomial tables[index[g]]
+        (int32 [n_tv][N]; index None: table 0 for every row) instead of (mu, ..., mu).  Row g's result has the body
+        v[phi] for phi in [0, N) and -v[phi - N] for phi in [N, 2N), phi = the row's modulus-switched phase (lut.py)."""
+        x = _i32c(x)
+        if x.ndim != 2 or x.shape[1] != self.n + 1:
+            raise ValueError(f"bootstrap_tv input must be [B][{self.n + 1}], got {x.shape}")
+        tables = _i32c(np.atleast_2d(tables))
+        if tables.ndim != 2 or tables.shape[1] != self.N:
+            raise ValueError(f"test polynomials must be [n_tv][{self.N}], got {tables.shape}")
+        B = x.shape[0]
+        idx = None
+        if index is not None:
+            idx = _i32c(index)
+            if idx.shape != (B,):
+                raise ValueError(f"index must have one entry per row ({B}), got {idx.shape}")
+        width = self.n + 1 if with_keyswitch else self.k * self.N + 1
+        out = np.empty((B, width), np.int32)
+        self._check(self._lib.tfhe_bootstrap_tv_batch(self._h, _ptr(tables), tables.shape[0], _ptr(idx) if idx is not None else None,
+                                                      _ptr(x), _ptr(out), B, 1 if with_keyswitch else 0))
         return out
 
     def keyswitch(self, x):

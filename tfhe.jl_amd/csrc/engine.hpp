@@ -8,6 +8,7 @@
 //   engine_circuits.hip   wire table, tfhe_gates_level, rows between the devices of a context         ("circuits")
 //   engine_multikey.hip   tfhe_mk_gate_nand_batch, tfhe_mk_gates_batch and their kernels              ("multi-key")
 //   engine_diag.hip       timing, rounding margin, in-kernel clock, options                           ("diagnostics")
+//   engine_tv.hip         the TV kernels (programmable bootstrapping) and their launches              ("tv")
 //   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
@@ -180,6 +181,7 @@ struct tfhe_ctx {
 
     // workspaces
     DevBuf bara, ext, map, io[4], diag, abar, mk_acc, spec;
+    DevBuf tv, tv_index;           // tfhe_bootstrap_tv_batch: the test polynomials and the table of each row
     size_t diag_rows = 0;
     bool mk_force_general = false; // tfhe_set_option("mk_general", 1): use the any-P kernel for 2 parties too (cross-check)
     int n2048_rw = 0;              // N = 2048: rotations per workgroup advancing in lockstep (tfhe_set_option("n2048_rw", 0|1|2); 0 = one up to
@@ -405,7 +407,9 @@ void quiesce(tfhe_ctx *c);
 struct DiagArgs;
 int32_t prepare_diag(tfhe_ctx *c, size_t R, hipStream_t s, DiagArgs &d);
 void name_kernel(tfhe_ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s);
+// a TV batch (tfhe_bootstrap_tv_batch): the test polynomials and the table of each rotation of the batch, device pointers
+struct TvPtrs { const int32_t *tv; const int32_t *index; };
+int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, const TvPtrs *tv = nullptr);
 int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out, hipStream_t s);
 int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, int32_t *out, hipStream_t s);
 // engine_gates.hip
@@ -424,5 +428,16 @@ int32_t launch_trivial(tfhe_ctx *c, size_t T, const int32_t *d_in0, const int32_
 int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s);
 int32_t run_mk_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t B, const int32_t *d_in0, const int32_t *d_in1, const int32_t *d_in2,
                      int32_t *d_out, const int32_t *ia, const int32_t *ib, const int32_t *ic, const int32_t *io, hipStream_t s);
+// engine_tv.hip: the TV form of each launch of launch_blind_rotate_part (same geometry)
+int32_t tv_launch_anyn(tfhe_ctx *c, const anyn::Args &g, const TvPtrs &tv, size_t R, unsigned nt, size_t lds, hipStream_t s);
+int32_t tv_launch_n512w2(tfhe_ctx *c, const N512Args &b, const TvPtrs &tv, int L, size_t R, size_t lds, hipStream_t s);
+int32_t tv_launch_n512(tfhe_ctx *c, const N512Args &b, const TvPtrs &tv, int L, bool group, size_t R, size_t lds, hipStream_t s);
+int32_t tv_launch_general(tfhe_ctx *c, const BrGenArgs &g, const TvPtrs &tv, bool n2048, size_t R, size_t lds, hipStream_t s);
+int32_t tv_launch_n2048(tfhe_ctx *c, const Br2048Args &b, const TvPtrs &tv, int rw, unsigned nblk, size_t lds, hipStream_t s);
+int32_t tv_launch_k2w3(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, size_t R, size_t lds, hipStream_t s);
+int32_t tv_launch_k2(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, bool grouped, size_t blocks, size_t lds, hipStream_t s);
+int32_t tv_launch_h2(tfhe_ctx *c, const BrArgs &a, const H2Tables &ht, const TvPtrs &tv, int L, size_t R, size_t lds, hipStream_t s);
+int32_t tv_launch_w2(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, bool pairs, size_t R, size_t lds, hipStream_t s);
+int32_t tv_launch_v3(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, bool group, size_t R, size_t lds, hipStream_t s);
 // engine_circuits.hip
 int32_t pull_wires(tfhe_ctx *c, int dst, const int32_t *wires, int64_t count);

@@ -63,8 +63,15 @@ void name_kernel(tfhe_ctx *c, const char *fmt, ...)
 
 // Blind rotation of rotations [first, first + R) of the batch (rows of the bara / ext workspaces): picks the kernel for a
 // batch of R rotations, launches it on `s` and names it.
-static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int32_t mu, hipStream_t s, const DiagArgs &diag, int k2_kind = -1 /* k = 2: 0 = one wave per rotation, 1 = three, -1 = by batch size */)
+// A TV batch (tv != NULL: programmable bootstrapping) takes the same kernel, geometry and LDS as a mu batch of the same size, in its TV
+// form (engine_tv.hip); the caller names it with "+tv".
+static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int32_t mu, hipStream_t s, const DiagArgs &diag, int k2_kind = -1 /* k = 2: 0 = one wave per rotation, 1 = three, -1 = by batch size */,
+                                        const TvPtrs *tv_all = nullptr)
 {
+    TvPtrs tv{nullptr, nullptr};
+    if (tv_all) tv = TvPtrs{tv_all->tv, tv_all->index + first};
+    const int32_t Ltv = (c->br_rt_l || (c->P.bs_l != 2 && c->P.bs_l != 3)) ? 0 : c->P.bs_l;     // (BR_CASES_ANY_L's choice)
+#define TV_OR(TVCALL, ...) do { if (tv_all) { const int32_t rtv_ = (TVCALL); if (rtv_) return rtv_; } else { __VA_ARGS__; } } while (0)
     BrArgs a;
     a.diag = diag;
     if (diag.margin_bits) { a.diag.margin_bits += first; a.diag.clk += 2 * first; }
@@ -99,7 +106,10 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         }
         const size_t ldsa = anyn::lds_bytes(N, spec_lds ? K1 : 0);
         const unsigned nt = (unsigned)anyn::threads_for(N);
-        if (dg) {
+        if (tv_all) {
+            const int32_t rtv = tv_launch_anyn(c, g, tv, R, nt, ldsa, s);
+            if (rtv) return rtv;
+        } else if (dg) {
             if (ldsa > 64 * 1024) LDS_TRY(c, ldsa, anyn::blind_rotate_kernel<true>);
             hipLaunchKernelGGL((anyn::blind_rotate_kernel<true>), dim3((unsigned)R), dim3(nt), ldsa, s, g);
         } else {
@@ -125,7 +135,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
 #define LAUNCH_N512W2(LL)                                                                                          \
             if (dg) hipLaunchKernelGGL((blind_rotate_kernel_n512w2<LL, true>), dim3((unsigned)R), dim3(128), ldsw, s, b);        \
             else hipLaunchKernelGGL((blind_rotate_kernel_n512w2<LL, false>), dim3((unsigned)R), dim3(128), ldsw, s, b)
-            BR_CASES_ANY_L(LAUNCH_N512W2)
+            TV_OR(tv_launch_n512w2(c, b, tv, Ltv, R, ldsw, s), BR_CASES_ANY_L(LAUNCH_N512W2));
 #undef LAUNCH_N512W2
             HIP_TRY(c, hipGetLastError());
             if ((L == 2 || L == 3) && !c->br_rt_l) name_kernel(c, "blind_rotate_kernel_n512w2<%d>", L);
@@ -138,7 +148,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         if (dg) hipLaunchKernelGGL((blind_rotate_kernel_n512<LL, true, 1>), dim3((unsigned)R), dim3(64), lds5, s, b);            \
         else if (group) hipLaunchKernelGGL((blind_rotate_kernel_n512<LL, false, 4>), dim3((unsigned)((R + 3) / 4)), dim3(256), lds5, s, b); \
         else hipLaunchKernelGGL((blind_rotate_kernel_n512<LL, false, 1>), dim3((unsigned)R), dim3(64), lds5, s, b)
-        BR_CASES_ANY_L(LAUNCH_N512)
+        TV_OR(tv_launch_n512(c, b, tv, Ltv, group, R, lds5, s), BR_CASES_ANY_L(LAUNCH_N512));
 #undef LAUNCH_N512
         HIP_TRY(c, hipGetLastError());
         if ((L == 2 || L == 3) && !c->br_rt_l) name_kernel(c, group ? "blind_rotate_kernel_n512<%d,rw4>" : "blind_rotate_kernel_n512<%d>", L);
@@ -163,7 +173,8 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
                 LDS_TRY(c, ldsg, blind_rotate_kernel_general<NB, DG>); \
             hipLaunchKernelGGL((blind_rotate_kernel_general<NB, DG>), dim3((unsigned)R), dim3(64), ldsg, s, g);     \
         } while (0)
-        if (c->P.N == kN2) { if (dg) LAUNCH_GEN(32, true); else LAUNCH_GEN(32, false); }
+        if (tv_all) { const int32_t rtv = tv_launch_general(c, g, tv, c->P.N == kN2, R, ldsg, s); if (rtv) return rtv; }
+        else if (c->P.N == kN2) { if (dg) LAUNCH_GEN(32, true); else LAUNCH_GEN(32, false); }
         else { if (dg) LAUNCH_GEN(16, true); else LAUNCH_GEN(16, false); }
 #undef LAUNCH_GEN
         HIP_TRY(c, hipGetLastError());
@@ -186,7 +197,8 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
                 LDS_TRY(c, ldsb, blind_rotate_kernel_n2048x<3, DG, RWV>); \
             hipLaunchKernelGGL((blind_rotate_kernel_n2048x<3, DG, RWV>), dim3(nblk), dim3(128 * RWV), ldsb, s, b); \
         } while (0)
-        if (dg) LAUNCH_2048(true, 1);
+        if (tv_all) { const int32_t rtv = tv_launch_n2048(c, b, tv, rw, nblk, ldsb, s); if (rtv) return rtv; }
+        else if (dg) LAUNCH_2048(true, 1);
         else if (rw == 2) LAUNCH_2048(false, 2);
         else LAUNCH_2048(false, 1);
 #undef LAUNCH_2048
@@ -217,7 +229,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
                 if (dg) { LDS_TRY(c, ldsw, blind_rotate_kernel_k2w3<LL, true>); hipLaunchKernelGGL((blind_rotate_kernel_k2w3<LL, true>), dim3((unsigned)R), dim3(192), ldsw, s, a); } \
                 else { LDS_TRY(c, ldsw, blind_rotate_kernel_k2w3<LL, false>); hipLaunchKernelGGL((blind_rotate_kernel_k2w3<LL, false>), dim3((unsigned)R), dim3(192), ldsw, s, a); } \
             } while (0)
-            BR_CASES(LAUNCH_K2W3)
+            TV_OR(tv_launch_k2w3(c, a, tv, L, R, ldsw, s), BR_CASES(LAUNCH_K2W3));
 #undef LAUNCH_K2W3
             HIP_TRY(c, hipGetLastError());
             name_kernel(c, "blind_rotate_kernel_k2w3<%d>", L);
@@ -234,7 +246,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
                 LDS_TRY(c, (7 * ldsk), blind_rotate_kernel_k2<LL, false, 7>); \
                 hipLaunchKernelGGL((blind_rotate_kernel_k2<LL, false, 7>), dim3((unsigned)G), dim3(448), 7 * ldsk, s, a); \
             } while (0)
-            BR_CASES(LAUNCH_K2)
+            TV_OR(tv_launch_k2(c, a, tv, L, true, G, ldsk, s), BR_CASES(LAUNCH_K2));
 #undef LAUNCH_K2
             HIP_TRY(c, hipGetLastError());
             name_kernel(c, "blind_rotate_kernel_k2<%d,rw7>", L);
@@ -243,7 +255,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
 #define LAUNCH_K2(LL)                                                                                              \
         if (dg) hipLaunchKernelGGL((blind_rotate_kernel_k2<LL, true>), dim3((unsigned)R), dim3(64), ldsk, s, a);  \
         else hipLaunchKernelGGL((blind_rotate_kernel_k2<LL, false>), dim3((unsigned)R), dim3(64), ldsk, s, a)
-        BR_CASES(LAUNCH_K2)
+        TV_OR(tv_launch_k2(c, a, tv, L, false, R, ldsk, s), BR_CASES(LAUNCH_K2));
 #undef LAUNCH_K2
         HIP_TRY(c, hipGetLastError());
         name_kernel(c, "blind_rotate_kernel_k2<%d>", L);
@@ -262,7 +274,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
             hipLaunchKernelGGL((blind_rotate_kernel_h2<LL, DG>), dim3((unsigned)R), dim3(256 * LL), ldsh, s, a, ht); \
         } while (0)
 #define LAUNCH_H2(LL) do { if (dg) LAUNCH_H2_(LL, true); else LAUNCH_H2_(LL, false); } while (0)
-        BR_CASES(LAUNCH_H2)
+        TV_OR(tv_launch_h2(c, a, ht, tv, L, R, ldsh, s), BR_CASES(LAUNCH_H2));
 #undef LAUNCH_H2
 #undef LAUNCH_H2_
         HIP_TRY(c, hipGetLastError());
@@ -281,7 +293,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         if (dg) hipLaunchKernelGGL((blind_rotate_kernel_w2<LL, true>), dim3((unsigned)R), dim3(128), ldsw, s, a); \
         else if (pairs) hipLaunchKernelGGL((blind_rotate_kernel_w2<LL, false, 2>), dim3((unsigned)((R + 1) / 2)), dim3(256), 2 * ldsw, s, a); \
         else hipLaunchKernelGGL((blind_rotate_kernel_w2<LL, false>), dim3((unsigned)R), dim3(128), ldsw, s, a)
-        BR_CASES_ANY_L(LAUNCH_W2)
+        TV_OR(tv_launch_w2(c, a, tv, Ltv, pairs, R, ldsw, s), BR_CASES_ANY_L(LAUNCH_W2));
 #undef LAUNCH_W2
         HIP_TRY(c, hipGetLastError());
         if ((L == 2 || L == 3) && !c->br_rt_l) name_kernel(c, pairs ? "blind_rotate_kernel_w2<%d,rw2>" : "blind_rotate_kernel_w2<%d>", L);
@@ -304,7 +316,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         else if (group) LAUNCH_V3_GROUP(LL, false);                                                                \
         else if (dg) hipLaunchKernelGGL((blind_rotate_kernel_v3<LL, 8, true, true>), dim3((unsigned)R), dim3(64), lds3, s, a);     \
         else hipLaunchKernelGGL((blind_rotate_kernel_v3<LL, 8, true, false>), dim3((unsigned)R), dim3(64), lds3, s, a)
-        BR_CASES_ANY_L(LAUNCH_V3)
+        TV_OR(tv_launch_v3(c, a, tv, Ltv, group, R, lds3, s), BR_CASES_ANY_L(LAUNCH_V3));
 #undef LAUNCH_V3
 #undef LAUNCH_V3_GROUP
         HIP_TRY(c, hipGetLastError());
@@ -379,8 +391,11 @@ static std::vector<K2Seg> k2_partition(size_t R, size_t cus, bool allow_w3)
     return seg;
 }
 
-int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s)
+#undef TV_OR
+
+int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, const TvPtrs *tv)
 {
+    if (tv && c->measure_margin) return c->set_err(TFHE_ERR_STATE, "bootstrap_tv: no DIAG instantiation of the TV kernels (measure_margin is on)");
     DiagArgs diag;
     int32_t rc = prepare_diag(c, R, s, diag);
     if (rc) return rc;
@@ -395,12 +410,18 @@ int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s)
         const size_t resident = 8 * (size_t)c->cu_count;      // rotations of blind_rotate_kernel_v3 on the chip
         if (R > resident && R % resident > 0 && R % resident <= (size_t)c->br_small) seg = {{R - R % resident, -1}, {R % resident, -1}};
     }
-    if (seg.empty()) return launch_blind_rotate_part(c, 0, R, mu, s, diag);
-    if (seg.size() == 1) return launch_blind_rotate_part(c, 0, R, mu, s, diag, seg[0].kind);
+    // (a TV batch's kernels carry "+tv" in tfhe_last_kernel_name)
+    auto part = [&](size_t first, size_t count, int kind) {
+        const int32_t r = launch_blind_rotate_part(c, first, count, mu, s, diag, kind, tv);
+        if (!r && tv) c->last_kernel += "+tv";
+        return r;
+    };
+    if (seg.empty()) return part(0, R, -1);
+    if (seg.size() == 1) return part(0, R, seg[0].kind);
     std::string names;
     size_t first = 0;
     for (const K2Seg &sg : seg) {
-        rc = launch_blind_rotate_part(c, first, sg.count, mu, s, diag, sg.kind);
+        rc = part(first, sg.count, sg.kind);
         if (rc) return rc;
         if (names.empty() || names.substr(names.rfind(" + ") == std::string::npos ? 0 : names.rfind(" + ") + 3) != c->last_kernel)
             names += (names.empty() ? "" : " + ") + c->last_kernel;

@@ -495,18 +495,24 @@ int32_t tfhe_gates_batch_wait(tfhe_ctx *c, int32_t ticket) try
 }
 ABI_CATCH(c, "tfhe_gates_batch_wait")
 
-int32_t tfhe_bootstrap_batch(tfhe_ctx *c, int32_t mu, const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch) try
+// The host-table form of a TV batch: tables [n_tv][N], index [B] (checked by the caller) or NULL = table 0 for every row.
+struct TvHost { const int32_t *tv; int32_t n_tv; const int32_t *index; };
+
+// tfhe_bootstrap_batch (tv == NULL) and tfhe_bootstrap_tv_batch on a device context or, row-split, on the kids of a multi-device one
+static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const TvHost *tv, const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch)
 {
-    ENTER_CTX(c);
-    if (!c) return TFHE_ERR_INVALID_ARG;
-    if (B < 0 || (B > 0 && (!in || !out))) return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_batch: NULL argument or negative B");
-    if (B == 0) return TFHE_OK;
-    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "bootstrap_batch: context is multi-key");
     if (c->multi()) {
         const size_t wi = (size_t)c->P.n + 1, wo = with_keyswitch ? wi : (size_t)c->P.k * c->P.N + 1;
-        return multi_rows(c, B, [&](tfhe_ctx *k, int64_t s0, int64_t cnt) { return tfhe_bootstrap_batch(k, mu, in + (size_t)s0 * wi, out + (size_t)s0 * wo, cnt, with_keyswitch); });
+        return multi_rows(c, B, [&](tfhe_ctx *k, int64_t s0, int64_t cnt) {
+            alloc_checkpoint();
+            CallGuard kid_guard(k);
+            if (!kid_guard.ok) return (int32_t)TFHE_ERR_STATE;
+            TvHost part;
+            if (tv) part = TvHost{tv->tv, tv->n_tv, tv->index ? tv->index + s0 : nullptr};      // every device gets every table
+            return bootstrap_rows(k, who, mu, tv ? &part : nullptr, in + (size_t)s0 * wi, out + (size_t)s0 * wo, cnt, with_keyswitch);
+        });
     }
-    if (!c->have_bk || (with_keyswitch && !c->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "bootstrap_batch: key not loaded");
+    if (!c->have_bk || (with_keyswitch && !c->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: key not loaded", who);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }
@@ -516,13 +522,23 @@ int32_t tfhe_bootstrap_batch(tfhe_ctx *c, int32_t mu, const int32_t *in, int32_t
     HIP_TRY(c, hipMemcpyAsync(c->io[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(c, c->bara.reserve((size_t)B * (n + 1) * 4));
     HIP_TRY(c, c->ext.reserve((size_t)B * (kNn + 1) * 4));
+    TvPtrs tvd{nullptr, nullptr};
+    if (tv) {
+        const size_t tv_bytes = (size_t)tv->n_tv * c->P.N * 4, idx_bytes = (size_t)B * 4;
+        HIP_TRY(c, c->tv.reserve(tv_bytes));
+        HIP_TRY(c, c->tv_index.reserve(idx_bytes));
+        HIP_TRY(c, hipMemcpyAsync(c->tv.p, tv->tv, tv_bytes, hipMemcpyHostToDevice, s));
+        if (tv->index) HIP_TRY(c, hipMemcpyAsync(c->tv_index.p, tv->index, idx_bytes, hipMemcpyHostToDevice, s));
+        else HIP_TRY(c, hipMemsetAsync(c->tv_index.p, 0, idx_bytes, s));
+        tvd = TvPtrs{(const int32_t *)c->tv.p, (const int32_t *)c->tv_index.p};
+    }
     next_timing_slot(c);
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     hipLaunchKernelGGL(modswitch_kernel, dim3((unsigned)B), dim3(256), 0, s, (const int32_t *)c->io[0].p, (int32_t *)c->bara.p, n,
                        ilog2i(2 * c->P.N));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    int32_t rc = launch_blind_rotate(c, (size_t)B, mu, s);
+    int32_t rc = launch_blind_rotate(c, (size_t)B, mu, s, tv ? &tvd : nullptr);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
     if (with_keyswitch) {
@@ -548,7 +564,37 @@ int32_t tfhe_bootstrap_batch(tfhe_ctx *c, int32_t mu, const int32_t *in, int32_t
     c->last_rotations = B;
     return TFHE_OK;
 }
+
+int32_t tfhe_bootstrap_batch(tfhe_ctx *c, int32_t mu, const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    if (B < 0 || (B > 0 && (!in || !out))) return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_batch: NULL argument or negative B");
+    if (B == 0) return TFHE_OK;
+    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "bootstrap_batch: context is multi-key");
+    return bootstrap_rows(c, "bootstrap_batch", mu, nullptr, in, out, B, with_keyswitch);
+}
 ABI_CATCH(c, "tfhe_bootstrap_batch")
+
+// Programmable bootstrapping: tfhe_bootstrap_batch with row g's test polynomial tv[tv_index[g]] instead of (mu, ..., mu).
+int32_t tfhe_bootstrap_tv_batch(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, const int32_t *in, int32_t *out, int64_t B,
+                                int32_t with_keyswitch) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    if (B < 0 || (B > 0 && (!in || !out || !tv))) return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_tv_batch: NULL argument or negative B");
+    if (n_tv < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_tv_batch: n_tv = %d (at least one table)", n_tv);
+    if (tv_index)
+        for (int64_t g = 0; g < B; g++)
+            if (tv_index[g] < 0 || tv_index[g] >= n_tv)
+                return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_tv_batch: tv_index[%lld] = %d is outside [0, %d)", (long long)g, tv_index[g], n_tv);
+    if (B == 0) return TFHE_OK;
+    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "bootstrap_tv_batch: context is multi-key");
+    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "bootstrap_tv_batch: measure_margin is on (the TV kernels have no DIAG instantiation)");
+    const TvHost th{tv, n_tv, tv_index};
+    return bootstrap_rows(c, "bootstrap_tv_batch", 0, &th, in, out, B, with_keyswitch);
+}
+ABI_CATCH(c, "tfhe_bootstrap_tv_batch")
 
 int32_t tfhe_keyswitch_batch(tfhe_ctx *c, const int32_t *in, int32_t *out, int64_t B) try
 {

@@ -187,7 +187,7 @@ __host__ inline int threads_for(int N)
 
 // ---- single key (bootstrap.jl:19-82, tgsw.jl:99-129) --------------------------------------------------------------
 template <bool MARGIN>
-__global__ __launch_bounds__(512) void blind_rotate_kernel(Args P)
+__global__ __launch_bounds__(512) void TV_KERNEL(blind_rotate_kernel)(TV_ARGS(Args) P)
 {
     unsigned long long dg_t0 = 0, dg_r0 = 0;
     diag_begin<MARGIN>(dg_t0, dg_r0);
@@ -209,10 +209,11 @@ __global__ __launch_bounds__(512) void blind_rotate_kernel(Args P)
 
     {   // accum = (0, ..., 0, X^{-barb} (mu, ..., mu))     bootstrap.jl:54-56,78 ; tlwe.jl:77-81
         const int barb = bara[P.n] & (2 * N - 1);
+        const int32_t *tvp = kTV ? tv_of(P, w, N) : nullptr;
         for (int e = tid; e < K1 * N; e += nt) {
             const int c = e >> P.log2N, j = e & (N - 1);
             const int idx = (j + barb) & (2 * N - 1);
-            acc[e] = c + 1 < K1 ? 0 : (idx & N) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
+            acc[e] = c + 1 < K1 ? 0 : kTV ? tv_coef(tvp, idx, N) : (idx & N) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
         }
     }
     __syncthreads();

@@ -12,6 +12,35 @@
 
 using namespace tfhe;
 
+// Programmable bootstrapping (bootstrap.jl:50-59 with any test polynomial): the translation unit that defines TFHE_TV_KERNELS
+// (engine_tv.hip) compiles every single-key blind-rotation kernel as its TV form, named <kernel>_tv, which starts rotation w from
+// X^{-barb} tv[tv_index[w]] instead of X^{-barb} (mu, ..., mu).  Everywhere else kTV is false and the kernels are what they were.
+// A TV kernel takes its family's argument struct extended by the tables (WithTv): the structs themselves are unchanged, so no kernel
+// argument of the existing kernels moves (blind_rotate_kernel_h2's second argument and the hidden arguments follow the first).
+template <class A>
+struct WithTv : A {
+    const int32_t *tv;        // [n_tv][N] test polynomials
+    const int32_t *tv_index;  // [R] the table of each rotation, in [0, n_tv)
+};
+#ifdef TFHE_TV_KERNELS
+#define TV_KERNEL(name) name##_tv
+#define TV_ARGS(A) WithTv<A>
+constexpr bool kTV = true;
+#else
+#define TV_KERNEL(name) name
+#define TV_ARGS(A) A
+constexpr bool kTV = false;
+#endif
+// the test polynomial of rotation w, tv + N tv_index[w] (TV kernels; NULL for the others): the index is read once, by a vector load
+// made wave-uniform
+template <class A>
+__device__ __forceinline__ const int32_t *tv_of(const A &, size_t, int) { return nullptr; }
+template <class A>
+__device__ __forceinline__ const int32_t *tv_of(const WithTv<A> &P, size_t w, int N)
+{
+    return P.tv + (size_t)__builtin_amdgcn_readfirstlane(P.tv_index[w]) * N;
+}
+
 // Diagnostics written only by the DIAG instantiations (tfhe_set_option("measure_margin", 1)):
 //   margin_bits[w] = bit pattern of the largest |pre-round value - nearest integer| of rotation w (non-negative doubles
 //                    order like their bit patterns, so waves combine with an integer atomicMax; zeroed before the launch),
@@ -251,6 +280,26 @@ __device__ __forceinline__ void init_body_poly(int lane, int barb, int32_t mu, i
         b[m] = (idx & kN) ? (int32_t)(0u - (uint32_t)mu) : mu;
     }
     store_cur<16>(lane, b, img);
+}
+// coefficient of X^{-barb} v at idx = (j + barb) mod 2N: v[idx mod N], negated when idx & N (init_body_poly's rule, the table read for mu)
+__device__ __forceinline__ int32_t tv_coef(const int32_t *v, int idx, int N)
+{
+    const int32_t x = v[idx & (N - 1)];
+    return (idx & N) ? (int32_t)(0u - (uint32_t)x) : x;
+}
+// the body polynomial of rotation w: init_body_poly, or its TV form
+template <class A>
+__device__ __forceinline__ void init_body(int lane, int barb, const A &P, size_t w, int32_t *img)
+{
+    if constexpr (kTV) {
+        const int32_t *v = tv_of(P, w, kN);
+        int32_t b[16];
+#pragma unroll
+        for (int m = 0; m < 16; m++) b[m] = tv_coef(v, (lane + 64 * m + barb) & (2 * kN - 1), kN);
+        store_cur<16>(lane, b, img);
+    } else {
+        init_body_poly(lane, barb, P.mu, img);
+    }
 }
 __device__ __forceinline__ void init_zero_poly(int lane, int32_t *img)
 {

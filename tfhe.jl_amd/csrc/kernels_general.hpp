@@ -24,7 +24,7 @@ struct BrGenArgs {
 };
 
 template <int NBLK /* N / 64: 16 or 32 */, bool MARGIN = false>
-__global__ __launch_bounds__(64, 1) void blind_rotate_kernel_general(BrGenArgs P)
+__global__ __launch_bounds__(64, 1) void TV_KERNEL(blind_rotate_kernel_general)(TV_ARGS(BrGenArgs) P)
 {
     constexpr int N = 64 * NBLK, H = NBLK / 16, kImgN = kMir + N;
     unsigned long long dg_t0 = 0, dg_r0 = 0;
@@ -50,12 +50,13 @@ __global__ __launch_bounds__(64, 1) void blind_rotate_kernel_general(BrGenArgs P
     tw2_lds[lane] = P.tw2[lane];
     {   // accum = (0, ..., 0, X^{-barb} (mu, ..., mu))     bootstrap.jl:54-56,78
         const int barb = bara[P.n] & (2 * N - 1);
+        const int32_t *tvp = kTV ? tv_of(P, w, N) : nullptr;
         int32_t v[NBLK];
         for (int c = 0; c < K1; c++) {
 #pragma unroll
             for (int m = 0; m < NBLK; m++) {
                 const int idx = (lane + 64 * m + barb) & (2 * N - 1);
-                v[m] = c + 1 < K1 ? 0 : (idx & N) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
+                v[m] = c + 1 < K1 ? 0 : kTV ? tv_coef(tvp, idx, N) : (idx & N) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
             }
             store_cur<NBLK>(lane, v, acc + c * kImgN);
         }

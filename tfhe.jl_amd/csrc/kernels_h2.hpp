@@ -181,7 +181,7 @@ __device__ __forceinline__ void h2_recombine(int lane, const cplx (&own)[4], con
 //  recombination (it shares the owner's SIMD and idles through the inverse phase): 1.615-1.621 against 1.596-1.628 ms, l = 3:
 //  2.45 against 2.47-2.48 ms — inside the spread, not kept.)
 template <int L, bool MARGIN = false>
-__global__ __launch_bounds__(256 * L, 1) void blind_rotate_kernel_h2(BrArgs P, H2Tables HT)
+__global__ __launch_bounds__(256 * L, 1) void TV_KERNEL(blind_rotate_kernel_h2)(TV_ARGS(BrArgs) P, H2Tables HT)
 {
     constexpr int K1 = 2, W = 2 * K1 * L;
     // Round 6: the rotation is SCATTERED by the owners instead of gathered by every wave.  All 4 l waves of a rotation need
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256 * L, 1) void blind_rotate_kernel_h2(BrArgs P, H
         tw.tw3[q] = HT.tw3q[q * 4 + (lane & 3)];
     }
     if (wv == 0) init_zero_poly(lane, acc_all);
-    else if (wv == 1) init_body_poly(lane, bara[P.n] & (2 * kN - 1), P.mu, acc_all + kImg);
+    else if (wv == 1) init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_all + kImg);
     __syncthreads();
 
     // this lane's four frequencies f = 2 k' + h, k' = q + 4 q2 + 16 q3 + 64 q4: in the key's (v3) order frequency f sits

@@ -10,7 +10,7 @@
 // 3 inverse transforms per step, out[co] += D[p, c] .* BK_i[p, c].a[co] for c, co in 0..2 (tgsw.jl:125-129).
 constexpr int kK2LdsBytes = 3 * kN * 4 + (kXchElems + 64) * (int)sizeof(cplx);      // per rotation
 template <int L, bool MARGIN = false, int RW = 1 /* rotations per workgroup, in lockstep (as blind_rotate_kernel_v3) */>
-__global__ __launch_bounds__(64 * RW, 2) void blind_rotate_kernel_k2(BrArgs P)
+__global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_k2)(TV_ARGS(BrArgs) P)
 {
     constexpr int K1 = 3;
     unsigned long long dg_t0 = 0, dg_r0 = 0;
@@ -46,12 +46,13 @@ __global__ __launch_bounds__(64 * RW, 2) void blind_rotate_kernel_k2(BrArgs P)
     tw2_lds[lane] = P.T.tw2[lane];
     {
         const int barb = bara[P.n] & (2 * kN - 1);
+        const int32_t *v = kTV ? tv_of(P, w, kN) : nullptr;
 #pragma unroll
         for (int m = 0; m < 16; m++) {
             const int idx = (lane + 64 * m + barb) & (2 * kN - 1);
             acc_lds[lane + 64 * m] = 0;
             acc_lds[kN + lane + 64 * m] = 0;
-            acc_lds[2 * kN + lane + 64 * m] = (idx & kN) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
+            acc_lds[2 * kN + lane + 64 * m] = kTV ? tv_coef(v, idx, kN) : (idx & kN) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
         }
     }
     WAVE_LDS_FENCE();
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(64 * RW, 2) void blind_rotate_kernel_k2(BrArgs P)
 // larger one when that is what is left (k2_partition).
 constexpr int kK2W3LdsBytes = 3 * kImg * 4 + (3 * kXchElems + 3 * kM + 64) * (int)sizeof(cplx);      // per rotation
 template <int L, bool MARGIN = false>
-__global__ __launch_bounds__(192, 2) void blind_rotate_kernel_k2w3(BrArgs P)
+__global__ __launch_bounds__(192, 2) void TV_KERNEL(blind_rotate_kernel_k2w3)(TV_ARGS(BrArgs) P)
 {
     constexpr int K1 = 3;
     unsigned long long dg_t0 = 0, dg_r0 = 0;
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(192, 2) void blind_rotate_kernel_k2w3(BrArgs P)
 #pragma unroll
     for (int q = 0; q < 8; q++) tw1f[q] = P.T.tw1f[q * 64 + lane];
     if (threadIdx.x < 64) tw2_lds[threadIdx.x] = P.T.tw2[threadIdx.x];
-    if (wv == 2) init_body_poly(lane, bara[P.n] & (2 * kN - 1), P.mu, acc_lds);
+    if (wv == 2) init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds);
     else init_zero_poly(lane, acc_lds);
     __syncthreads();
 

@@ -222,7 +222,7 @@ __device__ __forceinline__ void finish_2048(int lane, const cplx (&alpha)[8], co
 // in the stamped builds the rotate phase shrinks from 8.9 k to 3.9 k cycles of a 48 k-cycle step and the other phases take
 // up most of what it frees — a wave's issue slots were being used by its partner, not idle.
 template <int L, bool MARGIN = false, int RW = 2>
-__global__ __launch_bounds__(128 * RW, 2) void blind_rotate_kernel_n2048x(Br2048Args P)
+__global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(blind_rotate_kernel_n2048x)(TV_ARGS(Br2048Args) P)
 {
     constexpr int K1 = 2;
     // Every constant twist in tan form (round 6; twist32_tan): 92 FP64 instructions less per wave and step, 1 - 1.4 % of the launch.  (Kept
@@ -270,11 +270,12 @@ __global__ __launch_bounds__(128 * RW, 2) void blind_rotate_kernel_n2048x(Br2048
     if (lane0 == 0) pair_flags[wib & 1] = 0;
     {
         const int barb = bara[P.n] & (2 * kN2 - 1);
+        const int32_t *tvp = kTV ? tv_of(P, w, kN2) : nullptr;
         int32_t v[32];
 #pragma unroll
         for (int m = 0; m < 32; m++) {
             const int idx = (lane0 + 64 * m + barb) & (2 * kN2 - 1);
-            v[m] = !wave1_0 ? 0 : (idx & kN2) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
+            v[m] = !wave1_0 ? 0 : kTV ? tv_coef(tvp, idx, kN2) : (idx & kN2) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
         }
         store_cur<32>(lane0, v, acc_own);
     }

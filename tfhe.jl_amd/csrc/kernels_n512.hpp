@@ -75,7 +75,7 @@ __device__ __forceinline__ void untwist_add4(const cplx (&y)[4], int32_t (&acc)[
 // L = 0: the decomposition length is a run-time value (P.l), as in blind_rotate_kernel_v3<0, ...>.  RW rotations per workgroup in
 // lockstep (one barrier every kV3SyncEvery steps: they stream the same key lines together), a padding wave repeats the last rotation.
 template <int L, bool MARGIN = false, int RW = 1>
-__global__ __launch_bounds__(64 * RW, 3) void blind_rotate_kernel_n512(N512Args P)
+__global__ __launch_bounds__(64 * RW, 3) void TV_KERNEL(blind_rotate_kernel_n512)(TV_ARGS(N512Args) P)
 {
     constexpr int K1 = 2;
     unsigned long long dg_t0 = 0, dg_r0 = 0;
@@ -105,6 +105,7 @@ __global__ __launch_bounds__(64 * RW, 3) void blind_rotate_kernel_n512(N512Args 
     }
     {   // accum = (0, X^{-barb} (mu, ..., mu))     bootstrap.jl:54-56,78 ; tlwe.jl:77-81
         const int barb = bara[P.n] & (2 * kN5 - 1);
+        const int32_t *tvp = kTV ? tv_of(P, w, kN5) : nullptr;
         int32_t v[8];
 #pragma unroll
         for (int m = 0; m < 8; m++) v[m] = 0;
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(64 * RW, 3) void blind_rotate_kernel_n512(N512Args 
 #pragma unroll
         for (int m = 0; m < 8; m++) {
             const int idx = (lane + 64 * m + barb) & (2 * kN5 - 1);
-            v[m] = (idx & kN5) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
+            v[m] = kTV ? tv_coef(tvp, idx, kN5) : (idx & kN5) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
         }
         store_cur<8>(lane, v, acc_lds + kImg5);
     }
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(64) void bk_permute_c128_kernel_n512(const cplx *__
 // own polynomial.  14.8 KB of LDS per rotation.
 constexpr int kN512W2LdsBytes = 2 * kImg5 * 4 + 2 * kH2Buf * (int)sizeof(cplx);      // per rotation
 template <int L, bool MARGIN = false>
-__global__ __launch_bounds__(128, 3) void blind_rotate_kernel_n512w2(N512Args P)
+__global__ __launch_bounds__(128, 3) void TV_KERNEL(blind_rotate_kernel_n512w2)(TV_ARGS(N512Args) P)
 {
     constexpr int K1 = 2;
     unsigned long long dg_t0 = 0, dg_r0 = 0;
@@ -254,11 +255,12 @@ __global__ __launch_bounds__(128, 3) void blind_rotate_kernel_n512w2(N512Args P)
     }
     {
         const int barb = bara[P.n] & (2 * kN5 - 1);
+        const int32_t *tvp = kTV ? tv_of(P, w, kN5) : nullptr;
         int32_t v[8];
 #pragma unroll
         for (int m = 0; m < 8; m++) {
             const int idx = (lane + 64 * m + barb) & (2 * kN5 - 1);
-            v[m] = wv == 0 ? 0 : (idx & kN5) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
+            v[m] = wv == 0 ? 0 : kTV ? tv_coef(tvp, idx, kN5) : (idx & kN5) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
         }
         store_cur<8>(lane, v, acc_lds);
     }

@@ -26,7 +26,7 @@ constexpr int kV3LdsBytes = 2 * kImg * 4 + (kXchElems + 64) * (int)sizeof(cplx);
 //   * the first transform of a step writes the spectrum accumulators (a product, not a multiply-add): no zeroing.
 template <int L, int KPF /* key values prefetched per transform: 16 = whole chunk, 8 = half */, bool TW2REG = false /* pass-B twiddles in registers instead of LDS */,
           bool MARGIN = false /* diagnostics: rounding margin + in-kernel clock (DiagArgs) */, int RW = 1 /* rotations per workgroup */>
-__global__ __launch_bounds__(64 * RW, 2) void blind_rotate_kernel_v3(BrArgs P)
+__global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(TV_ARGS(BrArgs) P)
 {
     constexpr int K1 = 2;
     // KPF == 8: the first half of a transform's key chunk is requested a transform ahead, the first KMID values of the
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64 * RW, 2) void blind_rotate_kernel_v3(BrArgs P)
         for (int q = 1; q < 8; q++) tw2r[q] = P.T.tw2[q * 8 + (lane & 7)];
     }
     init_zero_poly(lane, acc_lds);
-    init_body_poly(lane, bara[P.n] & (2 * kN - 1), P.mu, acc_lds + kImg);
+    init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds + kImg);
     WAVE_LDS_FENCE();
 
     double worst = 0.0;

@@ -19,7 +19,7 @@ constexpr int kW2LdsBytes = 2 * kImg * 4 + (2 * kXchElems + 64) * (int)sizeof(cp
 // RW rotations per workgroup (RW = 2: the step barrier then spans both rotations, which keeps them in lockstep and lets
 // them share their key reads in the CU's L1, as in the other kernels; a padding rotation repeats the last one and stores nothing)
 template <int L, bool MARGIN = false, int RW = 1>
-__global__ __launch_bounds__(128 * RW, 2) void blind_rotate_kernel_w2(BrArgs P)
+__global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(blind_rotate_kernel_w2)(TV_ARGS(BrArgs) P)
 {
     constexpr int K1 = 2;
     unsigned long long dg_t0 = 0, dg_r0 = 0;
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(128 * RW, 2) void blind_rotate_kernel_w2(BrArgs P)
 #pragma unroll
     for (int q = 0; q < 8; q++) tw1f[q] = P.T.tw1f[q * 64 + lane];
     if (tid < 64) tw2_lds[tid] = P.T.tw2[tid];
-    if (wv) init_body_poly(lane, bara[P.n] & (2 * kN - 1), P.mu, acc_lds);
+    if (wv) init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds);
     else init_zero_poly(lane, acc_lds);
     __syncthreads();
     STAMP_DECL;

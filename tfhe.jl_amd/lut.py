@@ -1,0 +1,75 @@
+"""Programmable bootstrapping: any function of a small encrypted integer in one blind rotation.
+
+A message m of the space Z_p (p a power of two, 2 <= p <= N/2) is encrypted at the phase (2m + 1)/(4p): the centre of the m-th
+of 2p equal windows of the torus, in the half [0, 1/2) (the other half is the padding).  A phase within +-1/(4p) of that centre
+still decodes to m.  The blind rotation of a sample with the test polynomial v (Engine.bootstrap_tv, tfhe_bootstrap_tv_batch;
+bootstrap.jl:50-59) returns the body v[phi] for phi in [0, N) and -v[phi - N] for phi in [N, 2N), phi = the modulus-switched
+phase; make_test_vector(f, p, N, q) fills the N / p coefficients of window m with lut_encode(f(m), q), so the result encrypts f(m)
+in Z_q.  The output's noise is that of a fresh bootstrap, whatever the input's was, and samples combine linearly in between
+(LweSampleArray's +, -, integer scale and add_constant), which is how the functions chain.
+"""
+import numpy as np
+
+from .lwe import LweSampleArray, lwe_encrypt_many, lwe_phase
+from .numeric import wrap32
+
+
+def _log2(p, what="p"):
+    p = int(p)
+    if p < 2 or p & (p - 1):
+        raise ValueError(f"{what} = {p}: a power of two >= 2")
+    return p.bit_length() - 1
+
+
+def lut_encode(m, p):
+    """The Torus32 phase of message m in Z_p: encode_message(2m + 1, 4p) (numeric-functions.jl:42-45) — the centre of the
+    m-th window of width 1/(2p); anything within +-1/(4p) of it decodes to m."""
+    s = 32 - (_log2(p) + 2)
+    return wrap32((2 * np.asarray(m, np.int64) + 1) << s)
+
+
+def lut_decode(phase, p):
+    """The window a Torus32 phase lies in: (uint32(phase) >> (32 - log2 2p)) & (2p - 1).  A value >= p means the phase
+    crossed into the padding half: the noise broke the padding bit."""
+    s = 32 - (_log2(p) + 1)
+    return ((np.asarray(phase, np.int64) & 0xFFFFFFFF) >> s) & (2 * int(p) - 1)
+
+
+def lut_encrypt(rng, secret_key, m, p):
+    """Messages m (ints in [0, p)) of Z_p encrypted under `secret_key` (a SecretKey) with its LWE noise: LweSampleArray."""
+    m = np.atleast_1d(np.asarray(m, np.int64))
+    if np.any((m < 0) | (m >= p)):
+        raise ValueError(f"messages must lie in [0, {p})")
+    return LweSampleArray(lwe_encrypt_many(rng, lut_encode(m, p).astype(np.int64), secret_key.params.lwe_noise_stddev, secret_key.key))
+
+
+def lut_decrypt(secret_key, samples, p):
+    """lut_decode of each sample's phase; values >= p flag a broken padding bit."""
+    data = samples.data if isinstance(samples, LweSampleArray) else np.asarray(samples, np.int32)
+    return lut_decode(lwe_phase(data, secret_key.key), p)
+
+
+def make_test_vector(f, p, N, q=None):
+    """The test polynomial of x -> f(x), Z_p -> Z_q (q defaults to p): v[j] = lut_encode(f(floor(j p / N)), q), int32 [N].
+    2 <= p <= N / 2, both powers of two."""
+    q = p if q is None else q
+    _log2(p)
+    _log2(q, "q")
+    if p > N // 2:
+        raise ValueError(f"p = {p} > N/2 = {N // 2}")
+    vals = np.array([int(f(m)) % q for m in range(p)], np.int64)
+    return lut_encode(vals[(np.arange(N) * p) // N], q).astype(np.int32)
+
+
+def programmable_bootstrap(ck, samples, tables_or_functions, index=None, p=8, q=None, with_keyswitch=True, device=0):
+    """f(m) for every sample of m in Z_p, in one batch of blind rotations on the GPU.
+
+    `tables_or_functions`: one or a list of callables Z_p -> Z_q (made into test polynomials by make_test_vector) or int32
+    test polynomials [N]; `index[g]` picks row g's (None: the first for every row).  p, q: powers of two, 2 <= p <= N/2; an input
+    phase must lie within +-1/(4p) of its message's centre.  Returns an LweSampleArray of messages in Z_q (keyswitched back to
+    the LWE key unless with_keyswitch is False, then [B][k N + 1] words under the extracted TLWE key)."""
+    eng = ck.engine(device)
+    items = tables_or_functions if isinstance(tables_or_functions, (list, tuple)) else [tables_or_functions]
+    tables = np.stack([make_test_vector(t, p, eng.N, q) if callable(t) else np.asarray(t, np.int32) for t in items])
+    data = samples.data if isinstance(samples, LweSampleArray) else np.asarray(samples, np.int32)
+    return LweSampleArray(eng.bootstrap_tv(tables, data, index=index, with_keyswitch=with_keyswitch))

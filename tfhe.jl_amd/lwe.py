@@ -54,6 +54,52 @@ class LweSampleArray:
     def from_samples(samples):
         return LweSampleArray(np.stack([s.flat() for s in samples]))
 
+    # Linear combinations of samples (lwe.jl:62-90, every word modulo 2^32): the phase of the result is the same combination of
+    # the phases, and so is the noise — what chaining programmable bootstraps (lut.py) needs between them.
+    def __add__(self, other):
+        return LweSampleArray(lwe_add(self.data, _data(other)))
+
+    def __sub__(self, other):
+        return LweSampleArray(lwe_sub(self.data, _data(other)))
+
+    def __neg__(self):
+        return LweSampleArray(lwe_scale(self.data, -1))
+
+    def __mul__(self, k):
+        return LweSampleArray(lwe_scale(self.data, k))
+
+    __rmul__ = __mul__
+
+    def add_constant(self, mu):
+        """+ the trivial sample (0, ..., 0, mu): the phase moves by mu (Torus32), the noise stays."""
+        return LweSampleArray(lwe_add_constant(self.data, mu))
+
+
+def _data(x):
+    return x.data if isinstance(x, LweSampleArray) else np.asarray(x, np.int32)
+
+
+def lwe_add(x, y):
+    """x + y word by word (int32 [..][n+1], wrap-around)."""
+    return wrap32(np.asarray(x, np.int64) + np.asarray(y, np.int64)).astype(np.int32)
+
+
+def lwe_sub(x, y):
+    """x - y word by word (wrap-around)."""
+    return wrap32(np.asarray(x, np.int64) - np.asarray(y, np.int64)).astype(np.int32)
+
+
+def lwe_scale(x, k):
+    """k x for an integer k (wrap-around); the noise grows by |k|."""
+    return wrap32(np.asarray(x, np.int64) * int(k)).astype(np.int32)
+
+
+def lwe_add_constant(x, mu):
+    """x + (0, ..., 0, mu): mu (Torus32, or one per row) added to the body."""
+    out = np.array(x, np.int32, copy=True)
+    out[..., -1] = wrap32(out[..., -1].astype(np.int64) + np.asarray(mu, np.int64))
+    return out
+
 
 def lwe_encrypt(rng, message, alpha, key: LweKey):
     """lwe.jl:38-43 — b = gaussian(message, alpha) + <a, s>"""
