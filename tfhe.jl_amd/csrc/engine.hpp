@@ -8,7 +8,8 @@
 //   engine_circuits.hip   wire table, tfhe_gates_level, rows between the devices of a context         ("circuits")
 //   engine_multikey.hip   tfhe_mk_gate_nand_batch, tfhe_mk_gates_batch and their kernels              ("multi-key")
 //   engine_diag.hip       timing, rounding margin, in-kernel clock, options                           ("diagnostics")
-//   engine_tv.hip         the TV kernels (programmable bootstrapping) and their launches              ("tv")
+//   engine_tv.hip         the TV kernels (programmable bootstrapping) and the TV form of the launchers ("tv")
+//   br_launch.hpp         the launch of each single-key blind-rotation family, compiled by engine_dispatch.hip and engine_tv.hip
 //   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
@@ -428,16 +429,25 @@ int32_t launch_trivial(tfhe_ctx *c, size_t T, const int32_t *d_in0, const int32_
 int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s);
 int32_t run_mk_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t B, const int32_t *d_in0, const int32_t *d_in1, const int32_t *d_in2,
                      int32_t *d_out, const int32_t *ia, const int32_t *ib, const int32_t *ic, const int32_t *io, hipStream_t s);
-// engine_tv.hip: the TV form of each launch of launch_blind_rotate_part (same geometry)
-int32_t tv_launch_anyn(tfhe_ctx *c, const anyn::Args &g, const TvPtrs &tv, size_t R, unsigned nt, size_t lds, hipStream_t s);
-int32_t tv_launch_n512w2(tfhe_ctx *c, const N512Args &b, const TvPtrs &tv, int L, size_t R, size_t lds, hipStream_t s);
-int32_t tv_launch_n512(tfhe_ctx *c, const N512Args &b, const TvPtrs &tv, int L, bool group, size_t R, size_t lds, hipStream_t s);
-int32_t tv_launch_general(tfhe_ctx *c, const BrGenArgs &g, const TvPtrs &tv, bool n2048, size_t R, size_t lds, hipStream_t s);
-int32_t tv_launch_n2048(tfhe_ctx *c, const Br2048Args &b, const TvPtrs &tv, int rw, unsigned nblk, size_t lds, hipStream_t s);
-int32_t tv_launch_k2w3(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, size_t R, size_t lds, hipStream_t s);
-int32_t tv_launch_k2(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, bool grouped, size_t blocks, size_t lds, hipStream_t s);
-int32_t tv_launch_h2(tfhe_ctx *c, const BrArgs &a, const H2Tables &ht, const TvPtrs &tv, int L, size_t R, size_t lds, hipStream_t s);
-int32_t tv_launch_w2(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, bool pairs, size_t R, size_t lds, hipStream_t s);
-int32_t tv_launch_v3(tfhe_ctx *c, const BrArgs &a, const TvPtrs &tv, int L, bool group, size_t R, size_t lds, hipStream_t s);
+// br_launch.hpp: one launch of each single-key blind-rotation family with the instantiation and geometry launch_blind_rotate_part
+// decided, compiled in engine_dispatch.hip for the mu / DIAG kernels and in engine_tv.hip for the TV kernels (arguments WithTv<A>,
+// declared here for the dispatcher)
+struct BrLaunch {
+    int L;                 // decomposition-length instantiation: 2, 3, or 0 (run-time l)
+    int rw;                // rotations per workgroup
+    bool dg;               // the DIAG instantiation (measure_margin)
+    dim3 grid, block;
+    size_t lds;            // dynamic LDS per workgroup, bytes
+};
+int32_t br_launch_anyn(tfhe_ctx *c, const WithTv<anyn::Args> &a, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_n512w2(tfhe_ctx *c, const WithTv<N512Args> &a, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_n512(tfhe_ctx *c, const WithTv<N512Args> &a, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_general(tfhe_ctx *c, const WithTv<BrGenArgs> &a, bool n2048, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_n2048x(tfhe_ctx *c, const WithTv<Br2048Args> &a, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_k2w3(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_k2(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_h2(tfhe_ctx *c, const WithTv<BrArgs> &a, const H2Tables &ht, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_w2(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
+int32_t br_launch_v3(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
 // engine_circuits.hip
 int32_t pull_wires(tfhe_ctx *c, int dst, const int32_t *wires, int64_t count);

@@ -1,6 +1,7 @@
 // engine_dispatch.hip — dispatch: which blind-rotate / keyswitch kernel a batch takes (by parameter set and batch size) and its launch
 #define TFHE_EMIT_KEYSWITCH_KERNELS
 #include "engine.hpp"
+#include "br_launch.hpp"
 
 #include <map>
 #include <mutex>
@@ -34,23 +35,6 @@ int32_t prepare_diag(tfhe_ctx *c, size_t R, hipStream_t s, DiagArgs &d)
     return TFHE_OK;
 }
 
-// Tuned kernels are instantiated for the decomposition lengths the shipped parameter sets use: l = 2 (tfhe_parameters_80,
-// api.jl:30-52) and l = 3 (tfhe_parameters_128, api.jl:55-69; BASELINE config 4b), with either mask size at N = 1024.
-// Every other set the reference would accept runs on blind_rotate_kernel_general.
-#define BR_CASES(LAUNCH)                                                                                           \
-    switch (c->P.bs_l) {                                                                                           \
-    case 2: LAUNCH(2); break;                                                                                      \
-    case 3: LAUNCH(3); break;                                                                                      \
-    default: return c->set_err(TFHE_ERR_STATE, "blind rotate: no tuned kernel for bs_l = %d", c->P.bs_l);          \
-    }
-// ... the one- and two-waves-per-rotation kernels also exist with the decomposition length as a run-time value (L = 0)
-#define BR_CASES_ANY_L(LAUNCH)                                                                                     \
-    switch (c->br_rt_l ? 0 : c->P.bs_l) {                                                                          \
-    case 2: LAUNCH(2); break;                                                                                      \
-    case 3: LAUNCH(3); break;                                                                                      \
-    default: LAUNCH(0); break;                                                                                     \
-    }
-
 void name_kernel(tfhe_ctx *c, const char *fmt, ...)
 {
     char buf[128];
@@ -61,17 +45,32 @@ void name_kernel(tfhe_ctx *c, const char *fmt, ...)
     c->last_kernel = buf;
 }
 
-// Blind rotation of rotations [first, first + R) of the batch (rows of the bara / ext workspaces): picks the kernel for a
-// batch of R rotations, launches it on `s` and names it.
-// A TV batch (tv != NULL: programmable bootstrapping) takes the same kernel, geometry and LDS as a mu batch of the same size, in its TV
-// form (engine_tv.hip); the caller names it with "+tv".
+// The decomposition-length instantiation of the kernels with a run-time-l form (L = 0): the tuned kernels are instantiated for the
+// lengths the shipped parameter sets use, l = 2 (tfhe_parameters_80, api.jl:30-52) and l = 3 (tfhe_parameters_128, api.jl:55-69;
+// BASELINE config 4b), with either mask size at N = 1024; the one- and two-waves-per-rotation kernels also exist with the length as a
+// run-time value, taken for every other l and, under option br_rt_l, for l = 2 and 3 too.  (h2, k2 and k2w3 have the tuned lengths only;
+// every other set the reference would accept runs on blind_rotate_kernel_general.)
+static int br_inst_l(const tfhe_ctx *c)
+{
+    return (c->P.bs_l == 2 || c->P.bs_l == 3) && !c->br_rt_l ? c->P.bs_l : 0;
+}
+
+// "blind_rotate_kernel_<family><L<rest>>"; the run-time-l instantiation also names the context's l: "...<0<rest>>(l=<l>)"
+static void name_br(tfhe_ctx *c, const char *family, int L, const char *rest = "")
+{
+    if (L) name_kernel(c, "blind_rotate_kernel_%s<%d%s>", family, L, rest);
+    else name_kernel(c, "blind_rotate_kernel_%s<0%s>(l=%d)", family, rest, c->P.bs_l);
+}
+
+// Blind rotation of rotations [first, first + R) of the batch (rows of the bara / ext workspaces): picks the kernel and geometry for
+// a batch of R rotations, launches it on `s` (br_launch.hpp) and names it.
+// A TV batch (tv_all != NULL: programmable bootstrapping) takes the same kernel, geometry and LDS as a mu batch of the same size, in its
+// TV form (engine_tv.hip); the caller names it with "+tv".
 static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int32_t mu, hipStream_t s, const DiagArgs &diag, int k2_kind = -1 /* k = 2: 0 = one wave per rotation, 1 = three, -1 = by batch size */,
                                         const TvPtrs *tv_all = nullptr)
 {
     TvPtrs tv{nullptr, nullptr};
     if (tv_all) tv = TvPtrs{tv_all->tv, tv_all->index + first};
-    const int32_t Ltv = (c->br_rt_l || (c->P.bs_l != 2 && c->P.bs_l != 3)) ? 0 : c->P.bs_l;     // (BR_CASES_ANY_L's choice)
-#define TV_OR(TVCALL, ...) do { if (tv_all) { const int32_t rtv_ = (TVCALL); if (rtv_) return rtv_; } else { __VA_ARGS__; } } while (0)
     BrArgs a;
     a.diag = diag;
     if (diag.margin_bits) { a.diag.margin_bits += first; a.diag.clk += 2 * first; }
@@ -104,19 +103,9 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
             HIP_TRY(c, c->spec.reserve((first + R) * (size_t)K1 * (M > 0 ? M : 1) * sizeof(cplx)));
             g.spec_g = (cplx *)c->spec.p + first * (size_t)K1 * (M > 0 ? M : 1);
         }
-        const size_t ldsa = anyn::lds_bytes(N, spec_lds ? K1 : 0);
-        const unsigned nt = (unsigned)anyn::threads_for(N);
-        if (tv_all) {
-            const int32_t rtv = tv_launch_anyn(c, g, tv, R, nt, ldsa, s);
-            if (rtv) return rtv;
-        } else if (dg) {
-            if (ldsa > 64 * 1024) LDS_TRY(c, ldsa, anyn::blind_rotate_kernel<true>);
-            hipLaunchKernelGGL((anyn::blind_rotate_kernel<true>), dim3((unsigned)R), dim3(nt), ldsa, s, g);
-        } else {
-            if (ldsa > 64 * 1024) LDS_TRY(c, ldsa, anyn::blind_rotate_kernel<false>);
-            hipLaunchKernelGGL((anyn::blind_rotate_kernel<false>), dim3((unsigned)R), dim3(nt), ldsa, s, g);
-        }
-        HIP_TRY(c, hipGetLastError());
+        const BrLaunch geo{0, 1, dg, dim3((unsigned)R), dim3((unsigned)anyn::threads_for(N)), anyn::lds_bytes(N, spec_lds ? K1 : 0)};
+        const int32_t rc = tv_all ? br_launch_anyn(c, with_tv(g, tv), geo, s) : br_launch_anyn(c, g, geo, s);
+        if (rc) return rc;
         name_kernel(c, spec_lds ? "blind_rotate_kernel_anyn(N=%d,k=%d,l=%d)" : "blind_rotate_kernel_anyn(N=%d,k=%d,l=%d,spec=global)", N, c->P.k, L);
         return TFHE_OK;
     }
@@ -131,28 +120,18 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         // "n512_w2" (-1: up to 6 rotations per CU, 0: never, 1: always).  One device, tfhe_parameters_80 with N = 512
         // (profiles/r05/r05k_n512_timing.txt): 1 rotation 1.13 vs 1.98 ms, 1024: 1.94 vs 2.58, 1536: 2.71 vs 2.96, 2048: 3.92 vs 3.44
         if (c->n512_w2 == 1 || (c->n512_w2 < 0 && R <= 6 * (size_t)c->cu_count)) {
-            const size_t ldsw = kN512W2LdsBytes;
-#define LAUNCH_N512W2(LL)                                                                                          \
-            if (dg) hipLaunchKernelGGL((blind_rotate_kernel_n512w2<LL, true>), dim3((unsigned)R), dim3(128), ldsw, s, b);        \
-            else hipLaunchKernelGGL((blind_rotate_kernel_n512w2<LL, false>), dim3((unsigned)R), dim3(128), ldsw, s, b)
-            TV_OR(tv_launch_n512w2(c, b, tv, Ltv, R, ldsw, s), BR_CASES_ANY_L(LAUNCH_N512W2));
-#undef LAUNCH_N512W2
-            HIP_TRY(c, hipGetLastError());
-            if ((L == 2 || L == 3) && !c->br_rt_l) name_kernel(c, "blind_rotate_kernel_n512w2<%d>", L);
-            else name_kernel(c, "blind_rotate_kernel_n512w2<0>(l=%d)", L);
+            const BrLaunch geo{br_inst_l(c), 1, dg, dim3((unsigned)R), dim3(128), kN512W2LdsBytes};
+            const int32_t rc = tv_all ? br_launch_n512w2(c, with_tv(b, tv), geo, s) : br_launch_n512w2(c, b, geo, s);
+            if (rc) return rc;
+            name_br(c, "n512w2", geo.L);
             return TFHE_OK;
         }
         const bool group = !dg && (c->n512_rw == 4 || (c->n512_rw == 0 && R >= 8 * (size_t)c->cu_count));      // (2048 rotations: 3.44 vs 3.82 ms, 3072: 4.68 vs 5.11)
-        const size_t lds5 = (size_t)(group ? 4 : 1) * kN512LdsBytes;
-#define LAUNCH_N512(LL)                                                                                            \
-        if (dg) hipLaunchKernelGGL((blind_rotate_kernel_n512<LL, true, 1>), dim3((unsigned)R), dim3(64), lds5, s, b);            \
-        else if (group) hipLaunchKernelGGL((blind_rotate_kernel_n512<LL, false, 4>), dim3((unsigned)((R + 3) / 4)), dim3(256), lds5, s, b); \
-        else hipLaunchKernelGGL((blind_rotate_kernel_n512<LL, false, 1>), dim3((unsigned)R), dim3(64), lds5, s, b)
-        TV_OR(tv_launch_n512(c, b, tv, Ltv, group, R, lds5, s), BR_CASES_ANY_L(LAUNCH_N512));
-#undef LAUNCH_N512
-        HIP_TRY(c, hipGetLastError());
-        if ((L == 2 || L == 3) && !c->br_rt_l) name_kernel(c, group ? "blind_rotate_kernel_n512<%d,rw4>" : "blind_rotate_kernel_n512<%d>", L);
-        else name_kernel(c, group ? "blind_rotate_kernel_n512<0,rw4>(l=%d)" : "blind_rotate_kernel_n512<0>(l=%d)", L);
+        const int rw = group ? 4 : 1;
+        const BrLaunch geo{br_inst_l(c), rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(64 * rw), (size_t)rw * kN512LdsBytes};
+        const int32_t rc = tv_all ? br_launch_n512(c, with_tv(b, tv), geo, s) : br_launch_n512(c, b, geo, s);
+        if (rc) return rc;
+        name_br(c, "n512", geo.L, group ? ",rw4" : "");
         return TFHE_OK;
     }
     const bool tuned = c->P.N == kN2 ? (c->P.k == 1 && L == 3) : c->P.k == 1 ? true : (c->P.k == 2 && (L == 2 || L == 3));
@@ -166,18 +145,10 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         g.acc = (int32_t *)c->mk_acc.p + first * K1 * img;
         g.tw1f = c->P.N == kN2 ? (const cplx *)(c->d_tables + kTableElems) : c->T.tw1f;
         g.tw2 = c->T.tw2;
-        const size_t ldsg = (kXchElems + 64 + (size_t)K1 * H * kM) * sizeof(cplx);
-#define LAUNCH_GEN(NB, DG)                                                                                         \
-        do {                                                                                                       \
-            if (ldsg > 64 * 1024)                                                                                  \
-                LDS_TRY(c, ldsg, blind_rotate_kernel_general<NB, DG>); \
-            hipLaunchKernelGGL((blind_rotate_kernel_general<NB, DG>), dim3((unsigned)R), dim3(64), ldsg, s, g);     \
-        } while (0)
-        if (tv_all) { const int32_t rtv = tv_launch_general(c, g, tv, c->P.N == kN2, R, ldsg, s); if (rtv) return rtv; }
-        else if (c->P.N == kN2) { if (dg) LAUNCH_GEN(32, true); else LAUNCH_GEN(32, false); }
-        else { if (dg) LAUNCH_GEN(16, true); else LAUNCH_GEN(16, false); }
-#undef LAUNCH_GEN
-        HIP_TRY(c, hipGetLastError());
+        const BrLaunch geo{0, 1, dg, dim3((unsigned)R), dim3(64), (kXchElems + 64 + (size_t)K1 * H * kM) * sizeof(cplx)};
+        const bool n2048 = c->P.N == kN2;
+        const int32_t rc = tv_all ? br_launch_general(c, with_tv(g, tv), n2048, geo, s) : br_launch_general(c, g, n2048, geo, s);
+        if (rc) return rc;
         name_kernel(c, "blind_rotate_kernel_general(N=%d,k=%d,l=%d)", c->P.N, c->P.k, L);
         return TFHE_OK;
     }
@@ -190,24 +161,13 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         b.R = (int32_t)R;
         const int rw = dg ? 1 : c->n2048_rw ? c->n2048_rw : (R <= (size_t)c->cu_count ? 1 : 2);     // (the DIAG instantiation exists for single rotations only)
         const size_t ldsb = (size_t)rw * (2 * kImg2 * 4 + 2 * kXchElems * sizeof(cplx)) + 64 * sizeof(cplx) + 64;      // (+ the hand-off words of the pairs)
-        const unsigned nblk = (unsigned)((R + rw - 1) / rw);
-#define LAUNCH_2048(DG, RWV)                                                                                       \
-        do {                                                                                                       \
-            if (ldsb > 64 * 1024)                                                                                  \
-                LDS_TRY(c, ldsb, blind_rotate_kernel_n2048x<3, DG, RWV>); \
-            hipLaunchKernelGGL((blind_rotate_kernel_n2048x<3, DG, RWV>), dim3(nblk), dim3(128 * RWV), ldsb, s, b); \
-        } while (0)
-        if (tv_all) { const int32_t rtv = tv_launch_n2048(c, b, tv, rw, nblk, ldsb, s); if (rtv) return rtv; }
-        else if (dg) LAUNCH_2048(true, 1);
-        else if (rw == 2) LAUNCH_2048(false, 2);
-        else LAUNCH_2048(false, 1);
-#undef LAUNCH_2048
-        HIP_TRY(c, hipGetLastError());
-        name_kernel(c, "blind_rotate_kernel_n2048x<%d,rw%d>", L, rw);
+        const BrLaunch geo{L, rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(128 * rw), ldsb};
+        const int32_t rc = tv_all ? br_launch_n2048x(c, with_tv(b, tv), geo, s) : br_launch_n2048x(c, b, geo, s);
+        if (rc) return rc;
+        name_br(c, "n2048x", L, rw == 2 ? ",rw2" : ",rw1");
         return TFHE_OK;
     }
     if (c->P.k == 2) {
-        const size_t ldsk = kK2LdsBytes;      // (no mirror blocks in this kernel: seven rotations per CU)
         // Up to seven rotations per workgroup in lockstep = one workgroup per CU: the k = 2 key is 73.7 MB of spectra, 144 KB
         // per step and rotation, and independent waves stream it through the 4 MB L2 of their XCD at 77 % hits (58 GB beyond
         // L2 per 4096 rotations, VALU busy 0.46: profiles/r03/r03k2_*); in lockstep the waves of a CU share every key line in
@@ -218,112 +178,70 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         // (Round 4, measured dead end: groups of THREE in lockstep, two such workgroups per CU, handed out by the dispatcher as
         //  slots free up — no rounds, six rotations per CU: 1792 rotations 15.8 vs 11.4 ms, 4096: 30.8 vs 29.9, 7168: 49.9 vs 43.5,
         //  16384: 105.5 vs 100.1; profiles/r04/r04b_k2.jsonl)
+        // (h2, k2 and k2w3 exist for l = 2 and 3 only: br_rt_l does not apply)
         const size_t cus = (size_t)c->cu_count;
         // three waves per rotation (blind_rotate_kernel_k2w3: wave c owns polynomial c): up to two rotations per CU, where the
         // one-wave kernel would keep one SIMD in four busy — and the last round of a larger batch (k2_partition)
         const bool w3 = k2_kind >= 0 ? k2_kind == 1 : (c->k2_w3 == 1 || (c->k2_w3 < 0 && R <= 2 * cus));
         if (w3) {
-            const size_t ldsw = kK2W3LdsBytes;
-#define LAUNCH_K2W3(LL)                                                                                            \
-            do {                                                                                                   \
-                if (dg) { LDS_TRY(c, ldsw, blind_rotate_kernel_k2w3<LL, true>); hipLaunchKernelGGL((blind_rotate_kernel_k2w3<LL, true>), dim3((unsigned)R), dim3(192), ldsw, s, a); } \
-                else { LDS_TRY(c, ldsw, blind_rotate_kernel_k2w3<LL, false>); hipLaunchKernelGGL((blind_rotate_kernel_k2w3<LL, false>), dim3((unsigned)R), dim3(192), ldsw, s, a); } \
-            } while (0)
-            TV_OR(tv_launch_k2w3(c, a, tv, L, R, ldsw, s), BR_CASES(LAUNCH_K2W3));
-#undef LAUNCH_K2W3
-            HIP_TRY(c, hipGetLastError());
-            name_kernel(c, "blind_rotate_kernel_k2w3<%d>", L);
+            const BrLaunch geo{L, 1, dg, dim3((unsigned)R), dim3(192), kK2W3LdsBytes};
+            const int32_t rc = tv_all ? br_launch_k2w3(c, with_tv(a, tv), geo, s) : br_launch_k2w3(c, a, geo, s);
+            if (rc) return rc;
+            name_br(c, "k2w3", L);
             return TFHE_OK;
         }
         const bool grouped = !dg && (c->k2_rw == 7 || c->k2_rw == 0);     // (never slower than single-rotation workgroups: 6.7 vs 6.9 ms at 64 rotations, 6.8 vs 7.6 at 512)
+        size_t blocks = R;
         if (grouped) {
             const size_t rounds = (R + 7 * cus - 1) / (7 * cus);
-            const size_t G = std::min(R, rounds * cus);                 // workgroups; fewer than one per CU only for tiny batches
-            a.grp_q = (int32_t)(R / G);
-            a.grp_big = (int32_t)(R % G);
-#define LAUNCH_K2(LL)                                                                                              \
-            do {                                                                                                   \
-                LDS_TRY(c, (7 * ldsk), blind_rotate_kernel_k2<LL, false, 7>); \
-                hipLaunchKernelGGL((blind_rotate_kernel_k2<LL, false, 7>), dim3((unsigned)G), dim3(448), 7 * ldsk, s, a); \
-            } while (0)
-            TV_OR(tv_launch_k2(c, a, tv, L, true, G, ldsk, s), BR_CASES(LAUNCH_K2));
-#undef LAUNCH_K2
-            HIP_TRY(c, hipGetLastError());
-            name_kernel(c, "blind_rotate_kernel_k2<%d,rw7>", L);
-            return TFHE_OK;
+            blocks = std::min(R, rounds * cus);                 // workgroups; fewer than one per CU only for tiny batches
+            a.grp_q = (int32_t)(R / blocks);
+            a.grp_big = (int32_t)(R % blocks);
         }
-#define LAUNCH_K2(LL)                                                                                              \
-        if (dg) hipLaunchKernelGGL((blind_rotate_kernel_k2<LL, true>), dim3((unsigned)R), dim3(64), ldsk, s, a);  \
-        else hipLaunchKernelGGL((blind_rotate_kernel_k2<LL, false>), dim3((unsigned)R), dim3(64), ldsk, s, a)
-        TV_OR(tv_launch_k2(c, a, tv, L, false, R, ldsk, s), BR_CASES(LAUNCH_K2));
-#undef LAUNCH_K2
-        HIP_TRY(c, hipGetLastError());
-        name_kernel(c, "blind_rotate_kernel_k2<%d>", L);
+        const int rw = grouped ? 7 : 1;      // (no mirror blocks in this kernel: seven rotations per CU)
+        const BrLaunch geo{L, rw, dg, dim3((unsigned)blocks), dim3(64 * rw), (size_t)rw * kK2LdsBytes};
+        const int32_t rc = tv_all ? br_launch_k2(c, with_tv(a, tv), geo, s) : br_launch_k2(c, a, geo, s);
+        if (rc) return rc;
+        name_br(c, "k2", L, grouped ? ",rw7" : "");
         return TFHE_OK;
     }
     const int64_t tiny = c->br_tiny == -2 ? (int64_t)c->cu_count : c->br_tiny;
     if (tiny >= 0 && (int64_t)R <= tiny && (L == 2 || L == 3) && !c->br_rt_l) {      // (4 l waves per rotation: instantiated for the shipped l only)
-        // every transform split over two waves: acc[2][N] | transposition buffers [4L][320] | extra slots [4L][256]
+        // every transform split over two waves
         H2Tables ht;
         ht.tw1h = c->d_tables + kH2TableOffset; ht.tw2q = ht.tw1h + 512; ht.tw3q = ht.tw2q + 64;
         // acc[2][N] | transposition buffers [4L][320] | extra slots [4L][256] | rotated differences [2 (step parity)][2][N]
         const size_t ldsh = 2 * kImg * 4 + (size_t)4 * L * (kH2Buf + 256) * sizeof(cplx) + 2 * 2 * kN * 4;
-#define LAUNCH_H2_(LL, DG)                                                                                         \
-        do {                                                                                                       \
-            LDS_TRY(c, ldsh, blind_rotate_kernel_h2<LL, DG>); \
-            hipLaunchKernelGGL((blind_rotate_kernel_h2<LL, DG>), dim3((unsigned)R), dim3(256 * LL), ldsh, s, a, ht); \
-        } while (0)
-#define LAUNCH_H2(LL) do { if (dg) LAUNCH_H2_(LL, true); else LAUNCH_H2_(LL, false); } while (0)
-        TV_OR(tv_launch_h2(c, a, ht, tv, L, R, ldsh, s), BR_CASES(LAUNCH_H2));
-#undef LAUNCH_H2
-#undef LAUNCH_H2_
-        HIP_TRY(c, hipGetLastError());
-        name_kernel(c, "blind_rotate_kernel_h2<%d>", L);
+        const BrLaunch geo{L, 1, dg, dim3((unsigned)R), dim3(256 * L), ldsh};
+        const int32_t rc = tv_all ? br_launch_h2(c, with_tv(a, tv), ht, geo, s) : br_launch_h2(c, a, ht, geo, s);
+        if (rc) return rc;
+        name_br(c, "h2", L);
         return TFHE_OK;
     }
     if (c->br_small >= 0 && (int64_t)R <= c->br_small) {
-        // 27.4 KB of LDS and < 256 registers per wave: four workgroups per CU, 1024 rotations resident at two waves per SIMD
-        const size_t ldsw = kW2LdsBytes;
-        // two rotations per workgroup (lockstep through the step barrier, key reads shared in L1) when that fills the CUs evenly: from
+        // 27.4 KB of LDS and < 256 registers per wave: four workgroups per CU, 1024 rotations resident at two waves per SIMD.
+        // Two rotations per workgroup (lockstep through the step barrier, key reads shared in L1) when that fills the CUs evenly: from
         // more than one rotation up to one pair per CU (300 rotations 2.26 vs 2.58 ms, 512: 2.29 vs 2.57; 128-bit set 3.64 vs 4.10) and at (nearly) two
         // pairs per CU (1024: 3.35 vs 3.41; 128-bit 5.36 vs 5.57); in between single rotations spread better (700: 2.95 vs 3.29)
         const size_t cus2 = 2 * (size_t)c->cu_count;
         const bool pairs = !dg && (c->w2_rw == 2 || (c->w2_rw == 0 && ((R > cus2 / 2 && R <= cus2) || R > 2 * cus2 - cus2 / 8)));
-#define LAUNCH_W2(LL)                                                                                              \
-        if (dg) hipLaunchKernelGGL((blind_rotate_kernel_w2<LL, true>), dim3((unsigned)R), dim3(128), ldsw, s, a); \
-        else if (pairs) hipLaunchKernelGGL((blind_rotate_kernel_w2<LL, false, 2>), dim3((unsigned)((R + 1) / 2)), dim3(256), 2 * ldsw, s, a); \
-        else hipLaunchKernelGGL((blind_rotate_kernel_w2<LL, false>), dim3((unsigned)R), dim3(128), ldsw, s, a)
-        TV_OR(tv_launch_w2(c, a, tv, Ltv, pairs, R, ldsw, s), BR_CASES_ANY_L(LAUNCH_W2));
-#undef LAUNCH_W2
-        HIP_TRY(c, hipGetLastError());
-        if ((L == 2 || L == 3) && !c->br_rt_l) name_kernel(c, pairs ? "blind_rotate_kernel_w2<%d,rw2>" : "blind_rotate_kernel_w2<%d>", L);
-        else name_kernel(c, pairs ? "blind_rotate_kernel_w2<0,rw2>(l=%d)" : "blind_rotate_kernel_w2<0>(l=%d)", L);
+        const int rw = pairs ? 2 : 1;
+        const BrLaunch geo{br_inst_l(c), rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(128 * rw), (size_t)rw * kW2LdsBytes};
+        const int32_t rc = tv_all ? br_launch_w2(c, with_tv(a, tv), geo, s) : br_launch_w2(c, a, geo, s);
+        if (rc) return rc;
+        name_br(c, "w2", geo.L, pairs ? ",rw2" : "");
         return TFHE_OK;
     }
-    {
-        // one wave per rotation: half of a transform's key chunk requested a transform ahead, pass-B twiddles in registers
-        // (round 3's <l, 16> / <l, 8, tw2 in LDS> variants were A/B scaffolding and are gone); four rotations per workgroup in
-        // lockstep once the batch puts two waves on most SIMDs (option v3_rw: 0 = by batch size, 1, 4)
-        const size_t lds3 = kV3LdsBytes;
-        const bool group = c->v3_rw == 4 || (c->v3_rw == 0 && R >= 6 * (size_t)c->cu_count);      // 1536 on 256 CUs (1400 rotations: 5.47 vs 5.40 ms, 1700: 5.50 vs 5.66, 2000: 5.69 vs 5.93)
-#define LAUNCH_V3_GROUP(LL, DG)                                                                                    \
-        do {                                                                                                       \
-            LDS_TRY(c, (4 * lds3), blind_rotate_kernel_v3<LL, 8, true, DG, 4>); \
-            hipLaunchKernelGGL((blind_rotate_kernel_v3<LL, 8, true, DG, 4>), dim3((unsigned)((R + 3) / 4)), dim3(256), 4 * lds3, s, a); \
-        } while (0)
-#define LAUNCH_V3(LL)                                                                                              \
-        if (group && dg) LAUNCH_V3_GROUP(LL, true);                                                                \
-        else if (group) LAUNCH_V3_GROUP(LL, false);                                                                \
-        else if (dg) hipLaunchKernelGGL((blind_rotate_kernel_v3<LL, 8, true, true>), dim3((unsigned)R), dim3(64), lds3, s, a);     \
-        else hipLaunchKernelGGL((blind_rotate_kernel_v3<LL, 8, true, false>), dim3((unsigned)R), dim3(64), lds3, s, a)
-        TV_OR(tv_launch_v3(c, a, tv, Ltv, group, R, lds3, s), BR_CASES_ANY_L(LAUNCH_V3));
-#undef LAUNCH_V3
-#undef LAUNCH_V3_GROUP
-        HIP_TRY(c, hipGetLastError());
-        if ((L == 2 || L == 3) && !c->br_rt_l) name_kernel(c, group ? "blind_rotate_kernel_v3<%d,8,tw2reg,rw4>" : "blind_rotate_kernel_v3<%d,8,tw2reg>", L);
-        else name_kernel(c, group ? "blind_rotate_kernel_v3<0,8,tw2reg,rw4>(l=%d)" : "blind_rotate_kernel_v3<0,8,tw2reg>(l=%d)", L);
-        return TFHE_OK;
-    }
+    // one wave per rotation: half of a transform's key chunk requested a transform ahead, pass-B twiddles in registers
+    // (round 3's <l, 16> / <l, 8, tw2 in LDS> variants were A/B scaffolding and are gone); four rotations per workgroup in
+    // lockstep once the batch puts two waves on most SIMDs (option v3_rw: 0 = by batch size, 1, 4)
+    const bool group = c->v3_rw == 4 || (c->v3_rw == 0 && R >= 6 * (size_t)c->cu_count);      // 1536 on 256 CUs (1400 rotations: 5.47 vs 5.40 ms, 1700: 5.50 vs 5.66, 2000: 5.69 vs 5.93)
+    const int rw = group ? 4 : 1;
+    const BrLaunch geo{br_inst_l(c), rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(64 * rw), (size_t)rw * kV3LdsBytes};
+    const int32_t rc = tv_all ? br_launch_v3(c, with_tv(a, tv), geo, s) : br_launch_v3(c, a, geo, s);
+    if (rc) return rc;
+    name_br(c, "v3", geo.L, group ? ",8,tw2reg,rw4" : ",8,tw2reg");
+    return TFHE_OK;
 }
 
 // A batch whose size is not a multiple of what the chip holds pays for its last, partly filled round as for a full one
@@ -390,8 +308,6 @@ static std::vector<K2Seg> k2_partition(size_t R, size_t cus, bool allow_w3)
     if (done < R) seg.push_back({R - done, 1});
     return seg;
 }
-
-#undef TV_OR
 
 int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, const TvPtrs *tv)
 {
