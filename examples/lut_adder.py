@@ -5,7 +5,11 @@ Each operand is 8 base-4 digits, each digit encrypted as a message of Z_8 (tfhe_
 s = a + b + carry (0 .. 7) is a plain sum of LWE samples; the three encodings (2x + 1)/32 add up to (2s + 3)/32, so a trivial
 constant of -2/32 puts it at lut_encode(s, 8).  One tfhe_bootstrap_tv_batch call then evaluates both s mod 4 (the digit) and
 s >= 4 (the next carry) through tv_index: 8 calls of 2 x 1024 rotations add 1024 pairs.  The gate adder (5 gates per bit,
-a 32-level carry chain) runs as Circuit.run_batch over the same 1024 instances."""
+a 32-level carry chain) runs as Circuit.run_batch over the same 1024 instances.
+
+The third variant encrypts every digit as a message of Z_16 (p = 8 messages in a space of p K = 16, K = 2) and takes digit and
+carry from ONE rotation per sum (tfhe_bootstrap_tv_multi_batch, make_multi_test_vector): 8 calls of 1024 rotations.  Its noise
+headroom is half the Z_8 adder's, so it reports its wrong sums instead of asserting that there are none."""
 import os
 import sys
 import time
@@ -14,16 +18,17 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tfhe_jl_amd as tfhe
-from tfhe_jl_amd.lut import lut_decrypt, lut_encode, lut_encrypt, make_test_vector
+from tfhe_jl_amd.lut import lut_decrypt, lut_encode, lut_encrypt, make_multi_test_vector, make_test_vector
 
 P = 8            # message space of a digit sum
 DIGITS = 8       # base-4 digits of a 16-bit operand
+P_MULTI = 16     # the one-rotation adder: digit sums of Z_8 encrypted in Z_16, two outputs per rotation
 
 
-def encrypt_digits(rng, sk, values):
-    """int [M] -> [DIGITS] LweSampleArrays of M samples (digit i of every value, in Z_8)."""
+def encrypt_digits(rng, sk, values, space=P):
+    """int [M] -> [DIGITS] LweSampleArrays of M samples (digit i of every value, in Z_space)."""
     values = np.asarray(values, np.int64)
-    return [lut_encrypt(rng, sk, (values >> (2 * i)) & 3, P) for i in range(DIGITS)]
+    return [lut_encrypt(rng, sk, (values >> (2 * i)) & 3, space) for i in range(DIGITS)]
 
 
 def lut_add16(ck, a, b, device=0):
@@ -42,8 +47,23 @@ def lut_add16(ck, a, b, device=0):
     return out + [carry]
 
 
-def decrypt_sum(sk, digits):
-    return sum(lut_decrypt(sk, d, P).astype(np.int64) << (2 * i) for i, d in enumerate(digits))
+def lut_add16_multi(ck, a, b, device=0):
+    """lut_add16 on digits encrypted in Z_16 (encrypt_digits(..., P_MULTI)): digit s mod 4 and carry s >= 4 of every sum from one
+    multi-output rotation, both again in Z_16."""
+    eng = ck.engine(device)
+    table = make_multi_test_vector([lambda s: s % 4, lambda s: s >= 4], P, eng.N, P_MULTI)
+    out, carry = [], None
+    for i in range(DIGITS):
+        s = a[i] + b[i]
+        s = s.add_constant(-int(lut_encode(0, P_MULTI))) if carry is None else (s + carry).add_constant(-2 * int(lut_encode(0, P_MULTI)))
+        both = eng.bootstrap_tv_multi(table, s.data, 2)
+        out.append(tfhe.LweSampleArray(both[:, 0]))
+        carry = tfhe.LweSampleArray(both[:, 1])
+    return out + [carry]
+
+
+def decrypt_sum(sk, digits, space=P):
+    return sum(lut_decrypt(sk, d, space).astype(np.int64) << (2 * i) for i, d in enumerate(digits))
 
 
 def gate_adder():
@@ -75,6 +95,13 @@ def main(M=1024):
     t_lut = time.perf_counter() - t0
     assert np.array_equal(decrypt_sum(sk, digits), x + y), "LUT adder: wrong sums"
 
+    a16, b16 = encrypt_digits(rng, sk, x, P_MULTI), encrypt_digits(rng, sk, y, P_MULTI)
+    lut_add16_multi(ck, a16, b16)
+    t0 = time.perf_counter()
+    digits16 = lut_add16_multi(ck, a16, b16)
+    t_multi = time.perf_counter() - t0
+    wrong_multi = int(np.sum(decrypt_sum(sk, digits16, P_MULTI) != x + y))
+
     circ = gate_adder()
     bits = lambda v: np.stack([(v >> i) & 1 for i in range(16)], axis=1).astype(bool)
     inputs = np.stack([tfhe.encrypt(rng, sk, np.concatenate([bits(x)[m], bits(y)[m]])).data for m in range(M)])
@@ -87,6 +114,8 @@ def main(M=1024):
 
     print(f"{M} encrypted 16-bit additions, all correct")
     print(f"  LUT digits (8 calls of {2 * M} rotations): {t_lut * 1e3:8.1f} ms")
+    print(f"  LUT digits, digit and carry from one rotation (8 calls of {M} rotations, Z_16): {t_multi * 1e3:8.1f} ms, "
+          f"{wrong_multi} wrong sums of {M}")
     print(f"  ripple-carry gate adder ({len(circ.levels())} levels):   {t_gate * 1e3:8.1f} ms")
     ck.close()
 

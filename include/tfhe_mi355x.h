@@ -299,6 +299,18 @@ int32_t tfhe_bootstrap_batch(tfhe_ctx *ctx, int32_t mu, const int32_t *in, int32
 int32_t tfhe_bootstrap_tv_batch(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const int32_t *tv_index,
                                 const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch);
 
+/* Multi-output programmable bootstrapping (addition within ABI v7): tfhe_bootstrap_tv_batch returning n_out samples per row, from
+ * ONE blind rotation.  Sample j of row g is tlwe_extract_sample (tlwe.jl:55-59) of the final accumulator at coefficient
+ * c_j = j N / n_out instead of 0: mask polynomial i = X^{c_j} times mask polynomial i of the index-0 extraction (a[u] = e[u - c_j] for
+ * u >= c_j, -e[N + u - c_j] for u < c_j), body = coefficient c_j of the accumulator's body; each is keyswitched if with_keyswitch.
+ * Sample 0 is tfhe_bootstrap_tv_batch's result.  Its body is v[phi + c_j] for phi + c_j < N: a table packing f_j(m) at window
+ * j p + m of Z_{p n_out} gives f_j(m) for a message m of Z_p encrypted in Z_{p n_out} (tfhe_jl_amd.lut, make_multi_test_vector).
+ * out: host int32 [B][n_out][n+1], or [B][n_out][k*N+1] without keyswitch.  n_out: a power of two, 1 <= n_out <= 32, and n_out = 1
+ * or n_out <= N/4, else TFHE_ERR_INVALID_ARG before anything is uploaded.  Other arguments and errors as tfhe_bootstrap_tv_batch;
+ * tfhe_last_rotation_count reports B. */
+int32_t tfhe_bootstrap_tv_multi_batch(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out,
+                                      const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch);
+
 /* keyswitch(ks, sample) (keyswitch.jl:45-80). in: host int32 [B][k*N+1]; out: host int32 [B][n+1]. */
 int32_t tfhe_keyswitch_batch(tfhe_ctx *ctx, const int32_t *in, int32_t *out, int64_t B);
 

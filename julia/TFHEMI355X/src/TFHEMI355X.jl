@@ -394,6 +394,31 @@ function bootstrap_tv(gck::GpuCloudKey, tables::AbstractMatrix{Int32}, xs, index
     unflatten(out, LweParams(n_out))
 end
 
+"""
+    bootstrap_tv_multi(gck, tables, xs, n_out, index=nothing; with_keyswitch=true)  ->  Vector{Vector{LweSample}}
+
+Multi-output programmable bootstrapping (tfhe_bootstrap_tv_multi_batch): `bootstrap_tv` returning `n_out` results per sample from one
+blind rotation, result `j` (1-based) the sample extracted at the accumulator's coefficient `(j - 1) N / n_out` instead of 0
+(tlwe.jl:55-59).  With a table packing `f_j(m)` at window `(j - 1) p + m` of Z_{p n_out} and inputs encrypted in Z_{p n_out}, result
+`j` encrypts `f_j(m)`.  `n_out`: a power of two <= 32, and 1 or <= N / 4.  Returns `n_out` vectors of `length(xs)` samples.
+"""
+function bootstrap_tv_multi(gck::GpuCloudKey, tables::AbstractMatrix{Int32}, xs, n_out::Integer, index=nothing; with_keyswitch::Bool=true)
+    B = length(xs)
+    B == 0 && return [LweSample[] for _ in 1:max(n_out, 0)]
+    N = gck.params.tlwe_polynomial_degree
+    size(tables, 1) == N || error("tfhe_mi355x: test polynomials must have N = ", N, " rows")
+    1 <= n_out <= 32 || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32)")
+    tv = Matrix{Int32}(tables)
+    idx = index === nothing ? nothing : Int32.(collect(index) .- 1)
+    fx = flatten(xs)
+    width = with_keyswitch ? gck.params.lwe_size : gck.params.tlwe_mask_size * N
+    out = Array{Int32}(undef, width + 1, n_out, B)
+    GC.@preserve tv idx fx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_bootstrap_tv_multi_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Int32),
+        gck.ctx, tv, Int32(size(tv, 2)), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), Int32(n_out), fx, out, B, Int32(with_keyswitch)))
+    [unflatten(out[:, j, :], LweParams(width)) for j in 1:n_out]
+end
+
 # page-locked Int32 matrix (tfhe_host_alloc): the copies of a streamed batch are then single DMA transfers that overlap kernels
 function pinned_matrix(rows::Int, cols::Int)
     p = Ref{Ptr{Cvoid}}(C_NULL)

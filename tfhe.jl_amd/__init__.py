@@ -14,7 +14,8 @@ from .mk_keys import SharedKey, CloudKeyPart, MKCloudKey, MKLweSample, mk_encryp
 from .mk_gates import (mk_gate_or, mk_gate_and, mk_gate_xor, mk_gate_xnor, mk_gate_nor, mk_gate_andny, mk_gate_andyn,
                        mk_gate_orny, mk_gate_oryn, mk_gate_mux, mk_gate_not, mk_gate_constant, mk_gates_batch)
 from .circuit import Circuit
-from .lut import lut_encode, lut_decode, lut_encrypt, lut_decrypt, make_test_vector, programmable_bootstrap
+from .lut import (lut_encode, lut_decode, lut_encrypt, lut_decrypt, make_test_vector, programmable_bootstrap, make_multi_test_vector,
+                  programmable_bootstrap_multi)
 from .serialize import save_cloud_key, load_cloud_key
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
 
@@ -28,5 +29,6 @@ __all__ = [
     "mk_gate_or", "mk_gate_and", "mk_gate_xor", "mk_gate_xnor", "mk_gate_nor", "mk_gate_andny", "mk_gate_andyn",
     "mk_gate_orny", "mk_gate_oryn", "mk_gate_mux", "mk_gate_not", "mk_gate_constant", "mk_gates_batch",
     "Circuit", "lut_encode", "lut_decode", "lut_encrypt", "lut_decrypt", "make_test_vector", "programmable_bootstrap",
+    "make_multi_test_vector", "programmable_bootstrap_multi",
     "save_cloud_key", "load_cloud_key", "Engine", "EngineError", "OPCODES", "LIB_PATH", "pinned_empty",
 ]

@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "tfhe_mk_expand_load_bootstrap_key", "tfhe_keygen_cloud_key", "tfhe_host_alloc", "tfhe_host_free",
     "tfhe_timing_history_ms", "tfhe_gates_batch_submit", "tfhe_gates_batch_wait", "tfhe_last_device_count",
     "tfhe_get_option", "tfhe_ctx_synchronize", "tfhe_mk_gates_batch", "tfhe_mk_wires_alloc", "tfhe_mk_gates_level",
-    "tfhe_bootstrap_tv_batch",
+    "tfhe_bootstrap_tv_batch", "tfhe_bootstrap_tv_multi_batch",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -111,6 +111,7 @@ def load():
         lib.tfhe_gates_batch_wait.argtypes = [vp, i32]
     lib.tfhe_bootstrap_batch.argtypes = [vp, i32, vp, vp, i64, i32]
     lib.tfhe_bootstrap_tv_batch.argtypes = [vp, vp, i32, vp, vp, vp, i64, i32]
+    lib.tfhe_bootstrap_tv_multi_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, i64, i32]
     lib.tfhe_keyswitch_batch.argtypes = [vp, vp, vp, i64]
     lib.tfhe_mk_load_bootstrap_key_i32.argtypes = [vp, vp, i32]
     lib.tfhe_mk_load_keyswitch_key.argtypes = [vp, vp, i32]
@@ -329,13 +330,10 @@ class Engine:
         self._check(self._lib.tfhe_bootstrap_batch(self._h, int(mu), _ptr(x), _ptr(out), B, 1 if with_keyswitch else 0))
         return out
 
-    def bootstrap_tv(self, tables, x, index=None, with_keyswitch=True):
-        """Programmable bootstrapping (tfhe_bootstrap_tv_batch): `bootstrap` with row g's test polynomial tables[index[g]]
-        (int32 [n_tv][N]; index None: table 0 for every row) instead of (mu, ..., mu).  Row g's result has the body
-        v[phi] for phi in [0, N) and -v[phi - N] for phi in [N, 2N), phi = the row's modulus-switched phase (lut.py)."""
+    def _tv_args(self, what, tables, x, index):
         x = _i32c(x)
         if x.ndim != 2 or x.shape[1] != self.n + 1:
-            raise ValueError(f"bootstrap_tv input must be [B][{self.n + 1}], got {x.shape}")
+            raise ValueError(f"{what} input must be [B][{self.n + 1}], got {x.shape}")
         tables = _i32c(np.atleast_2d(tables))
         if tables.ndim != 2 or tables.shape[1] != self.N:
             raise ValueError(f"test polynomials must be [n_tv][{self.N}], got {tables.shape}")
@@ -345,10 +343,31 @@ class Engine:
             idx = _i32c(index)
             if idx.shape != (B,):
                 raise ValueError(f"index must have one entry per row ({B}), got {idx.shape}")
+        return tables, x, idx
+
+    def bootstrap_tv(self, tables, x, index=None, with_keyswitch=True):
+        """Programmable bootstrapping (tfhe_bootstrap_tv_batch): `bootstrap` with row g's test polynomial tables[index[g]]
+        (int32 [n_tv][N]; index None: table 0 for every row) instead of (mu, ..., mu).  Row g's result has the body
+        v[phi] for phi in [0, N) and -v[phi - N] for phi in [N, 2N), phi = the row's modulus-switched phase (lut.py)."""
+        tables, x, idx = self._tv_args("bootstrap_tv", tables, x, index)
+        B = x.shape[0]
         width = self.n + 1 if with_keyswitch else self.k * self.N + 1
         out = np.empty((B, width), np.int32)
         self._check(self._lib.tfhe_bootstrap_tv_batch(self._h, _ptr(tables), tables.shape[0], _ptr(idx) if idx is not None else None,
                                                       _ptr(x), _ptr(out), B, 1 if with_keyswitch else 0))
+        return out
+
+    def bootstrap_tv_multi(self, tables, x, n_out, index=None, with_keyswitch=True):
+        """Multi-output programmable bootstrapping (tfhe_bootstrap_tv_multi_batch): `bootstrap_tv` returning n_out samples per
+        row from one blind rotation, int32 [B][n_out][width].  Sample j is extracted at the accumulator's coefficient j N / n_out:
+        its body is v[phi + j N / n_out] where that index is below N (lut.py: make_multi_test_vector).  n_out: a power of two,
+        1 <= n_out <= 32, and 1 or <= N / 4 (the library returns TFHE_ERR_INVALID_ARG otherwise)."""
+        tables, x, idx = self._tv_args("bootstrap_tv_multi", tables, x, index)
+        B, n_out = x.shape[0], int(n_out)
+        width = self.n + 1 if with_keyswitch else self.k * self.N + 1
+        out = np.empty((B, n_out if 1 <= n_out <= 32 else 0, width), np.int32)      # (an n_out the library refuses: nothing written)
+        self._check(self._lib.tfhe_bootstrap_tv_multi_batch(self._h, _ptr(tables), tables.shape[0], _ptr(idx) if idx is not None else None,
+                                                            n_out, _ptr(x), _ptr(out), B, 1 if with_keyswitch else 0))
         return out
 
     def keyswitch(self, x):

@@ -17,6 +17,8 @@ static WithTv<A> with_tv(const A &a, const TvPtrs &tv)
     static_cast<A &>(t) = a;
     t.tv = tv.tv;
     t.tv_index = tv.index;
+    t.bodies = tv.bodies;
+    t.n_out = tv.n_out;
     return t;
 }
 

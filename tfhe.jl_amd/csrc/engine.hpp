@@ -183,6 +183,7 @@ struct tfhe_ctx {
     // workspaces
     DevBuf bara, ext, map, io[4], diag, abar, mk_acc, spec;
     DevBuf tv, tv_index;           // tfhe_bootstrap_tv_batch: the test polynomials and the table of each row
+    DevBuf tv_bodies, tv_ext;      // tfhe_bootstrap_tv_multi_batch: [B][n_out] body coefficients, [B][n_out][kN+1] shifted extractions
     size_t diag_rows = 0;
     bool mk_force_general = false; // tfhe_set_option("mk_general", 1): use the any-P kernel for 2 parties too (cross-check)
     int n2048_rw = 0;              // N = 2048: rotations per workgroup advancing in lockstep (tfhe_set_option("n2048_rw", 0|1|2); 0 = one up to
@@ -409,7 +410,9 @@ struct DiagArgs;
 int32_t prepare_diag(tfhe_ctx *c, size_t R, hipStream_t s, DiagArgs &d);
 void name_kernel(tfhe_ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 // a TV batch (tfhe_bootstrap_tv_batch): the test polynomials and the table of each rotation of the batch, device pointers
-struct TvPtrs { const int32_t *tv; const int32_t *index; };
+// A multi-output TV batch (tfhe_bootstrap_tv_multi_batch) adds `bodies`, [R][n_out]: the kernels also write the body coefficients
+// j N / n_out of each rotation there (kernels_common.hpp: store_bodies); NULL for a plain TV batch.
+struct TvPtrs { const int32_t *tv; const int32_t *index; int32_t *bodies = nullptr; int32_t n_out = 1; };
 int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, const TvPtrs *tv = nullptr);
 int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out, hipStream_t s);
 int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, int32_t *out, hipStream_t s);

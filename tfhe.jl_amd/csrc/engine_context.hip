@@ -324,7 +324,7 @@ void tfhe_ctx_destroy(tfhe_ctx *c)
     if (c->d_mk_ks4) (void)hipFree(c->d_mk_ks4);
     if (c->d_mk_bk) (void)hipFree(c->d_mk_bk);
     if (c->d_mk_ksp) (void)hipFree(c->d_mk_ksp);
-    c->bara.release(); c->ext.release(); c->map.release(); c->diag.release(); c->abar.release(); c->mk_acc.release(); c->spec.release(); c->tv.release(); c->tv_index.release();
+    c->bara.release(); c->ext.release(); c->map.release(); c->diag.release(); c->abar.release(); c->mk_acc.release(); c->spec.release(); c->tv.release(); c->tv_index.release(); c->tv_bodies.release(); c->tv_ext.release();
     for (auto &b : c->io) b.release();
     for (auto &st : c->map_stage) {
         if (st.h) (void)hipHostFree(st.h);

@@ -70,7 +70,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
                                         const TvPtrs *tv_all = nullptr)
 {
     TvPtrs tv{nullptr, nullptr};
-    if (tv_all) tv = TvPtrs{tv_all->tv, tv_all->index + first};
+    if (tv_all) tv = TvPtrs{tv_all->tv, tv_all->index + first, tv_all->bodies ? tv_all->bodies + first * (size_t)tv_all->n_out : nullptr, tv_all->n_out};
     BrArgs a;
     a.diag = diag;
     if (diag.margin_bits) { a.diag.margin_bits += first; a.diag.clk += 2 * first; }

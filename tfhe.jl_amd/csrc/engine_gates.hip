@@ -498,18 +498,22 @@ ABI_CATCH(c, "tfhe_gates_batch_wait")
 // The host-table form of a TV batch: tables [n_tv][N], index [B] (checked by the caller) or NULL = table 0 for every row.
 struct TvHost { const int32_t *tv; int32_t n_tv; const int32_t *index; };
 
-// tfhe_bootstrap_batch (tv == NULL) and tfhe_bootstrap_tv_batch on a device context or, row-split, on the kids of a multi-device one
-static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const TvHost *tv, const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch)
+// tfhe_bootstrap_batch (tv == NULL), tfhe_bootstrap_tv_batch (n_out = 1) and tfhe_bootstrap_tv_multi_batch on a device context or,
+// row-split, on the kids of a multi-device one.  With n_out > 1 the TV kernels also write each rotation's body coefficients
+// j N / n_out (bodies), extract_shift_kernel turns row g into the n_out samples extracted at those coefficients, and the keyswitch
+// (if any) runs on the B n_out rows: out is [B][n_out][width].  The shift belongs to the keyswitch phase of the timing events.
+static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const TvHost *tv, int32_t n_out, const int32_t *in, int32_t *out, int64_t B,
+                              int32_t with_keyswitch)
 {
     if (c->multi()) {
-        const size_t wi = (size_t)c->P.n + 1, wo = with_keyswitch ? wi : (size_t)c->P.k * c->P.N + 1;
+        const size_t wi = (size_t)c->P.n + 1, wo = (with_keyswitch ? wi : (size_t)c->P.k * c->P.N + 1) * (size_t)n_out;
         return multi_rows(c, B, [&](tfhe_ctx *k, int64_t s0, int64_t cnt) {
             alloc_checkpoint();
             CallGuard kid_guard(k);
             if (!kid_guard.ok) return (int32_t)TFHE_ERR_STATE;
             TvHost part;
             if (tv) part = TvHost{tv->tv, tv->n_tv, tv->index ? tv->index + s0 : nullptr};      // every device gets every table
-            return bootstrap_rows(k, who, mu, tv ? &part : nullptr, in + (size_t)s0 * wi, out + (size_t)s0 * wo, cnt, with_keyswitch);
+            return bootstrap_rows(k, who, mu, tv ? &part : nullptr, n_out, in + (size_t)s0 * wi, out + (size_t)s0 * wo, cnt, with_keyswitch);
         });
     }
     if (!c->have_bk || (with_keyswitch && !c->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: key not loaded", who);
@@ -517,7 +521,8 @@ static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const Tv
     hipStream_t s = c->stream;
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }
     const int n = c->P.n, kNn = c->P.k * c->P.N;
-    const size_t in_bytes = (size_t)B * (n + 1) * 4;
+    const size_t in_bytes = (size_t)B * (n + 1) * 4, G = (size_t)B * n_out;      // G: output samples
+    const bool multi_out = n_out > 1;
     HIP_TRY(c, c->io[0].reserve(in_bytes));
     HIP_TRY(c, hipMemcpyAsync(c->io[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(c, c->bara.reserve((size_t)B * (n + 1) * 4));
@@ -531,7 +536,15 @@ static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const Tv
         if (tv->index) HIP_TRY(c, hipMemcpyAsync(c->tv_index.p, tv->index, idx_bytes, hipMemcpyHostToDevice, s));
         else HIP_TRY(c, hipMemsetAsync(c->tv_index.p, 0, idx_bytes, s));
         tvd = TvPtrs{(const int32_t *)c->tv.p, (const int32_t *)c->tv_index.p};
+        if (multi_out) {
+            HIP_TRY(c, c->tv_bodies.reserve(G * 4));
+            HIP_TRY(c, c->tv_ext.reserve(G * (kNn + 1) * 4));
+            tvd.bodies = (int32_t *)c->tv_bodies.p;
+            tvd.n_out = n_out;
+        }
     }
+    // the extracted samples the keyswitch reads or the caller receives: [G][kN + 1]
+    const int32_t *samples = multi_out ? (const int32_t *)c->tv_ext.p : (const int32_t *)c->ext.p;
     next_timing_slot(c);
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     hipLaunchKernelGGL(modswitch_kernel, dim3((unsigned)B), dim3(256), 0, s, (const int32_t *)c->io[0].p, (int32_t *)c->bara.p, n,
@@ -541,21 +554,28 @@ static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const Tv
     int32_t rc = launch_blind_rotate(c, (size_t)B, mu, s, tv ? &tvd : nullptr);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    if (multi_out) {
+        const size_t total = G * (kNn + 1), groups = (total + 3) / 4;
+        hipLaunchKernelGGL(extract_shift_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const int32_t *)c->ext.p,
+                           (const int32_t *)c->tv_bodies.p, (int32_t *)c->tv_ext.p, total, kNn + 1, ilog2i(c->P.N), ilog2i(n_out));
+        HIP_TRY(c, hipGetLastError());
+    }
     if (with_keyswitch) {
         // identity maps: e0[g] = g
-        rc = ensure_host_map(c, (size_t)B * 4);
+        const size_t out_bytes = G * (n + 1) * 4;
+        rc = ensure_host_map(c, G * 4);
         if (rc) return rc;
-        for (int64_t g = 0; g < B; g++) ((int32_t *)c->h_map)[g] = (int32_t)g;
-        HIP_TRY(c, c->map.reserve((size_t)B * 4));
-        HIP_TRY(c, hipMemcpyAsync(c->map.p, c->h_map, (size_t)B * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, c->io[3].reserve(in_bytes));
-        rc = launch_keyswitch(c, (size_t)B, (const int32_t *)c->map.p, nullptr, nullptr, (const int32_t *)c->ext.p, (int32_t *)c->io[3].p, s);
+        for (size_t g = 0; g < G; g++) ((int32_t *)c->h_map)[g] = (int32_t)g;
+        HIP_TRY(c, c->map.reserve(G * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->map.p, c->h_map, G * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, c->io[3].reserve(out_bytes));
+        rc = launch_keyswitch(c, G, (const int32_t *)c->map.p, nullptr, nullptr, samples, (int32_t *)c->io[3].p, s);
         if (rc) return rc;
         HIP_TRY(c, hipEventRecord(c->ev[3], s));
-        HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, in_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, out_bytes, hipMemcpyDeviceToHost, s));
     } else {
         HIP_TRY(c, hipEventRecord(c->ev[3], s));
-        HIP_TRY(c, hipMemcpyAsync(out, c->ext.p, (size_t)B * (kNn + 1) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(out, samples, G * (kNn + 1) * 4, hipMemcpyDeviceToHost, s));
     }
     rc = leave_stream(c, s);
     if (rc) return rc;
@@ -572,29 +592,47 @@ int32_t tfhe_bootstrap_batch(tfhe_ctx *c, int32_t mu, const int32_t *in, int32_t
     if (B < 0 || (B > 0 && (!in || !out))) return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_batch: NULL argument or negative B");
     if (B == 0) return TFHE_OK;
     if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "bootstrap_batch: context is multi-key");
-    return bootstrap_rows(c, "bootstrap_batch", mu, nullptr, in, out, B, with_keyswitch);
+    return bootstrap_rows(c, "bootstrap_batch", mu, nullptr, 1, in, out, B, with_keyswitch);
 }
 ABI_CATCH(c, "tfhe_bootstrap_batch")
 
-// Programmable bootstrapping: tfhe_bootstrap_batch with row g's test polynomial tv[tv_index[g]] instead of (mu, ..., mu).
+// Programmable bootstrapping: tfhe_bootstrap_batch with row g's test polynomial tv[tv_index[g]] instead of (mu, ..., mu), and n_out
+// samples per row, extracted at the coefficients j N / n_out (tfhe_bootstrap_tv_batch: n_out = 1).
+static int32_t bootstrap_tv_rows(tfhe_ctx *c, const char *who, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out,
+                                 const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch)
+{
+    if (B < 0 || (B > 0 && (!in || !out || !tv))) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL argument or negative B", who);
+    if (n_tv < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: n_tv = %d (at least one table)", who, n_tv);
+    if (n_out < 1 || n_out > 32 || (n_out & (n_out - 1)) || (n_out > 1 && n_out > c->P.N / 4))
+        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: n_out = %d (a power of two <= 32, and 1 or <= N/4 = %d)", who, n_out, c->P.N / 4);
+    if (tv_index)
+        for (int64_t g = 0; g < B; g++)
+            if (tv_index[g] < 0 || tv_index[g] >= n_tv)
+                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: tv_index[%lld] = %d is outside [0, %d)", who, (long long)g, tv_index[g], n_tv);
+    if (B == 0) return TFHE_OK;
+    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key", who);
+    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the TV kernels have no DIAG instantiation)", who);
+    const TvHost th{tv, n_tv, tv_index};
+    return bootstrap_rows(c, who, 0, &th, n_out, in, out, B, with_keyswitch);
+}
+
 int32_t tfhe_bootstrap_tv_batch(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, const int32_t *in, int32_t *out, int64_t B,
                                 int32_t with_keyswitch) try
 {
     ENTER_CTX(c);
     if (!c) return TFHE_ERR_INVALID_ARG;
-    if (B < 0 || (B > 0 && (!in || !out || !tv))) return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_tv_batch: NULL argument or negative B");
-    if (n_tv < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_tv_batch: n_tv = %d (at least one table)", n_tv);
-    if (tv_index)
-        for (int64_t g = 0; g < B; g++)
-            if (tv_index[g] < 0 || tv_index[g] >= n_tv)
-                return c->set_err(TFHE_ERR_INVALID_ARG, "bootstrap_tv_batch: tv_index[%lld] = %d is outside [0, %d)", (long long)g, tv_index[g], n_tv);
-    if (B == 0) return TFHE_OK;
-    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "bootstrap_tv_batch: context is multi-key");
-    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "bootstrap_tv_batch: measure_margin is on (the TV kernels have no DIAG instantiation)");
-    const TvHost th{tv, n_tv, tv_index};
-    return bootstrap_rows(c, "bootstrap_tv_batch", 0, &th, in, out, B, with_keyswitch);
+    return bootstrap_tv_rows(c, "bootstrap_tv_batch", tv, n_tv, tv_index, 1, in, out, B, with_keyswitch);
 }
 ABI_CATCH(c, "tfhe_bootstrap_tv_batch")
+
+int32_t tfhe_bootstrap_tv_multi_batch(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out, const int32_t *in,
+                                      int32_t *out, int64_t B, int32_t with_keyswitch) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    return bootstrap_tv_rows(c, "bootstrap_tv_multi_batch", tv, n_tv, tv_index, n_out, in, out, B, with_keyswitch);
+}
+ABI_CATCH(c, "tfhe_bootstrap_tv_multi_batch")
 
 int32_t tfhe_keyswitch_batch(tfhe_ctx *c, const int32_t *in, int32_t *out, int64_t B) try
 {

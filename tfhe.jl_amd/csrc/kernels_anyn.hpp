@@ -262,6 +262,7 @@ __global__ __launch_bounds__(512) void TV_KERNEL(blind_rotate_kernel)(TV_ARGS(Ar
         else ext[(size_t)c * N + N - j] = (int32_t)(0u - (uint32_t)v);
     }
     if (tid == 0) ext[(size_t)(K1 - 1) * N] = acc[(size_t)(K1 - 1) * N];
+    store_bodies(P, w, tid, acc + (size_t)(K1 - 1) * N, N);
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0);
 }
 

@@ -17,10 +17,14 @@ using namespace tfhe;
 // X^{-barb} tv[tv_index[w]] instead of X^{-barb} (mu, ..., mu).  Everywhere else kTV is false and the kernels are what they were.
 // A TV kernel takes its family's argument struct extended by the tables (WithTv): the structs themselves are unchanged, so no kernel
 // argument of the existing kernels moves (blind_rotate_kernel_h2's second argument and the hidden arguments follow the first).
+// Multi-output TV batches (tfhe_bootstrap_tv_multi_batch) also pass `bodies`: the kernel then writes the accumulator's body
+// coefficients j N / n_out, j < n_out, of rotation w to bodies[w][j] (store_bodies); a plain TV batch passes NULL.
 template <class A>
 struct WithTv : A {
     const int32_t *tv;        // [n_tv][N] test polynomials
     const int32_t *tv_index;  // [R] the table of each rotation, in [0, n_tv)
+    int32_t *bodies;          // [R][n_out], or NULL
+    int32_t n_out;            // a power of two, 1 <= n_out <= min(32, N / 4) where bodies != NULL
 };
 #ifdef TFHE_TV_KERNELS
 #define TV_KERNEL(name) name##_tv
@@ -39,6 +43,16 @@ template <class A>
 __device__ __forceinline__ const int32_t *tv_of(const WithTv<A> &P, size_t w, int N)
 {
     return P.tv + (size_t)__builtin_amdgcn_readfirstlane(P.tv_index[w]) * N;
+}
+// The body coefficients of a multi-output TV batch: bodies[w][j] = body[j N / n_out] for lanes j < n_out (<= 32, one wave), where
+// body[c] is coefficient c of the final accumulator's body polynomial (body[0] is what the extraction writes).  Called by the
+// lanes of the wave that writes the extracted body, after the same barrier; nothing for the mu kernels and for plain TV batches.
+template <class A>
+__device__ __forceinline__ void store_bodies(const A &, size_t, int, const int32_t *, int) {}
+template <class A>
+__device__ __forceinline__ void store_bodies(const WithTv<A> &P, size_t w, int lane, const int32_t *body, int N)
+{
+    if (P.bodies && lane < P.n_out) P.bodies[w * P.n_out + lane] = body[lane * (N / P.n_out)];
 }
 
 // Diagnostics written only by the DIAG instantiations (tfhe_set_option("measure_margin", 1)):

@@ -94,3 +94,44 @@ __global__ void trivial_gates_kernel(const int32_t *in0, const int32_t *__restri
     }
 }
 
+
+// Multi-output programmable bootstrapping (tfhe_bootstrap_tv_multi_batch): sample j of row g is the extraction of row g's final
+// accumulator at coefficient c_j = j N / K instead of 0 (tlwe.jl:55-59 generalised), made from the index-0 extraction ext[g] and the
+// body coefficients bodies[g][j] the TV kernel wrote.  Mask polynomial i of out[g][j] = X^{c_j} (mask polynomial i of ext[g]):
+// a[u] = e[u - c_j] for u >= c_j, -e[N + u - c_j] for u < c_j; its body = bodies[g][j].  ext: [B][W], bodies: [B][K] = [B K],
+// out: [B][K][W] = [B K][W], W = k N + 1.  out is one flat array of `total` = B K W words: thread t writes words 4t .. 4t + 3 with one
+// 16-byte store (out is 256-byte aligned; the last, partial group word by word) and reads its source words with dword loads,
+// consecutive threads reading consecutive words of a row.  A row spans at least N + 1 > 4 words, so four words cross at most one row end.
+__global__ __launch_bounds__(256) void extract_shift_kernel(const int32_t *__restrict__ ext, const int32_t *__restrict__ bodies,
+                                                            int32_t *__restrict__ out, size_t total, int W, int log2N, int log2K)
+{
+    const size_t f0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (f0 >= total) return;
+    size_t r = f0 / (size_t)W;                    // output row g K + j
+    int p = (int)(f0 - r * (size_t)W);            // word within the row
+    const int Nm = (1 << log2N) - 1;
+    int32_t v[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        int32_t x = 0;
+        if (f0 + q < total) {
+            if (p == W - 1) {
+                x = bodies[r];
+            } else {
+                const int c = (int)(r & ((1u << log2K) - 1)) << (log2N - log2K);
+                const int u = p & Nm, s = u - c;
+                const uint32_t e = (uint32_t)ext[(r >> log2K) * (size_t)W + (p - u) + (s & Nm)];
+                x = (int32_t)(s >= 0 ? e : 0u - e);
+            }
+        }
+        v[q] = x;
+        if (++p == W) { p = 0; r++; }
+    }
+    if (f0 + 4 <= total) {
+        *reinterpret_cast<int4 *>(out + f0) = make_int4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (f0 + q < total) out[f0 + q] = v[q];
+    }
+}

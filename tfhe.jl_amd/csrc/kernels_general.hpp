@@ -145,5 +145,6 @@ __global__ __launch_bounds__(64, 1) void TV_KERNEL(blind_rotate_kernel_general)(
             else ext[(size_t)c * N + N - j] = (int32_t)(0u - (uint32_t)v);
         }
     if (lane == 0) ext[(size_t)(K1 - 1) * N] = acc[(K1 - 1) * kImgN + kMir];
+    store_bodies(P, w, lane, acc + (K1 - 1) * kImgN + kMir, N);
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0);
 }

@@ -366,4 +366,5 @@ __global__ __launch_bounds__(256 * L, 1) void TV_KERNEL(blind_rotate_kernel_h2)(
     int32_t *ext = P.ext + w * (kN + 1);
     if (wv == 0) extract_mask_poly(lane, acc_all, ext);
     else if (tid == 64) ext[kN] = acc_all[kImg + kMir];
+    if (wv == 1) store_bodies(P, w, lane, acc_all + kImg + kMir, kN);
 }

@@ -127,6 +127,7 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_k2)(
             else ext[c * kN + kN - jj] = (int32_t)(0u - (uint32_t)v);
         }
     if (lane == 0) ext[2 * kN] = acc_lds[2 * kN];
+    store_bodies(P, w, lane, acc_lds + 2 * kN, kN);
 }
 
 // ---- k = 2, small batches and the last round of a large one: THREE waves per blind rotation (round 5) ------------------
@@ -230,4 +231,5 @@ __global__ __launch_bounds__(192, 2) void TV_KERNEL(blind_rotate_kernel_k2w3)(TV
     int32_t *ext = P.ext + w * (2 * kN + 1);
     if (wv < 2) extract_mask_poly(lane, acc_lds, ext + (size_t)wv * kN);
     else if (lane == 0) ext[2 * kN] = acc_lds[kMir];
+    if (wv == 2) store_bodies(P, w, lane, acc_lds + kMir, kN);
 }

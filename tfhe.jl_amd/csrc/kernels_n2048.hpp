@@ -416,6 +416,7 @@ __global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(blind_rotate_kernel_n20
         else ext[kN2 - j] = (int32_t)(0u - (uint32_t)v);
     }
     if (tid_e == 0) ext[kN2] = acc_lds[kImg2 + kMir];
+    store_bodies(P, w, tid_e, acc_lds + kImg2 + kMir, kN2);
 }
 
 // (Round 5, measured and removed — commit "Experiment: one wave per rotation at N = 2048": ONE wave running both halves of the

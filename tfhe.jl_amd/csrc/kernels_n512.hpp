@@ -173,6 +173,7 @@ __global__ __launch_bounds__(64 * RW, 3) void TV_KERNEL(blind_rotate_kernel_n512
         else ext[kN5 - j] = (int32_t)(0u - (uint32_t)v);
     }
     if (lane == 0) ext[kN5] = acc_lds[kImg5 + kMir];
+    store_bodies(P, w, lane, acc_lds + kImg5 + kMir, kN5);
 }
 
 #ifdef TFHE_EMIT_KEYPREP_KERNELS       // (defined by engine_keys.hip, the one translation unit that launches them)
@@ -324,4 +325,5 @@ __global__ __launch_bounds__(128, 3) void TV_KERNEL(blind_rotate_kernel_n512w2)(
     } else if (lane == 0) {
         ext[kN5] = acc_all[kImg5 + kMir];
     }
+    if (wv == 1) store_bodies(P, w, lane, acc_all + kImg5 + kMir, kN5);
 }

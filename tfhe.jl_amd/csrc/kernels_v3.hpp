@@ -195,5 +195,6 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
     int32_t *ext = P.ext + w * (kN + 1);
     extract_mask_poly(lane, acc_lds, ext);
     if (lane == 0) ext[kN] = acc_lds[kImg + kMir];
+    store_bodies(P, w, lane, acc_lds + kImg + kMir, kN);
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0);
 }

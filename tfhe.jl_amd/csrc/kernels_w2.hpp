@@ -117,4 +117,5 @@ __global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(blind_rotate_kernel_w2)
     int32_t *ext = P.ext + w * (kN + 1);
     if (wv == 0) extract_mask_poly(lane, acc_all, ext);
     else if (lane == 0) ext[kN] = acc_all[kImg + kMir];
+    if (wv == 1) store_bodies(P, w, lane, acc_all + kImg + kMir, kN);
 }

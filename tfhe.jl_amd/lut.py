@@ -7,6 +7,13 @@ bootstrap.jl:50-59) returns the body v[phi] for phi in [0, N) and -v[phi - N] fo
 phase; make_test_vector(f, p, N, q) fills the N / p coefficients of window m with lut_encode(f(m), q), so the result encrypts f(m)
 in Z_q.  The output's noise is that of a fresh bootstrap, whatever the input's was, and samples combine linearly in between
 (LweSampleArray's +, -, integer scale and add_constant), which is how the functions chain.
+
+Several functions of one input from one blind rotation (Engine.bootstrap_tv_multi, tfhe_bootstrap_tv_multi_batch): sample j of K
+(a power of two) is extracted at the accumulator's coefficient j N / K, so its body is v[phi + j N / K].  The input m of Z_p must
+then be encrypted as a message of Z_{pK} (lut_encrypt(rng, sk, m, p * K), or any sample whose phase is within +-1/(4pK) of
+lut_encode(m, p * K)): phi lies in window m of Z_{pK}, phi + j N / K in window j p + m, below N, so no negacyclic sign enters.
+make_multi_test_vector([f_0, ..., f_{K-1}], p, N, q) is the table of g(j p + m) = f_j(m); output j encrypts f_j(m) in Z_q.
+The price is log2 K bits of message space: the input's noise must stay within a window K times narrower, and p K <= N / 2.
 """
 import numpy as np
 
@@ -73,3 +80,44 @@ def programmable_bootstrap(ck, samples, tables_or_functions, index=None, p=8, q=
     tables = np.stack([make_test_vector(t, p, eng.N, q) if callable(t) else np.asarray(t, np.int32) for t in items])
     data = samples.data if isinstance(samples, LweSampleArray) else np.asarray(samples, np.int32)
     return LweSampleArray(eng.bootstrap_tv(tables, data, index=index, with_keyswitch=with_keyswitch))
+
+
+def make_multi_test_vector(fs, p, N, q=None):
+    """The packed test polynomial of the K = len(fs) functions fs[j]: Z_p -> Z_q (q defaults to p) for one multi-output blind
+    rotation: make_test_vector(g, p K, N, q) with g(j p + m) = fs[j](m).  K a power of two, p >= 2 a power of two, p K <= N / 2."""
+    fs = list(fs)
+    K = len(fs)
+    if K < 1 or K & (K - 1):
+        raise ValueError(f"K = {K} functions: a power of two >= 1")
+    _log2(p)
+    if p * K > N // 2:
+        raise ValueError(f"p K = {p * K} > N/2 = {N // 2}")
+    return make_test_vector(lambda x: fs[x // p](x % p), p * K, N, p if q is None else q)
+
+
+def programmable_bootstrap_multi(ck, samples, fs_or_tables, p, q=None, index=None, with_keyswitch=True, device=0, n_out=None):
+    """[f_0(m), ..., f_{K-1}(m)] for every sample of m in Z_p encrypted in Z_{pK}, from one batch of blind rotations on the GPU:
+    a list of K LweSampleArrays (keyswitched back to the LWE key unless with_keyswitch is False, then [B][k N + 1] words under the
+    extracted TLWE key).
+
+    `fs_or_tables`: a list of K callables Z_p -> Z_q (one packed table, make_multi_test_vector), a list of such lists with the same
+    K (`index[g]` picks row g's, None: the first), or int32 packed tables [N] / [n_tv][N], for which `n_out` gives K."""
+    eng = ck.engine(device)
+    items = list(fs_or_tables) if isinstance(fs_or_tables, (list, tuple)) else [fs_or_tables]
+    if items and all(callable(f) for f in items):
+        items = [items]
+    tables, ks = [], set()
+    for t in items:
+        if isinstance(t, (list, tuple)) and all(callable(f) for f in t):
+            ks.add(len(t))
+            tables.append(make_multi_test_vector(t, p, eng.N, q))
+        else:
+            tables.extend(np.atleast_2d(np.asarray(t, np.int32)))
+    if n_out is not None:
+        ks.add(int(n_out))
+    if len(ks) != 1:
+        raise ValueError(f"the number of outputs is ambiguous: {sorted(ks) or 'not given'} (pass n_out with raw tables)")
+    K = ks.pop()
+    data = samples.data if isinstance(samples, LweSampleArray) else np.asarray(samples, np.int32)
+    out = eng.bootstrap_tv_multi(np.stack(tables), data, K, index=index, with_keyswitch=with_keyswitch)
+    return [LweSampleArray(np.ascontiguousarray(out[:, j])) for j in range(K)]
