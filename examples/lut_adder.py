@@ -9,7 +9,11 @@ a 32-level carry chain) runs as Circuit.run_batch over the same 1024 instances.
 
 The third variant encrypts every digit as a message of Z_16 (p = 8 messages in a space of p K = 16, K = 2) and takes digit and
 carry from ONE rotation per sum (tfhe_bootstrap_tv_multi_batch, make_multi_test_vector): 8 calls of 1024 rotations.  Its noise
-headroom is half the Z_8 adder's, so it reports its wrong sums instead of asserting that there are none."""
+headroom is half the Z_8 adder's, so it reports its wrong sums instead of asserting that there are none.
+
+Both LUT adders also run as a Circuit of lut / lut_multi nodes (lut_adder_circuit) with run_batch over the same 1024 instances: the
+digit sums are formed on the device from the wire table (tfhe_lut_level), nothing crosses PCIe between the digits, and the result
+words are those of the host-orchestrated adders."""
 import os
 import sys
 import time
@@ -62,6 +66,35 @@ def lut_add16_multi(ck, a, b, device=0):
     return out + [carry]
 
 
+DIGIT = lambda s: s % 4                       # (one callable each: equal (f, p, q) share a table per level)
+CARRY = lambda s: s >= 4
+
+
+def lut_adder_circuit(multi=False):
+    """lut_add16 (multi=False: two lut nodes per digit, Z_8) or lut_add16_multi (one lut_multi node per digit, Z_16) as a Circuit:
+    inputs a_0 .. a_7, b_0 .. b_7 (digit samples), outputs the 8 digits and the carry out.  Row sums a + b + carry - const are the
+    host adders' (LweSampleArray + and add_constant, mod 2^32), so the words are the same."""
+    space = P_MULTI if multi else P
+    c = tfhe.Circuit()
+    a, b = c.inputs(DIGITS), c.inputs(DIGITS)
+    outs, carry = [], None
+    for i in range(DIGITS):
+        terms = [a[i], b[i]] + ([] if carry is None else [carry])
+        const = -(1 if carry is None else 2) * int(lut_encode(0, space))
+        if multi:
+            digit, carry = c.lut_multi([DIGIT, CARRY], terms, P, space, const=const)
+        else:
+            digit, carry = c.lut(DIGIT, terms, P, const=const), c.lut(CARRY, terms, P, const=const)
+        outs.append(digit)
+    c.set_outputs(outs + [carry])
+    return c
+
+
+def circuit_inputs(a, b):
+    """[DIGITS] LweSampleArrays of M samples, twice -> run_batch's inputs [M][2 DIGITS][n + 1]."""
+    return np.ascontiguousarray(np.stack([d.data for d in a + b], axis=1))
+
+
 def decrypt_sum(sk, digits, space=P):
     return sum(lut_decrypt(sk, d, space).astype(np.int64) << (2 * i) for i, d in enumerate(digits))
 
@@ -102,6 +135,19 @@ def main(M=1024):
     t_multi = time.perf_counter() - t0
     wrong_multi = int(np.sum(decrypt_sum(sk, digits16, P_MULTI) != x + y))
 
+    res_words = {}
+    t_circ = {}
+    for multi, (da, db, host) in ((False, (a, b, digits)), (True, (a16, b16, digits16))):
+        lc = lut_adder_circuit(multi)
+        inp = circuit_inputs(da, db)
+        lc.run_batch(ck, inp)                                     # (warm-up: workspaces and staging blocks at full size)
+        t0 = time.perf_counter()
+        res = lc.run_batch(ck, inp)
+        t_circ[multi] = time.perf_counter() - t0
+        assert np.array_equal(res, np.stack([d.data for d in host], axis=1)), "LUT circuit: words differ from the host adder's"
+        res_words[multi] = res
+    assert np.array_equal(decrypt_sum(sk, [tfhe.LweSampleArray(res_words[False][:, i]) for i in range(DIGITS + 1)]), x + y)
+
     circ = gate_adder()
     bits = lambda v: np.stack([(v >> i) & 1 for i in range(16)], axis=1).astype(bool)
     inputs = np.stack([tfhe.encrypt(rng, sk, np.concatenate([bits(x)[m], bits(y)[m]])).data for m in range(M)])
@@ -116,6 +162,9 @@ def main(M=1024):
     print(f"  LUT digits (8 calls of {2 * M} rotations): {t_lut * 1e3:8.1f} ms")
     print(f"  LUT digits, digit and carry from one rotation (8 calls of {M} rotations, Z_16): {t_multi * 1e3:8.1f} ms, "
           f"{wrong_multi} wrong sums of {M}")
+    print(f"  LUT digits as a device circuit (run_batch, {DIGITS} levels of {2 * M} rotations, Z_8):         {t_circ[False] * 1e3:8.1f} ms")
+    print(f"  LUT digits as a device circuit, one rotation per digit (run_batch, Z_16):              {t_circ[True] * 1e3:8.1f} ms, "
+          "words identical to the host loops")
     print(f"  ripple-carry gate adder ({len(circ.levels())} levels):   {t_gate * 1e3:8.1f} ms")
     ck.close()
 

@@ -280,6 +280,24 @@ int32_t tfhe_wires_gather(tfhe_ctx *ctx, const int32_t *wires, int64_t count, in
  * every participating device's stream, the exchange of operand rows between devices included); ordered with later calls. */
 int32_t tfhe_gates_level(tfhe_ctx *ctx, const uint8_t *opcodes, const int32_t *a, const int32_t *b,
                          const int32_t *c, const int32_t *out, int64_t B);
+/* Programmable bootstrapping on the wire table (addition within ABI v7).  For every row g < B:
+ *   x_g = sum over t in [term_start[g], term_start[g+1]) of term_coef[t] * wire[term_wire[t]], plus cst[g] on the body (mod 2^32)
+ *   wire[out[g*n_out + j]] = keyswitch of the sample extracted at coefficient j N / n_out of the blind rotation of x_g
+ *                            with test polynomial tv[tv_index[g]],   j < n_out
+ * n_out, tv, n_tv, tv_index (NULL: table 0 for every row): as tfhe_bootstrap_tv_multi_batch.  cst may be NULL (all zero).
+ * term_start: host int32 [B+1], from 0, never decreasing (a row without terms is the trivial sample (0, cst[g])); term_wire,
+ * term_coef: [term_start[B]]; out: [B*n_out].  Every index inside the table, no output wire written twice, no term reading a wire
+ * the call writes (TFHE_ERR_INVALID_ARG).  Asynchronous as tfhe_gates_level: every host array is staged before the call returns,
+ * so the caller may reuse them at once.  TFHE_ERR_STATE: a multi-key context or wire table, no wire table, measure_margin on;
+ * TFHE_ERR_NO_KEY: bootstrapping or keyswitch key missing.  tfhe_last_rotation_count reports B.  A multi-device context runs a
+ * level below "level_split_min" rows on its first device and cuts a wider one into equal contiguous shards, as tfhe_gates_level. */
+int32_t tfhe_lut_level(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out,
+                       const int32_t *term_start, const int32_t *term_wire, const int32_t *term_coef, const int32_t *cst,
+                       const int32_t *out, int64_t B);
+/* wire[out[g]] = x_g as above, with no bootstrap (exact mod-2^32 arithmetic: LweSampleArray's +, integer scale, add_constant).
+ * Arguments, checks, errors (but TFHE_ERR_NO_KEY and measure_margin) and asynchrony as tfhe_lut_level. */
+int32_t tfhe_linear_level(tfhe_ctx *ctx, const int32_t *term_start, const int32_t *term_wire, const int32_t *term_coef,
+                          const int32_t *cst, const int32_t *out, int64_t B);
 
 /* bootstrap(bk, ks, mu, x) (bootstrap.jl:92-95) if with_keyswitch != 0, else
  * bootstrap_wo_keyswitch(bk, mu, x) (bootstrap.jl:69-82).

@@ -419,6 +419,40 @@ function bootstrap_tv_multi(gck::GpuCloudKey, tables::AbstractMatrix{Int32}, xs,
     [unflatten(out[:, j, :], LweParams(width)) for j in 1:n_out]
 end
 
+"""
+    bootstrap_tv(gck, tables, d::GpuLweArray, index=nothing)              ->  GpuLweArray
+    bootstrap_tv_multi(gck, tables, d::GpuLweArray, n_out, index=nothing)  ->  Vector{GpuLweArray}
+
+`bootstrap_tv` / `bootstrap_tv_multi` on device-resident samples (tfhe_lut_level with one term of coefficient 1 per row): the results
+are new rows of the wire table, keyswitched, so a chain of LUTs never crosses PCIe.  Asynchronous as the gates on GpuLweArrays.
+"""
+function lut_on_device(g::GpuCloudKey, tables::AbstractMatrix{Int32}, d::GpuLweArray, n_out::Integer, index)
+    d.key === g || error("GpuLweArray belongs to another GpuCloudKey")
+    B = length(d)
+    N = g.params.tlwe_polynomial_degree
+    size(tables, 1) == N || error("tfhe_mi355x: test polynomials must have N = ", N, " rows")
+    1 <= n_out <= 32 || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32)")
+    B == 0 && return Int32[]
+    tv = Matrix{Int32}(tables)
+    idx = index === nothing ? nothing : Int32.(collect(index) .- 1)
+    term_start = collect(Int32, 0:B)
+    coef = ones(Int32, B)
+    out = alloc_rows!(g, B * n_out)
+    GC.@preserve tv idx term_start coef out d @locked g.ctx check(g.ctx, ccall((:tfhe_lut_level, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64),
+        g.ctx, tv, Int32(size(tv, 2)), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), Int32(n_out), term_start, d.rows, coef,
+        Ptr{Int32}(C_NULL), out, B))
+    out
+end
+
+bootstrap_tv(g::GpuCloudKey, tables::AbstractMatrix{Int32}, d::GpuLweArray, index=nothing) =
+    GpuLweArray(g, lut_on_device(g, tables, d, 1, index))
+
+function bootstrap_tv_multi(g::GpuCloudKey, tables::AbstractMatrix{Int32}, d::GpuLweArray, n_out::Integer, index=nothing)
+    out = lut_on_device(g, tables, d, n_out, index)          # row g's output j is out[(g - 1) n_out + j]
+    [GpuLweArray(g, out[j:n_out:end]) for j in 1:n_out]
+end
+
 # page-locked Int32 matrix (tfhe_host_alloc): the copies of a streamed batch are then single DMA transfers that overlap kernels
 function pinned_matrix(rows::Int, cols::Int)
     p = Ref{Ptr{Cvoid}}(C_NULL)

@@ -15,7 +15,7 @@ from .mk_gates import (mk_gate_or, mk_gate_and, mk_gate_xor, mk_gate_xnor, mk_ga
                        mk_gate_orny, mk_gate_oryn, mk_gate_mux, mk_gate_not, mk_gate_constant, mk_gates_batch)
 from .circuit import Circuit
 from .lut import (lut_encode, lut_decode, lut_encrypt, lut_decrypt, make_test_vector, programmable_bootstrap, make_multi_test_vector,
-                  programmable_bootstrap_multi)
+                  programmable_bootstrap_multi, make_gate_test_vector, GATE_BIT_TO_Z2)
 from .serialize import save_cloud_key, load_cloud_key
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
 
@@ -29,6 +29,6 @@ __all__ = [
     "mk_gate_or", "mk_gate_and", "mk_gate_xor", "mk_gate_xnor", "mk_gate_nor", "mk_gate_andny", "mk_gate_andyn",
     "mk_gate_orny", "mk_gate_oryn", "mk_gate_mux", "mk_gate_not", "mk_gate_constant", "mk_gates_batch",
     "Circuit", "lut_encode", "lut_decode", "lut_encrypt", "lut_decrypt", "make_test_vector", "programmable_bootstrap",
-    "make_multi_test_vector", "programmable_bootstrap_multi",
+    "make_multi_test_vector", "programmable_bootstrap_multi", "make_gate_test_vector", "GATE_BIT_TO_Z2",
     "save_cloud_key", "load_cloud_key", "Engine", "EngineError", "OPCODES", "LIB_PATH", "pinned_empty",
 ]

@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "tfhe_mk_expand_load_bootstrap_key", "tfhe_keygen_cloud_key", "tfhe_host_alloc", "tfhe_host_free",
     "tfhe_timing_history_ms", "tfhe_gates_batch_submit", "tfhe_gates_batch_wait", "tfhe_last_device_count",
     "tfhe_get_option", "tfhe_ctx_synchronize", "tfhe_mk_gates_batch", "tfhe_mk_wires_alloc", "tfhe_mk_gates_level",
-    "tfhe_bootstrap_tv_batch", "tfhe_bootstrap_tv_multi_batch",
+    "tfhe_bootstrap_tv_batch", "tfhe_bootstrap_tv_multi_batch", "tfhe_lut_level", "tfhe_linear_level",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -136,6 +136,9 @@ def load():
     lib.tfhe_wires_upload.argtypes = [vp, i64, i64, vp]
     lib.tfhe_wires_download.argtypes = [vp, i64, i64, vp]
     lib.tfhe_gates_level.argtypes = [vp, vp, vp, vp, vp, vp, i64]
+    if hasattr(lib, "tfhe_lut_level"):
+        lib.tfhe_lut_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64]
+        lib.tfhe_linear_level.argtypes = [vp, vp, vp, vp, vp, vp, i64]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -417,6 +420,45 @@ class Engine:
                 raise ValueError("index arrays must have one entry per gate")
         self._check(self._lib.tfhe_gates_level(self._h, _ptr(ops), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
                                                _ptr(arrs[3]), ops.size))
+
+    def _level_terms(self, term_start, term_wire, term_coef, cst, out, per_row):
+        start = _i32c(term_start).reshape(-1)
+        B = start.size - 1
+        if B < 0:
+            raise ValueError("term_start must have B + 1 entries")
+        T = int(start[-1]) if B >= 0 else 0
+        wire, coef = _i32c(term_wire).reshape(-1), _i32c(term_coef).reshape(-1)
+        if wire.size != coef.size or wire.size < T:
+            raise ValueError(f"term_wire / term_coef must have term_start[B] = {T} entries, got {wire.size} / {coef.size}")
+        c = None if cst is None else _i32c(cst).reshape(-1)
+        if c is not None and c.size != B:
+            raise ValueError(f"cst must have one entry per row ({B}), got {c.size}")
+        o = _i32c(out).reshape(-1)
+        if o.size != B * per_row:
+            raise ValueError(f"out must have {B * per_row} entries (B n_out), got {o.size}")
+        return start, wire, coef, c, o, B
+
+    def lut_level(self, tables, term_start, term_wire, term_coef, cst, out, index=None, n_out=1):
+        """Programmable bootstrapping on the wire table (tfhe_lut_level): row g's sample is sum_t term_coef[t] wire[term_wire[t]] over
+        t in [term_start[g], term_start[g+1]), plus cst[g] on the body (mod 2^32; cst None: 0); its n_out results (bootstrap_tv_multi:
+        tables[index[g]], index None: table 0) go to wires out[g n_out + j].  Asynchronous; the arrays may be reused at once."""
+        tables = _i32c(np.atleast_2d(tables))
+        if tables.ndim != 2 or tables.shape[1] != self.N:
+            raise ValueError(f"test polynomials must be [n_tv][{self.N}], got {tables.shape}")
+        n_out = int(n_out)
+        start, wire, coef, c, o, B = self._level_terms(term_start, term_wire, term_coef, cst, out, max(n_out, 1))
+        idx = None
+        if index is not None:
+            idx = _i32c(index).reshape(-1)
+            if idx.size != B:
+                raise ValueError(f"index must have one entry per row ({B}), got {idx.size}")
+        self._check(self._lib.tfhe_lut_level(self._h, _ptr(tables), tables.shape[0], _ptr(idx), n_out, _ptr(start), _ptr(wire), _ptr(coef),
+                                             _ptr(c), _ptr(o), B))
+
+    def linear_level(self, term_start, term_wire, term_coef, cst, out):
+        """wire[out[g]] = the combination of lut_level's row g itself, no bootstrap (tfhe_linear_level): exact mod-2^32 arithmetic."""
+        start, wire, coef, c, o, B = self._level_terms(term_start, term_wire, term_coef, cst, out, 1)
+        self._check(self._lib.tfhe_linear_level(self._h, _ptr(start), _ptr(wire), _ptr(coef), _ptr(c), _ptr(o), B))
 
     # ---- multi-key ----
     def mk_load_bootstrap_key(self, bk_i32, parties):

@@ -4,10 +4,21 @@ Real workloads are gate DAGs (examples/tutorial.jl:42-62: a 16-deep XNOR->MUX ch
 MUXes).  A Circuit records gates with the reference's gate names, assigns every gate the level
 1 + max(level of its operands), and runs level by level: one tfhe_gates_level call per level over all the
 level's independent gates, ciphertexts staying in the engine's wire table on the GPU — only the inputs go
-up and only the requested outputs come down."""
+up and only the requested outputs come down.
+
+Integer nodes join the gates in the same levels (programmable bootstrapping, tfhe_jl_amd.lut): `lut(f, terms, p)` is one blind
+rotation of the integer combination of `terms` with test polynomial make_test_vector(f, p, N, q), `lut_multi(fs, terms, p)` K results
+from one rotation, `linear(terms)` the combination itself.  A term is a wire or (wire, integer coefficient); `const` is a Torus32 word
+added to the body.  Linear nodes are folded into the terms of whatever reads them through a LUT or another linear node (coefficients
+multiplied, constants summed mod 2^32), so a LUT never waits a level for one; a linear node is computed (tfhe_linear_level) only if
+a gate reads it or it is an output.  A level runs as one tfhe_gates_level, one tfhe_lut_level per distinct K and one
+tfhe_linear_level, all on the context's stream.  The caller chooses the coefficients: their noise growth is not checked."""
+import numbers
+
 import numpy as np
 
 from ._lib import OPCODES
+from .numeric import wrap32
 from .lwe import LweSample, LweSampleArray
 from .mk_keys import MKCloudKey, MKLweSample
 
@@ -20,6 +31,9 @@ class Circuit:
         self._gates = []          # (opcode name, a, b, c) with wire ids
         self._level = []          # level per wire (inputs: 0)
         self._outputs = []
+        self._gate_wire = []      # output wire of gate g
+        self._linear = {}         # wire -> ({base wire: coefficient mod 2^32}, constant mod 2^32), terms folded to non-linear wires
+        self._luts = []           # (table key, K, terms {base wire: coefficient}, constant, [output wires])
 
     # ---- building -----------------------------------------------------------------------------------
     def input(self):
@@ -31,6 +45,79 @@ class Circuit:
 
     def inputs(self, count):
         return [self.input() for _ in range(count)]
+
+    def _check_wire(self, w):
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, numbers.Integral) or not (0 <= int(w) < len(self._level)):
+            raise ValueError(f"operand wire {w} does not exist")
+        return int(w)
+
+    def _fold(self, terms, const):
+        """terms (wire or (wire, coef)) + const -> ({non-linear wire: coef mod 2^32}, const mod 2^32), linear nodes expanded."""
+        if isinstance(const, (bool, np.bool_)) or not isinstance(const, numbers.Integral):
+            raise ValueError(f"const {const!r} is not an integer (a Torus32 word)")
+        acc, cst = {}, int(const) % 2**32
+        for t in terms:
+            w, coef = (t, 1) if not isinstance(t, (tuple, list)) else tuple(t)
+            w = self._check_wire(w)
+            if isinstance(coef, (bool, np.bool_)) or not isinstance(coef, numbers.Integral):
+                raise ValueError(f"coefficient {coef!r} of wire {w} is not an integer")
+            coef = int(coef)
+            inner, inner_c = self._linear.get(w, ({w: 1}, 0))
+            for b, cb in inner.items():
+                acc[b] = (acc.get(b, 0) + coef * cb) % 2**32
+            cst = (cst + coef * inner_c) % 2**32
+        return {b: v for b, v in acc.items() if v}, cst
+
+    def _new_wire(self, level):
+        self._level.append(level)
+        return len(self._level) - 1
+
+    def linear(self, terms, const=0):
+        """A wire holding sum coef * wire + const (mod 2^32), no bootstrap: LweSampleArray's +, integer scale and add_constant."""
+        folded, cst = self._fold(terms, const)
+        w = self._new_wire(1 + max((self._level[b] for b in folded), default=0))
+        self._linear[w] = (folded, cst)
+        return w
+
+    def _add_lut(self, key, K, terms, const):
+        folded, cst = self._fold(terms, const)
+        level = 1 + max((self._level[b] for b in folded), default=0)
+        outs = [self._new_wire(level) for _ in range(K)]
+        self._luts.append((key, K, folded, cst, outs))
+        return outs
+
+    @staticmethod
+    def _spaces(p, q):
+        for v, what in ((p, "p"), (q, "q")):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 2 or v & (v - 1)):
+                raise ValueError(f"{what} = {v}: a power of two >= 2")
+        return int(p), None if q is None else int(q)
+
+    def lut(self, f, terms, p, q=None, const=0):
+        """One wire: f(m) in Z_q (q defaults to p) of the message m in Z_p that the combination of `terms` + const encrypts, by one
+        blind rotation with make_test_vector(f, p, N, q).  `f` may also be a raw int32 test polynomial [N] (lut.make_gate_test_vector:
+        a gate-encoded bit).  Equal (f, p, q) share one table per level."""
+        p, q = self._spaces(p, q)
+        if callable(f):
+            key = ("f", f, p, q)
+        else:
+            t = np.ascontiguousarray(f, dtype=np.int32)
+            if t.ndim != 1:
+                raise ValueError(f"a raw test polynomial is int32 [N], got shape {t.shape}")
+            key = ("raw", t.tobytes())
+        return self._add_lut(key, 1, terms, const)[0]
+
+    def lut_multi(self, fs, terms, p, q=None, const=0):
+        """K = len(fs) wires from ONE blind rotation: fs[j](m) in Z_q for the message m of Z_p encrypted in Z_{pK}
+        (make_multi_test_vector; K a power of two, p K <= N / 2)."""
+        p, q = self._spaces(p, q)
+        fs = tuple(fs)
+        K = len(fs)
+        if K < 1 or K > 32 or K & (K - 1):
+            raise ValueError(f"K = {K} functions: a power of two, 1 <= K <= 32")
+        if not all(callable(f) for f in fs):
+            raise ValueError("lut_multi takes callables")
+        return self._add_lut(("multi", fs, p, q), K, terms, const)
 
     def gate(self, name, *operands):
         name = name.upper()
@@ -44,6 +131,7 @@ class Circuit:
                 raise ValueError(f"operand wire {w} does not exist")
         ops = list(operands) + [-1] * (3 - arity)
         self._gates.append((name, ops[0], ops[1], ops[2]))
+        self._gate_wire.append(len(self._level))
         self._level.append(1 + max([self._level[w] for w in operands], default=0))
         return len(self._level) - 1
 
@@ -75,12 +163,16 @@ class Circuit:
         return list(self._outputs)
 
     def levels(self):
-        """List of levels; each level is a list of gate indices (gate g drives wire n_inputs + g)."""
+        """List of levels; each level is a list of gate indices (gate g drives wire gate_wire(g): n_inputs + g in a circuit of
+        gates only)."""
         depth = max(self._level, default=0)
         out = [[] for _ in range(depth)]
         for g in range(len(self._gates)):
-            out[self._level[self._n_inputs + g] - 1].append(g)
+            out[self._level[self._gate_wire[g]] - 1].append(g)
         return out
+
+    def gate_wire(self, g):
+        return self._gate_wire[g]
 
     def level_arrays(self):
         """Per level: (opcodes u8, a, b, c, out) index arrays as tfhe_gates_level takes them."""
@@ -90,9 +182,79 @@ class Circuit:
             a = np.array([max(self._gates[g][1], 0) for g in gates], np.int32)
             b = np.array([max(self._gates[g][2], 0) for g in gates], np.int32)
             c = np.array([max(self._gates[g][3], 0) for g in gates], np.int32)
-            out = np.array([self._n_inputs + g for g in gates], np.int32)
+            out = np.array([self._gate_wire[g] for g in gates], np.int32)
             res.append((ops, a, b, c, out))
         return res
+
+    def level_plan(self, N, M=1):
+        """Per level, what run (M = 1) and run_batch (M instances; wire w of instance i is row w M + i) call:
+        {"gates": (opcodes, a, b, c, out) or None, "lut": [(K, tables [n_tv][N], index, term_start, term_wire, term_coef, cst, out)]
+        in increasing K, "linear": (term_start, term_wire, term_coef, cst, out) or None}; the index arrays are int32 and spread over
+        the instances exactly as the gates' operands are.  Tables are built at ring degree N (ValueError for p K > N / 2)."""
+        from .lut import make_multi_test_vector, make_test_vector
+        inst = np.arange(M, dtype=np.int64)
+        spread = lambda w: (np.asarray(w, np.int64)[:, None] * M + inst[None, :]).reshape(-1).astype(np.int32)
+        read_by_gate = {w for (_, a, b, c) in self._gates for w in (a, b, c) if w >= 0}
+        outputs = set(self._outputs)
+        tables = {}
+
+        def table(key):
+            if key not in tables:
+                if key[0] == "raw":
+                    t = np.frombuffer(key[1], np.int32)
+                    if t.size != N:
+                        raise ValueError(f"raw test polynomial of {t.size} words, the ring has N = {N}")
+                elif key[0] == "f":
+                    t = make_test_vector(key[1], key[2], N, key[3])
+                else:
+                    t = make_multi_test_vector(list(key[1]), key[2], N, key[3])
+                tables[key] = t
+            return tables[key]
+
+        def rows(nodes, per_row):
+            """[(terms, const, outs)] -> spread (term_start, term_wire, term_coef, cst, out)."""
+            counts = np.array([len(t) for t, _, _ in nodes], np.int64)
+            wires = np.array([w for t, _, _ in nodes for w in sorted(t)], np.int64)
+            coefs = np.array([t[w] for t, _, _ in nodes for w in sorted(t)], np.int64)
+            first = np.concatenate([[0], np.cumsum(counts)])[:-1]
+            row_counts = np.repeat(counts, M)
+            start = np.concatenate([[0], np.cumsum(row_counts)]).astype(np.int64)
+            T = int(start[-1])
+            t_node = np.repeat(np.repeat(first, M), row_counts) + (np.arange(T) - np.repeat(start[:-1], row_counts))
+            term_wire = (wires[t_node] * M + np.repeat(np.tile(inst, len(nodes)), row_counts)).astype(np.int32)
+            term_coef = wrap32(coefs[t_node])
+            cst = wrap32(np.repeat(np.array([c for _, c, _ in nodes], np.int64), M))
+            outs = np.array([o for _, _, o in nodes], np.int64).reshape(len(nodes), 1, per_row)
+            out = (outs * M + inst[None, :, None]).reshape(-1).astype(np.int32)
+            return start.astype(np.int32), term_wire, term_coef, cst, out
+
+        gate_arrays = self.level_arrays()
+        plan = []
+        for li in range(len(gate_arrays)):
+            level = li + 1
+            ops, a, b, c, out = gate_arrays[li]
+            gates = (np.repeat(ops, M), spread(a), spread(b), spread(c), spread(out)) if ops.size else None
+            luts = []
+            for K in sorted({K for (_, K, _, _, outs) in self._luts if self._level[outs[0]] == level}):
+                nodes = [n for n in self._luts if n[1] == K and self._level[n[4][0]] == level]
+                keys = list(dict.fromkeys(n[0] for n in nodes))
+                tv = np.stack([table(k) for k in keys]).astype(np.int32)
+                index = np.repeat(np.array([keys.index(n[0]) for n in nodes], np.int32), M)
+                luts.append((K, tv, index) + rows([(n[2], n[3], n[4]) for n in nodes], K))
+            lin = [(t, cst, [w]) for w, (t, cst) in self._linear.items()
+                   if self._level[w] == level and (w in read_by_gate or w in outputs)]
+            plan.append({"gates": gates, "lut": luts, "linear": rows(lin, 1) if lin else None})
+        return plan
+
+    def _run_plan(self, eng, plan, mk):
+        level = eng.mk_gates_level if mk else eng.gates_level
+        for lv in plan:
+            if lv["gates"] is not None:
+                level(*lv["gates"])
+            for K, tv, index, start, wire, coef, cst, out in lv["lut"]:
+                eng.lut_level(tv, start, wire, coef, cst, out, index=index, n_out=K)
+            if lv["linear"] is not None:
+                eng.linear_level(*lv["linear"])
 
     # ---- execution ----------------------------------------------------------------------------------
     def run(self, ck, inputs, device=0):
@@ -113,14 +275,15 @@ class Circuit:
         (eng.mk_wires_alloc if mk else eng.wires_alloc)(self.num_wires)
         if self._n_inputs:
             eng.wires_upload(0, m)
-        level = eng.mk_gates_level if mk else eng.gates_level
+        if mk and (self._luts or self._linear):
+            raise ValueError("integer nodes (lut, lut_multi, linear) run on single-key contexts only")
+        plan = self.level_plan(eng.N)
         # no per-phase timing events while the levels run: each record keeps the stream's next kernel waiting ~5 us, and a level
         # of a narrow circuit is six short operations around one single-rotation kernel (tutorial circuit: 30.5 -> 30.1 ms)
         timing_before = eng.get_option("timing_events")              # (the engine is shared through ck.engine(): put the caller's setting back)
         eng.set_option("timing_events", 0)
         try:
-            for ops, a, b, c, out in self.level_arrays():
-                level(ops, a, b, c, out)
+            self._run_plan(eng, plan, mk)
             rows = eng.wires_gather(self._outputs)                    # one device gather + one copy for all outputs
             return rows if mk else LweSampleArray(rows)
         finally:
@@ -143,17 +306,17 @@ class Circuit:
         M = m.shape[0]
         if M == 0:
             return np.zeros((0, len(self._outputs), m.shape[2]), np.int32)
+        if mk and (self._luts or self._linear):
+            raise ValueError("integer nodes (lut, lut_multi, linear) run on single-key contexts only")
+        plan = self.level_plan(eng.N, M)
         (eng.mk_wires_alloc if mk else eng.wires_alloc)(self.num_wires * M)
-        level = eng.mk_gates_level if mk else eng.gates_level
         if self._n_inputs:
             eng.wires_upload(0, np.ascontiguousarray(m.transpose(1, 0, 2)).reshape(self._n_inputs * M, -1))
-        inst = np.arange(M, dtype=np.int32)
-        spread = lambda w: (w[:, None] * M + inst[None, :]).reshape(-1).astype(np.int32)      # wire ids -> rows, instance fastest
+        spread = lambda w: (w[:, None] * M + np.arange(M, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)      # wire ids -> rows, instance fastest
         timing_before = eng.get_option("timing_events")
         eng.set_option("timing_events", 0)
         try:
-            for ops, a, b, c, out in self.level_arrays():
-                level(np.repeat(ops, M), spread(a), spread(b), spread(c), spread(out))
+            self._run_plan(eng, plan, mk)
             rows = eng.wires_gather(spread(np.asarray(self._outputs, np.int32)))
         finally:
             eng.set_option("timing_events", timing_before)

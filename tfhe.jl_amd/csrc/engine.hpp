@@ -426,6 +426,16 @@ int32_t launch_prologue(tfhe_ctx *c, size_t R, const int32_t *d_in0, const int32
                         const uint8_t *d_kind, int words, hipStream_t s);
 int32_t run_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t B, const int32_t *d_in0, const int32_t *d_in1, const int32_t *d_in2,
                   int32_t *d_out, const int32_t *ia, const int32_t *ib, const int32_t *ic, const int32_t *io, hipStream_t s);
+int32_t launch_linear_prologue(tfhe_ctx *c, bool lut, size_t B, const int32_t *d_start, const int32_t *d_wire, const int32_t *d_coef,
+                               const int32_t *d_cst, const int32_t *d_out, hipStream_t s);
+// one level of tfhe_lut_level (tv != NULL; n_out samples per row) or tfhe_linear_level (tv == NULL) as the caller passed it: host arrays,
+// term_start rebased to 0 (engine_circuits.hip validates; run_int_level stages and queues it on a device context)
+struct IntLevel {
+    const int32_t *tv; int32_t n_tv; const int32_t *tv_index; int32_t n_out;
+    const int32_t *term_start, *term_wire, *term_coef, *cst, *out;
+    int64_t B;
+};
+int32_t run_int_level(tfhe_ctx *c, const IntLevel &L);
 int32_t launch_trivial(tfhe_ctx *c, size_t T, const int32_t *d_in0, const int32_t *d_ts, const int32_t *d_td, const uint8_t *d_top, int32_t *d_out,
                        int words, hipStream_t s);
 // engine_multikey.hip

@@ -374,3 +374,118 @@ int32_t tfhe_mk_gates_level(tfhe_ctx *c, const uint8_t *opcodes, const int32_t *
                         c->stream);
 }
 ABI_CATCH(c, "tfhe_mk_gates_level")
+
+// ---- integer levels: programmable bootstrapping and linear combinations on the wire table ----------------------------------
+// tfhe_lut_level / tfhe_linear_level (L.tv == NULL): term_start [B+1] from 0 and never decreasing, every index inside the table, no
+// output wire written twice, no term reading a wire the call writes; the tables, n_out and tv_index as tfhe_bootstrap_tv_multi_batch.
+// O(B + terms) whatever the size of the wire table: only the call's outputs are hashed, as validate_level does.
+static int32_t validate_int_level(tfhe_ctx *c, const char *who, int64_t num_wires, int N, const IntLevel &L)
+{
+    const bool lut = L.tv != nullptr;
+    const int64_t B = L.B;
+    if (B > (int64_t)1 << 30) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: B too large", who);
+    if (lut) {
+        if (L.n_tv < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: n_tv = %d (at least one table)", who, L.n_tv);
+        if (L.n_out < 1 || L.n_out > 32 || (L.n_out & (L.n_out - 1)) || (L.n_out > 1 && L.n_out > N / 4))
+            return c->set_err(TFHE_ERR_INVALID_ARG, "%s: n_out = %d (a power of two <= 32, and 1 or <= N/4 = %d)", who, L.n_out, N / 4);
+        if (L.tv_index)
+            for (int64_t g = 0; g < B; g++)
+                if (L.tv_index[g] < 0 || L.tv_index[g] >= L.n_tv)
+                    return c->set_err(TFHE_ERR_INVALID_ARG, "%s: tv_index[%lld] = %d is outside [0, %d)", who, (long long)g, L.tv_index[g], L.n_tv);
+    }
+    if (L.term_start[0] != 0) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: term_start[0] = %d (must be 0)", who, L.term_start[0]);
+    for (int64_t g = 0; g < B; g++)
+        if (L.term_start[g + 1] < L.term_start[g]) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: term_start decreases at row %lld", who, (long long)g);
+    const int64_t T = L.term_start[B];
+    if (T > 0 && (!L.term_wire || !L.term_coef)) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: %lld terms and a NULL term array", who, (long long)T);
+    auto bad = [&](int64_t v) { return v < 0 || v >= num_wires; };
+    for (int64_t t = 0; t < T; t++)
+        if (bad(L.term_wire[t])) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: term %lld reads wire %d, outside the table of %lld wires", who, (long long)t, L.term_wire[t], (long long)num_wires);
+    const int64_t G = B * (lut ? L.n_out : 1);
+    alloc_checkpoint();
+    std::unordered_set<int32_t> written;
+    written.reserve((size_t)G * 2);
+    for (int64_t g = 0; g < G; g++) {
+        if (bad(L.out[g])) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: output %lld is wire %d, outside the table of %lld wires", who, (long long)g, L.out[g], (long long)num_wires);
+        if (!written.insert(L.out[g]).second) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: wire %d written twice in one level", who, L.out[g]);
+    }
+    for (int64_t t = 0; t < T; t++)
+        if (written.count(L.term_wire[t])) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: term %lld reads wire %d, which the same level writes", who, (long long)t, L.term_wire[t]);
+    return TFHE_OK;
+}
+
+// One integer level on a multi-device context, as multi_gates_level: fewer than level_split_min rows (every LUT row is one blind
+// rotation) run on the first device; a wider level is cut into contiguous equal shards, one per device.  Every shard's device first
+// fetches the term rows it lacks (all transfers queued before any shard), then runs its rows; the outputs become its own.
+static int32_t multi_int_level(tfhe_ctx *c, const IntLevel &L)
+{
+    const int nk = (int)c->kids.size();
+    const int64_t B = L.B, per_row = L.tv ? L.n_out : 1;
+    const bool split = !(nk == 1 || c->level_split_min < 0 || B < c->level_split_min);
+    alloc_checkpoint();
+    std::vector<int64_t> bounds((size_t)nk + 1, B);
+    for (int r = 0; r <= nk; r++) bounds[(size_t)r] = split ? B * r / nk : (r == 0 ? 0 : B);
+    std::fill(c->kid_ran.begin(), c->kid_ran.end(), 0);
+    for (int r = 0; r < nk; r++) {
+        const int64_t s0 = bounds[(size_t)r], s1 = bounds[(size_t)r + 1];
+        if (s1 <= s0) continue;
+        const int32_t rc = pull_wires(c, r, L.term_wire + L.term_start[s0], (int64_t)L.term_start[s1] - L.term_start[s0]);
+        if (rc) return rc;
+    }
+    std::vector<int32_t> starts;
+    for (int r = 0; r < nk; r++) {
+        const int64_t s0 = bounds[(size_t)r], cnt = bounds[(size_t)r + 1] - s0;
+        if (cnt <= 0) continue;
+        const int32_t base = L.term_start[s0];
+        starts.resize((size_t)cnt + 1);
+        for (int64_t g = 0; g <= cnt; g++) starts[(size_t)g] = L.term_start[s0 + g] - base;
+        const int32_t *out = L.out + s0 * per_row;
+        tfhe_ctx *k = c->kids[(size_t)r];
+        const int32_t rc = L.tv ? tfhe_lut_level(k, L.tv, L.n_tv, L.tv_index ? L.tv_index + s0 : nullptr, L.n_out, starts.data(), L.term_wire + base,
+                                                 L.term_coef + base, L.cst ? L.cst + s0 : nullptr, out, cnt)
+                                : tfhe_linear_level(k, starts.data(), L.term_wire + base, L.term_coef + base, L.cst ? L.cst + s0 : nullptr, out, cnt);
+        c->kid_ran[(size_t)r] = 1;
+        for (int64_t g = 0; g < cnt * per_row; g++) {
+            const size_t w = (size_t)out[g];
+            for (int q = 0; q < nk; q++) c->wire_valid[(size_t)q][w] = (q == r);
+            c->wire_owner[w] = r;
+        }
+        if (rc) return c->set_err(rc, "device %d (kid %d): %s", k->device, r, k->err.c_str());
+    }
+    return TFHE_OK;
+}
+
+static int32_t int_level(tfhe_ctx *c, const char *who, const IntLevel &L)
+{
+    const bool lut = L.tv != nullptr;
+    if (L.B < 0 || (L.B > 0 && (!L.term_start || !L.out))) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL argument or negative B", who);
+    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key", who);
+    if (c->multi() ? c->num_wires <= 0 : !c->d_wires) return c->set_err(TFHE_ERR_STATE, "%s: no wire table allocated", who);
+    if (!c->multi() && c->wires_parties) return c->set_err(TFHE_ERR_STATE, "%s: the wire table has multi-key rows (tfhe_mk_wires_alloc)", who);
+    const tfhe_ctx *dev0 = c->multi() ? c->kids[0] : c;        // (options and keys are the same on every device of a context)
+    if (lut && dev0->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the TV kernels have no DIAG instantiation)", who);
+    if (L.B == 0) return TFHE_OK;
+    { const int32_t rcv = validate_int_level(c, who, c->num_wires, c->P.N, L); if (rcv) return rcv; }
+    if (lut && (!dev0->have_bk || !dev0->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: bootstrapping/keyswitch key not loaded", who);
+    if (c->multi()) return multi_int_level(c, L);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_int_level(c, L);
+}
+
+int32_t tfhe_lut_level(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out, const int32_t *term_start,
+                       const int32_t *term_wire, const int32_t *term_coef, const int32_t *cst, const int32_t *out, int64_t B) try
+{
+    ENTER_CTX(c);
+    if (B > 0 && !tv) return c->set_err(TFHE_ERR_INVALID_ARG, "lut_level: NULL test polynomials");
+    static const int32_t kNoTable = 0;      // (B == 0 with tv NULL: nothing to run, but the call is still the LUT form)
+    return int_level(c, "lut_level", IntLevel{tv ? tv : &kNoTable, n_tv, tv_index, n_out, term_start, term_wire, term_coef, cst, out, B});
+}
+ABI_CATCH(c, "tfhe_lut_level")
+
+int32_t tfhe_linear_level(tfhe_ctx *c, const int32_t *term_start, const int32_t *term_wire, const int32_t *term_coef, const int32_t *cst,
+                          const int32_t *out, int64_t B) try
+{
+    ENTER_CTX(c);
+    return int_level(c, "linear_level", IntLevel{nullptr, 0, nullptr, 1, term_start, term_wire, term_coef, cst, out, B});
+}
+ABI_CATCH(c, "tfhe_linear_level")

@@ -197,6 +197,22 @@ int32_t launch_prologue(tfhe_ctx *c, size_t R, const int32_t *d_in0, const int32
     return TFHE_OK;
 }
 
+// integer linear prologue of B rows of a tfhe_lut_level (lut: the modulus-switched combinations into bara) or tfhe_linear_level (the
+// combinations themselves into their output rows of the wire table); device index arrays (kernels_gates.hpp: linear_prologue_kernel)
+int32_t launch_linear_prologue(tfhe_ctx *c, bool lut, size_t B, const int32_t *d_start, const int32_t *d_wire, const int32_t *d_coef,
+                               const int32_t *d_cst, const int32_t *d_out, hipStream_t s)
+{
+    const int n = c->P.n, log2_2N = ilog2i(2 * c->P.N);
+    if (lut)
+        hipLaunchKernelGGL(linear_prologue_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, (const int32_t *)c->d_wires, d_start, d_wire, d_coef,
+                           d_cst, d_out, (int32_t *)c->bara.p, n, log2_2N);
+    else
+        hipLaunchKernelGGL(linear_prologue_kernel<false>, dim3((unsigned)B), dim3(256), 0, s, (const int32_t *)c->d_wires, d_start, d_wire, d_coef,
+                           d_cst, d_out, c->d_wires, n, log2_2N);
+    HIP_TRY(c, hipGetLastError());
+    return TFHE_OK;
+}
+
 // NOT / COPY / CONST0 / CONST1 of T gates (multi-key: `words` = P n mask words per sample; run_gates launches the kernel itself)
 int32_t launch_trivial(tfhe_ctx *c, size_t T, const int32_t *d_in0, const int32_t *d_ts, const int32_t *d_td, const uint8_t *d_top, int32_t *d_out,
                        int words, hipStream_t s)
@@ -495,13 +511,54 @@ int32_t tfhe_gates_batch_wait(tfhe_ctx *c, int32_t ticket) try
 }
 ABI_CATCH(c, "tfhe_gates_batch_wait")
 
+// The device half of every bootstrap: the R rows modulus-switched in bara are blind-rotated (with mu, or row g's table tv->tv[tv->index[g]]),
+// n_out samples are extracted per row — with n_out > 1 the TV kernels also write each rotation's body coefficients j N / n_out (bodies),
+// and extract_shift_kernel turns row g into the n_out samples extracted at those coefficients, rows g n_out + j — and, with e0 non-NULL,
+// the R n_out samples are keyswitched through launch_keyswitch's maps (e0, dst) into out.  *samples receives the extracted samples,
+// [R n_out][k N + 1] (what a call without keyswitch hands back).  Timing events 1 - 3 if `events`: rotation, then shift + keyswitch.
+// Callers: bootstrap_rows (host buffers: identity maps into io[3]) and run_lut_level (the wire table: dst = the level's output wires).
+static int32_t rotate_rows(tfhe_ctx *c, size_t R, int32_t mu, const TvPtrs *tv, int32_t n_out, const int32_t *e0, const int32_t *dst,
+                           int32_t *out, const int32_t **samples, bool events, hipStream_t s)
+{
+    const int kNn = c->P.k * c->P.N;
+    const size_t G = R * (size_t)n_out;                                          // output samples
+    const bool multi_out = n_out > 1;
+    HIP_TRY(c, c->ext.reserve(R * (kNn + 1) * 4));
+    TvPtrs tvd{nullptr, nullptr};
+    if (tv) {
+        tvd = TvPtrs{tv->tv, tv->index};
+        if (multi_out) {
+            HIP_TRY(c, c->tv_bodies.reserve(G * 4));
+            HIP_TRY(c, c->tv_ext.reserve(G * (kNn + 1) * 4));
+            tvd.bodies = (int32_t *)c->tv_bodies.p;
+            tvd.n_out = n_out;
+        }
+    }
+    *samples = multi_out ? (const int32_t *)c->tv_ext.p : (const int32_t *)c->ext.p;
+    if (events) HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    int32_t rc = launch_blind_rotate(c, R, mu, s, tv ? &tvd : nullptr);
+    if (rc) return rc;
+    if (events) HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    if (multi_out) {
+        const size_t total = G * (kNn + 1), groups = (total + 3) / 4;
+        hipLaunchKernelGGL(extract_shift_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const int32_t *)c->ext.p,
+                           (const int32_t *)c->tv_bodies.p, (int32_t *)c->tv_ext.p, total, kNn + 1, ilog2i(c->P.N), ilog2i(n_out));
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (e0) {
+        rc = launch_keyswitch(c, G, e0, nullptr, dst, *samples, out, s);
+        if (rc) return rc;
+    }
+    if (events) HIP_TRY(c, hipEventRecord(c->ev[3], s));
+    return TFHE_OK;
+}
+
 // The host-table form of a TV batch: tables [n_tv][N], index [B] (checked by the caller) or NULL = table 0 for every row.
 struct TvHost { const int32_t *tv; int32_t n_tv; const int32_t *index; };
 
 // tfhe_bootstrap_batch (tv == NULL), tfhe_bootstrap_tv_batch (n_out = 1) and tfhe_bootstrap_tv_multi_batch on a device context or,
-// row-split, on the kids of a multi-device one.  With n_out > 1 the TV kernels also write each rotation's body coefficients
-// j N / n_out (bodies), extract_shift_kernel turns row g into the n_out samples extracted at those coefficients, and the keyswitch
-// (if any) runs on the B n_out rows: out is [B][n_out][width].  The shift belongs to the keyswitch phase of the timing events.
+// row-split, on the kids of a multi-device one: upload, modulus switch, rotate_rows with identity maps, download.  out is
+// [B][n_out][width].  The shift belongs to the keyswitch phase of the timing events.
 static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const TvHost *tv, int32_t n_out, const int32_t *in, int32_t *out, int64_t B,
                               int32_t with_keyswitch)
 {
@@ -522,11 +579,9 @@ static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const Tv
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }
     const int n = c->P.n, kNn = c->P.k * c->P.N;
     const size_t in_bytes = (size_t)B * (n + 1) * 4, G = (size_t)B * n_out;      // G: output samples
-    const bool multi_out = n_out > 1;
     HIP_TRY(c, c->io[0].reserve(in_bytes));
     HIP_TRY(c, hipMemcpyAsync(c->io[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(c, c->bara.reserve((size_t)B * (n + 1) * 4));
-    HIP_TRY(c, c->ext.reserve((size_t)B * (kNn + 1) * 4));
     TvPtrs tvd{nullptr, nullptr};
     if (tv) {
         const size_t tv_bytes = (size_t)tv->n_tv * c->P.N * 4, idx_bytes = (size_t)B * 4;
@@ -536,53 +591,95 @@ static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const Tv
         if (tv->index) HIP_TRY(c, hipMemcpyAsync(c->tv_index.p, tv->index, idx_bytes, hipMemcpyHostToDevice, s));
         else HIP_TRY(c, hipMemsetAsync(c->tv_index.p, 0, idx_bytes, s));
         tvd = TvPtrs{(const int32_t *)c->tv.p, (const int32_t *)c->tv_index.p};
-        if (multi_out) {
-            HIP_TRY(c, c->tv_bodies.reserve(G * 4));
-            HIP_TRY(c, c->tv_ext.reserve(G * (kNn + 1) * 4));
-            tvd.bodies = (int32_t *)c->tv_bodies.p;
-            tvd.n_out = n_out;
-        }
     }
-    // the extracted samples the keyswitch reads or the caller receives: [G][kN + 1]
-    const int32_t *samples = multi_out ? (const int32_t *)c->tv_ext.p : (const int32_t *)c->ext.p;
-    next_timing_slot(c);
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    hipLaunchKernelGGL(modswitch_kernel, dim3((unsigned)B), dim3(256), 0, s, (const int32_t *)c->io[0].p, (int32_t *)c->bara.p, n,
-                       ilog2i(2 * c->P.N));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    int32_t rc = launch_blind_rotate(c, (size_t)B, mu, s, tv ? &tvd : nullptr);
-    if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    if (multi_out) {
-        const size_t total = G * (kNn + 1), groups = (total + 3) / 4;
-        hipLaunchKernelGGL(extract_shift_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const int32_t *)c->ext.p,
-                           (const int32_t *)c->tv_bodies.p, (int32_t *)c->tv_ext.p, total, kNn + 1, ilog2i(c->P.N), ilog2i(n_out));
-        HIP_TRY(c, hipGetLastError());
-    }
+    const size_t out_bytes = G * (n + 1) * 4;
+    const int32_t *d_e0 = nullptr;
     if (with_keyswitch) {
         // identity maps: e0[g] = g
-        const size_t out_bytes = G * (n + 1) * 4;
-        rc = ensure_host_map(c, G * 4);
+        int32_t rc = ensure_host_map(c, G * 4);
         if (rc) return rc;
         for (size_t g = 0; g < G; g++) ((int32_t *)c->h_map)[g] = (int32_t)g;
         HIP_TRY(c, c->map.reserve(G * 4));
         HIP_TRY(c, hipMemcpyAsync(c->map.p, c->h_map, G * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(c, c->io[3].reserve(out_bytes));
-        rc = launch_keyswitch(c, G, (const int32_t *)c->map.p, nullptr, nullptr, samples, (int32_t *)c->io[3].p, s);
-        if (rc) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev[3], s));
-        HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, out_bytes, hipMemcpyDeviceToHost, s));
-    } else {
-        HIP_TRY(c, hipEventRecord(c->ev[3], s));
-        HIP_TRY(c, hipMemcpyAsync(out, samples, G * (kNn + 1) * 4, hipMemcpyDeviceToHost, s));
+        d_e0 = (const int32_t *)c->map.p;
     }
+    next_timing_slot(c);
+    HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    hipLaunchKernelGGL(modswitch_kernel, dim3((unsigned)B), dim3(256), 0, s, (const int32_t *)c->io[0].p, (int32_t *)c->bara.p, n,
+                       ilog2i(2 * c->P.N));
+    HIP_TRY(c, hipGetLastError());
+    const int32_t *samples = nullptr;
+    int32_t rc = rotate_rows(c, (size_t)B, mu, tv ? &tvd : nullptr, n_out, d_e0, nullptr, (int32_t *)c->io[3].p, &samples, true, s);
+    if (rc) return rc;
+    if (with_keyswitch) HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, out_bytes, hipMemcpyDeviceToHost, s));
+    else HIP_TRY(c, hipMemcpyAsync(out, samples, G * (kNn + 1) * 4, hipMemcpyDeviceToHost, s));
     rc = leave_stream(c, s);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     commit_timing_slot(c);
     c->last_rotations = B;
     return TFHE_OK;
+}
+
+// One validated level of tfhe_lut_level (L.tv != NULL) or tfhe_linear_level on a device context's wire table, queued on its stream.
+// Every host array goes into one block of the pinned staging ring and up in ONE copy (the caller may reuse its arrays at once):
+//   tv [n_tv][N] | tv_index [B] | e0 [G] | term_start [B + 1] | term_wire [T] | term_coef [T] | cst [B] | out [G]
+// (G = B n_out output samples; e0 the identity map of the keyswitch; each part starts on a 256-byte boundary, the tables first).
+// The LUT form is linear_prologue_kernel<true> into bara, then rotate_rows with the staged tables, keyswitched straight into the
+// output rows (dst = out); timing events as bootstrap_rows: prologue, rotation, shift + keyswitch.
+int32_t run_int_level(tfhe_ctx *c, const IntLevel &L)
+{
+    const bool lut = L.tv != nullptr;
+    const int32_t n_out = lut ? L.n_out : 1;
+    const size_t B = (size_t)L.B, G = B * (size_t)n_out, T = (size_t)L.term_start[B], N = (size_t)c->P.N;
+    auto up = [](size_t words) { return (words + 63) / 64 * 64; };
+    const size_t o_idx = lut ? up((size_t)L.n_tv * N) : 0, o_e0 = o_idx + (lut ? up(B) : 0), o_start = o_e0 + (lut ? up(G) : 0);
+    const size_t o_wire = o_start + up(B + 1), o_coef = o_wire + up(T), o_cst = o_coef + up(T), o_out = o_cst + (L.cst ? up(B) : 0);
+    const size_t map_bytes = (o_out + G) * 4;
+    hipStream_t s = c->stream;
+    { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }
+    int32_t rc = ensure_host_map(c, map_bytes);
+    if (rc) return rc;
+    int32_t *h = (int32_t *)c->h_map;
+    if (lut) {
+        memcpy(h, L.tv, (size_t)L.n_tv * N * 4);
+        if (L.tv_index) memcpy(h + o_idx, L.tv_index, B * 4);
+        else memset(h + o_idx, 0, B * 4);
+        for (size_t g = 0; g < G; g++) h[o_e0 + g] = (int32_t)g;
+    }
+    memcpy(h + o_start, L.term_start, (B + 1) * 4);
+    if (T) {
+        memcpy(h + o_wire, L.term_wire, T * 4);
+        memcpy(h + o_coef, L.term_coef, T * 4);
+    }
+    if (L.cst) memcpy(h + o_cst, L.cst, B * 4);
+    memcpy(h + o_out, L.out, G * 4);
+    HIP_TRY(c, c->map.reserve(map_bytes));
+    HIP_TRY(c, hipMemcpyAsync(c->map.p, c->h_map, map_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipEventRecord(c->map_ev, s));
+    c->map_cur->pending = true;
+    const int32_t *d = (const int32_t *)c->map.p;
+    const int32_t *d_cst = L.cst ? d + o_cst : nullptr;
+    next_timing_slot(c);
+    if (!lut) {
+        rc = launch_linear_prologue(c, false, B, d + o_start, d + o_wire, d + o_coef, d_cst, d + o_out, s);
+        if (rc) return rc;
+        c->last_rotations = 0;
+        return leave_stream(c, s);
+    }
+    const bool events = c->timing_events != 0;
+    HIP_TRY(c, c->bara.reserve(B * (size_t)(c->P.n + 1) * 4));
+    if (events) HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    rc = launch_linear_prologue(c, true, B, d + o_start, d + o_wire, d + o_coef, d_cst, nullptr, s);
+    if (rc) return rc;
+    const TvPtrs tvd{d, d + o_idx};
+    const int32_t *samples = nullptr;
+    rc = rotate_rows(c, B, 0, &tvd, n_out, d + o_e0, d + o_out, c->d_wires, &samples, events, s);
+    if (rc) return rc;
+    if (events) commit_timing_slot(c);
+    c->last_rotations = (int64_t)B;
+    return leave_stream(c, s);
 }
 
 int32_t tfhe_bootstrap_batch(tfhe_ctx *c, int32_t mu, const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch) try

@@ -78,6 +78,31 @@ __global__ void modswitch_kernel(const int32_t *__restrict__ in, int32_t *__rest
     }
 }
 
+// Integer linear combination of wire-table rows (tfhe_lut_level / tfhe_linear_level): row g is
+//   x_g = sum over t in [term_start[g], term_start[g+1]) of term_coef[t] * wires[term_wire[t]], plus cst[g] on the body (cst NULL: 0)
+// in uint32_t wrap-around, exactly LweSampleArray's +, integer scale and add_constant.  kLut: decode_message(x_g, 2N) into
+// dst[g] (the modulus switch of modswitch_kernel, the rotation's input in bara); otherwise x_g itself into dst[out[g]] (the wire
+// table: no row of a level reads a row it writes, tfhe_lut_level's validation).  One workgroup per row, consecutive threads on
+// consecutive words of each term row; the term list is uniform over the workgroup.
+template <bool kLut>
+__global__ __launch_bounds__(256) void linear_prologue_kernel(const int32_t *wires, const int32_t *__restrict__ term_start,
+                                                              const int32_t *__restrict__ term_wire, const int32_t *__restrict__ term_coef,
+                                                              const int32_t *__restrict__ cst, const int32_t *__restrict__ out, int32_t *dst,
+                                                              int n, int log2_2N)
+{
+    const size_t g = blockIdx.x;
+    const int t0 = term_start[g], t1 = term_start[g + 1];
+    const size_t n1 = (size_t)n + 1;
+    int32_t *row = dst + (kLut ? g : (size_t)out[g]) * n1;
+    for (int i = threadIdx.x; i <= n; i += blockDim.x) {
+        uint32_t v = 0;
+        for (int t = t0; t < t1; t++) v += (uint32_t)term_coef[t] * (uint32_t)wires[(size_t)term_wire[t] * n1 + i];
+        if (i == n && cst) v += (uint32_t)cst[g];
+        if (kLut) row[i] = (int32_t)(v + (1u << (32 - log2_2N - 1))) >> (32 - log2_2N);      // numeric-functions.jl:31-34
+        else row[i] = (int32_t)v;
+    }
+}
+
 // gate_not / gate_constant / copy (gates.jl:76-93)
 __global__ void trivial_gates_kernel(const int32_t *in0, const int32_t *__restrict__ src_rows,
                                      const int32_t *__restrict__ dst_rows, const uint8_t *__restrict__ ops,

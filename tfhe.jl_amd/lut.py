@@ -14,6 +14,15 @@ then be encrypted as a message of Z_{pK} (lut_encrypt(rng, sk, m, p * K), or any
 lut_encode(m, p * K)): phi lies in window m of Z_{pK}, phi + j N / K in window j p + m, below N, so no negacyclic sign enters.
 make_multi_test_vector([f_0, ..., f_{K-1}], p, N, q) is the table of g(j p + m) = f_j(m); output j encrypts f_j(m) in Z_q.
 The price is log2 K bits of message space: the input's noise must stay within a window K times narrower, and p K <= N / 2.
+
+On the device-resident wire table (Circuit.lut / lut_multi / linear, Engine.lut_level, tfhe_lut_level) LUTs and gates mix in one
+circuit through two conversions:
+  - a gate-encoded bit (+-1/8, gates.jl) is the message lut_encode(b, 2) = (2b + 1)/8 of Z_2 once GATE_BIT_TO_Z2 = +1/4 is added:
+    c.lut(f, [bit_wire], 2, q, const=GATE_BIT_TO_Z2) (or as one term among others of a sum in Z_2);
+  - a LUT whose table holds the raw values +-1/8 returns a gate-encoded bit: make_gate_test_vector(pred, p, N) (pred(m) true: +1/8),
+    passed to Circuit.lut as a raw table; its output is an operand of any gate.
+The coefficients of a combination are the caller's choice, as with LweSampleArray arithmetic: a term of coefficient c multiplies its
+sample's noise by |c|, and nothing checks that the sum still decodes.
 """
 import numpy as np
 
@@ -26,6 +35,19 @@ def _log2(p, what="p"):
     if p < 2 or p & (p - 1):
         raise ValueError(f"{what} = {p}: a power of two >= 2")
     return p.bit_length() - 1
+
+
+GATE_BIT_TO_Z2 = 1 << 30      # +1/4: a gate-encoded bit (+-1/8) plus this is lut_encode(b, 2)
+
+
+def make_gate_test_vector(pred, p, N):
+    """The test polynomial of m -> gate-encoded bit pred(m), Z_p -> {+-1/8}: v[j] = +2^29 where pred(floor(j p / N)) else -2^29,
+    int32 [N] (the encoding of gate_* outputs, so the result feeds any gate).  2 <= p <= N / 2, a power of two."""
+    _log2(p)
+    if p > N // 2:
+        raise ValueError(f"p = {p} > N/2 = {N // 2}")
+    vals = np.array([1 if pred(m) else -1 for m in range(p)], np.int64) << 29
+    return vals[(np.arange(N) * p) // N].astype(np.int32)
 
 
 def lut_encode(m, p):
