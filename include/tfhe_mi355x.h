@@ -376,6 +376,27 @@ int32_t tfhe_mk_wires_alloc(tfhe_ctx *ctx, int64_t num_wires);
 int32_t tfhe_mk_gates_level(tfhe_ctx *ctx, const uint8_t *opcodes, const int32_t *a, const int32_t *b,
                             const int32_t *c, const int32_t *out, int64_t B);
 
+/* Multi-key programmable bootstrapping (additions within ABI v7): tfhe_bootstrap_tv_batch / tfhe_bootstrap_tv_multi_batch on
+ * multi-key samples.  The multi-key blind rotation (mk_internals.jl:464-495) starts its body polynomial from X^{-barb} tv[tv_index[g]]
+ * instead of X^{-barb} (mu, ..., mu) (the masks from zero); sample j of row g is mk_tlwe_extract_sample (mk_internals.jl:88-95) at
+ * coefficient j N / n_out, then mk_keyswitch (mk_internals.jl:397-411) if with_keyswitch.  in: host int32 [B][P*n+1]; out: host
+ * int32 [B][n_out][P*n+1], or [B][n_out][P*N+1] without keyswitch.  Tables, tv_index, n_out and TFHE_ERR_INVALID_ARG as the
+ * single-key pair (checked before anything is uploaded).  TFHE_ERR_STATE: a single-key context, measure_margin on, or (with
+ * keyswitch) keys loaded for different party counts; TFHE_ERR_NO_KEY: multi-key keys not loaded.  A multi-device context splits
+ * the rows; every device receives all tables.  The single-key entry points keep refusing multi-key contexts. */
+int32_t tfhe_mk_bootstrap_tv_batch(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const int32_t *tv_index,
+                                   const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch);
+int32_t tfhe_mk_bootstrap_tv_multi_batch(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out,
+                                         const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch);
+/* tfhe_lut_level / tfhe_linear_level on the multi-key wire table (rows [P*n+1]; the multi-key rotation and keyswitch): same index
+ * arrays, checks, staging and asynchrony.  TFHE_ERR_STATE on a single-key context or table, measure_margin on (LUT form), or (LUT
+ * form) when the keys now loaded are for a party count other than the table's; TFHE_ERR_NO_KEY (LUT form): multi-key keys missing. */
+int32_t tfhe_mk_lut_level(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out,
+                          const int32_t *term_start, const int32_t *term_wire, const int32_t *term_coef, const int32_t *cst,
+                          const int32_t *out, int64_t B);
+int32_t tfhe_mk_linear_level(tfhe_ctx *ctx, const int32_t *term_start, const int32_t *term_wire, const int32_t *term_coef,
+                             const int32_t *cst, const int32_t *out, int64_t B);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Timing of the most recent batch call on ctx, from HIP events recorded on the stream the kernels

@@ -681,4 +681,41 @@ mk_gate_nand(mck::GpuMKCloudKey, xs::MKVec, ys::MKVec) = mk_nand_batch(mck, xs, 
 broadcasted(::typeof(mk_gate_nand), mck::GpuMKCloudKey, xs::MKVec, ys::MKVec) = mk_nand_batch(mck, xs, ys)
 broadcasted(::typeof(mk_gate_nand), mck::Base.RefValue{GpuMKCloudKey}, xs::MKVec, ys::MKVec) = mk_nand_batch(mck[], xs, ys)
 
+"""
+    mk_bootstrap_tv(mck, tables, xs, index=nothing; with_keyswitch=true)  ->  Vector{MKLweSample}
+
+Multi-key programmable bootstrapping (tfhe_mk_bootstrap_tv_batch): `bootstrap_tv` on multi-key samples.  The multi-key blind rotation
+(src/mk_internals.jl:464-495) starts its body from `X^{-barb} v`, `v = tables[:, index[g]]` (Int32 N x n_tv; `index` 1-based or
+`nothing` for the first table), instead of `X^{-barb} repeat([mu], N)`; mk_tlwe_extract_sample (:88-95), then mk_keyswitch (:397-411)
+unless `with_keyswitch = false` (then samples of N words per party under the extracted keys).
+"""
+mk_bootstrap_tv(mck::GpuMKCloudKey, tables::AbstractMatrix{Int32}, xs::MKVec, index=nothing; with_keyswitch::Bool=true) =
+    mk_bootstrap_tv_multi(mck, tables, xs, 1, index; with_keyswitch=with_keyswitch)[1]
+
+"""
+    mk_bootstrap_tv_multi(mck, tables, xs, n_out, index=nothing; with_keyswitch=true)  ->  Vector{Vector{MKLweSample}}
+
+Multi-key multi-output programmable bootstrapping (tfhe_mk_bootstrap_tv_multi_batch): `mk_bootstrap_tv` returning `n_out` results per
+sample from one blind rotation, result `j` (1-based) extracted at the accumulator's coefficient `(j - 1) N / n_out`, as
+`bootstrap_tv_multi`.  Returns `n_out` vectors of `length(xs)` samples.
+"""
+function mk_bootstrap_tv_multi(mck::GpuMKCloudKey, tables::AbstractMatrix{Int32}, xs::MKVec, n_out::Integer, index=nothing;
+                               with_keyswitch::Bool=true)
+    B = length(xs)
+    B == 0 && return [MKLweSample[] for _ in 1:max(n_out, 0)]
+    N, P = mck.params.tlwe_polynomial_degree, mck.parties
+    size(tables, 1) == N || error("tfhe_mi355x: test polynomials must have N = ", N, " rows")
+    1 <= n_out <= 32 || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32)")
+    tv = Matrix{Int32}(tables)
+    idx = index === nothing ? nothing : Int32.(collect(index) .- 1)
+    fx = flatten(xs)
+    width = with_keyswitch ? mck.params.lwe_size : N               # words per party of a result
+    out = Array{Int32}(undef, width * P + 1, n_out, B)
+    GC.@preserve tv idx fx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_bootstrap_tv_multi_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Int32),
+        mck.ctx, tv, Int32(size(tv, 2)), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), Int32(n_out), fx, out, B, Int32(with_keyswitch)))
+    params = LweParams(width)
+    [[MKLweSample(params, reshape(out[1:width*P, j, g], width, P), out[width * P + 1, j, g], 0.) for g in 1:B] for j in 1:n_out]
+end
+
 end # module

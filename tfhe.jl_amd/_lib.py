@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "tfhe_timing_history_ms", "tfhe_gates_batch_submit", "tfhe_gates_batch_wait", "tfhe_last_device_count",
     "tfhe_get_option", "tfhe_ctx_synchronize", "tfhe_mk_gates_batch", "tfhe_mk_wires_alloc", "tfhe_mk_gates_level",
     "tfhe_bootstrap_tv_batch", "tfhe_bootstrap_tv_multi_batch", "tfhe_lut_level", "tfhe_linear_level",
+    "tfhe_mk_bootstrap_tv_batch", "tfhe_mk_bootstrap_tv_multi_batch", "tfhe_mk_lut_level", "tfhe_mk_linear_level",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -139,6 +140,11 @@ def load():
     if hasattr(lib, "tfhe_lut_level"):
         lib.tfhe_lut_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64]
         lib.tfhe_linear_level.argtypes = [vp, vp, vp, vp, vp, vp, i64]
+    if hasattr(lib, "tfhe_mk_bootstrap_tv_batch"):
+        lib.tfhe_mk_bootstrap_tv_batch.argtypes = [vp, vp, i32, vp, vp, vp, i64, i32]
+        lib.tfhe_mk_bootstrap_tv_multi_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, i64, i32]
+        lib.tfhe_mk_lut_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64]
+        lib.tfhe_mk_linear_level.argtypes = [vp, vp, vp, vp, vp, vp, i64]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -333,10 +339,11 @@ class Engine:
         self._check(self._lib.tfhe_bootstrap_batch(self._h, int(mu), _ptr(x), _ptr(out), B, 1 if with_keyswitch else 0))
         return out
 
-    def _tv_args(self, what, tables, x, index):
+    def _tv_args(self, what, tables, x, index, words=None):
         x = _i32c(x)
-        if x.ndim != 2 or x.shape[1] != self.n + 1:
-            raise ValueError(f"{what} input must be [B][{self.n + 1}], got {x.shape}")
+        words = self.n + 1 if words is None else words
+        if x.ndim != 2 or x.shape[1] != words:
+            raise ValueError(f"{what} input must be [B][{words}], got {x.shape}")
         tables = _i32c(np.atleast_2d(tables))
         if tables.ndim != 2 or tables.shape[1] != self.N:
             raise ValueError(f"test polynomials must be [n_tv][{self.N}], got {tables.shape}")
@@ -371,6 +378,30 @@ class Engine:
         out = np.empty((B, n_out if 1 <= n_out <= 32 else 0, width), np.int32)      # (an n_out the library refuses: nothing written)
         self._check(self._lib.tfhe_bootstrap_tv_multi_batch(self._h, _ptr(tables), tables.shape[0], _ptr(idx) if idx is not None else None,
                                                             n_out, _ptr(x), _ptr(out), B, 1 if with_keyswitch else 0))
+        return out
+
+    def _mk_width(self, what):
+        P = getattr(self, "_mk_parties", None)
+        if P is None:
+            raise EngineError(3, f"{what}: multi-key keys not loaded")
+        return P
+
+    def mk_bootstrap_tv(self, tables, x, index=None, with_keyswitch=True):
+        """Multi-key programmable bootstrapping (tfhe_mk_bootstrap_tv_batch): `bootstrap_tv` on multi-key samples int32 [B][P*n+1];
+        the result is [B][P*n+1], or [B][P*N+1] without keyswitch."""
+        return self.mk_bootstrap_tv_multi(tables, x, 1, index, with_keyswitch)[:, 0]
+
+    def mk_bootstrap_tv_multi(self, tables, x, n_out, index=None, with_keyswitch=True):
+        """Multi-key multi-output programmable bootstrapping (tfhe_mk_bootstrap_tv_multi_batch): `bootstrap_tv_multi` on multi-key
+        samples, int32 [B][n_out][P*n+1] (or [B][n_out][P*N+1] without keyswitch)."""
+        P = self._mk_width("mk_bootstrap_tv")
+        tables, x, idx = self._tv_args("mk_bootstrap_tv", tables, x, index, P * self.n + 1)
+        B, n_out = x.shape[0], int(n_out)
+        width = P * self.n + 1 if with_keyswitch else P * self.N + 1
+        out = np.empty((B, n_out if 1 <= n_out <= 32 else 0, width), np.int32)      # (an n_out the library refuses: nothing written)
+        fn = self._lib.tfhe_mk_bootstrap_tv_multi_batch
+        self._check(fn(self._h, _ptr(tables), tables.shape[0], _ptr(idx) if idx is not None else None, n_out, _ptr(x), _ptr(out), B,
+                       1 if with_keyswitch else 0))
         return out
 
     def keyswitch(self, x):
@@ -442,6 +473,9 @@ class Engine:
         """Programmable bootstrapping on the wire table (tfhe_lut_level): row g's sample is sum_t term_coef[t] wire[term_wire[t]] over
         t in [term_start[g], term_start[g+1]), plus cst[g] on the body (mod 2^32; cst None: 0); its n_out results (bootstrap_tv_multi:
         tables[index[g]], index None: table 0) go to wires out[g n_out + j].  Asynchronous; the arrays may be reused at once."""
+        self._lut_level(self._lib.tfhe_lut_level, tables, term_start, term_wire, term_coef, cst, out, index, n_out)
+
+    def _lut_level(self, fn, tables, term_start, term_wire, term_coef, cst, out, index, n_out):
         tables = _i32c(np.atleast_2d(tables))
         if tables.ndim != 2 or tables.shape[1] != self.N:
             raise ValueError(f"test polynomials must be [n_tv][{self.N}], got {tables.shape}")
@@ -452,13 +486,23 @@ class Engine:
             idx = _i32c(index).reshape(-1)
             if idx.size != B:
                 raise ValueError(f"index must have one entry per row ({B}), got {idx.size}")
-        self._check(self._lib.tfhe_lut_level(self._h, _ptr(tables), tables.shape[0], _ptr(idx), n_out, _ptr(start), _ptr(wire), _ptr(coef),
-                                             _ptr(c), _ptr(o), B))
+        self._check(fn(self._h, _ptr(tables), tables.shape[0], _ptr(idx), n_out, _ptr(start), _ptr(wire), _ptr(coef), _ptr(c), _ptr(o), B))
 
     def linear_level(self, term_start, term_wire, term_coef, cst, out):
         """wire[out[g]] = the combination of lut_level's row g itself, no bootstrap (tfhe_linear_level): exact mod-2^32 arithmetic."""
+        self._linear_level(self._lib.tfhe_linear_level, term_start, term_wire, term_coef, cst, out)
+
+    def _linear_level(self, fn, term_start, term_wire, term_coef, cst, out):
         start, wire, coef, c, o, B = self._level_terms(term_start, term_wire, term_coef, cst, out, 1)
-        self._check(self._lib.tfhe_linear_level(self._h, _ptr(start), _ptr(wire), _ptr(coef), _ptr(c), _ptr(o), B))
+        self._check(fn(self._h, _ptr(start), _ptr(wire), _ptr(coef), _ptr(c), _ptr(o), B))
+
+    def mk_lut_level(self, tables, term_start, term_wire, term_coef, cst, out, index=None, n_out=1):
+        """`lut_level` on the multi-key wire table (tfhe_mk_lut_level, mk_wires_alloc): the multi-key rotation and keyswitch."""
+        self._lut_level(self._lib.tfhe_mk_lut_level, tables, term_start, term_wire, term_coef, cst, out, index, n_out)
+
+    def mk_linear_level(self, term_start, term_wire, term_coef, cst, out):
+        """`linear_level` on the multi-key wire table (tfhe_mk_linear_level)."""
+        self._linear_level(self._lib.tfhe_mk_linear_level, term_start, term_wire, term_coef, cst, out)
 
     # ---- multi-key ----
     def mk_load_bootstrap_key(self, bk_i32, parties):

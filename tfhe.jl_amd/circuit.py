@@ -248,20 +248,23 @@ class Circuit:
 
     def _run_plan(self, eng, plan, mk):
         level = eng.mk_gates_level if mk else eng.gates_level
+        lut_level = eng.mk_lut_level if mk else eng.lut_level
+        linear_level = eng.mk_linear_level if mk else eng.linear_level
         for lv in plan:
             if lv["gates"] is not None:
                 level(*lv["gates"])
             for K, tv, index, start, wire, coef, cst, out in lv["lut"]:
-                eng.lut_level(tv, start, wire, coef, cst, out, index=index, n_out=K)
+                lut_level(tv, start, wire, coef, cst, out, index=index, n_out=K)
             if lv["linear"] is not None:
-                eng.linear_level(*lv["linear"])
+                linear_level(*lv["linear"])
 
     # ---- execution ----------------------------------------------------------------------------------
     def run(self, ck, inputs, device=0):
         """inputs: LweSampleArray / list of LweSample / int32 [n_inputs][n+1].  Returns an LweSampleArray
         of the output wires.  Everything between upload and download runs on the GPU.
         Under an MKCloudKey: inputs int32 [n_inputs][P*n+1] (or a list of flat samples / MKLweSample), result int32
-        [n_outputs][P*n+1]; the levels run on a multi-key wire table (tfhe_mk_wires_alloc, tfhe_mk_gates_level)."""
+        [n_outputs][P*n+1]; the levels run on a multi-key wire table (tfhe_mk_wires_alloc, tfhe_mk_gates_level, tfhe_mk_lut_level,
+        tfhe_mk_linear_level)."""
         eng = ck.engine(device)
         mk = isinstance(ck, MKCloudKey)
         if isinstance(inputs, LweSampleArray):
@@ -275,8 +278,6 @@ class Circuit:
         (eng.mk_wires_alloc if mk else eng.wires_alloc)(self.num_wires)
         if self._n_inputs:
             eng.wires_upload(0, m)
-        if mk and (self._luts or self._linear):
-            raise ValueError("integer nodes (lut, lut_multi, linear) run on single-key contexts only")
         plan = self.level_plan(eng.N)
         # no per-phase timing events while the levels run: each record keeps the stream's next kernel waiting ~5 us, and a level
         # of a narrow circuit is six short operations around one single-rotation kernel (tutorial circuit: 30.5 -> 30.1 ms)
@@ -306,8 +307,6 @@ class Circuit:
         M = m.shape[0]
         if M == 0:
             return np.zeros((0, len(self._outputs), m.shape[2]), np.int32)
-        if mk and (self._luts or self._linear):
-            raise ValueError("integer nodes (lut, lut_multi, linear) run on single-key contexts only")
         plan = self.level_plan(eng.N, M)
         (eng.mk_wires_alloc if mk else eng.wires_alloc)(self.num_wires * M)
         if self._n_inputs:

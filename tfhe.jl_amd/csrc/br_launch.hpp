@@ -9,19 +9,7 @@
 
 #include <type_traits>
 
-// a TV batch's arguments: the family's struct and the tables of the part's rows
-template <class A>
-static WithTv<A> with_tv(const A &a, const TvPtrs &tv)
-{
-    WithTv<A> t;
-    static_cast<A &>(t) = a;
-    t.tv = tv.tv;
-    t.tv_index = tv.index;
-    t.bodies = tv.bodies;
-    t.n_out = tv.n_out;
-    return t;
-}
-
+// (with_tv, engine.hpp: a TV batch's arguments)
 // One launch.  Dynamic LDS beyond the default 64 KB is granted first (ensure_dyn_lds: once per device and kernel).
 template <class K, class... A>
 static int32_t br_run(tfhe_ctx *c, K *kernel, const BrLaunch &g, hipStream_t s, const A &...args)

@@ -10,7 +10,8 @@
 //   engine_diag.hip       timing, rounding margin, in-kernel clock, options                           ("diagnostics")
 //   engine_tv.hip         the TV kernels (programmable bootstrapping) and the TV form of the launchers ("tv")
 //   br_launch.hpp         the launch of each single-key blind-rotation family, compiled by engine_dispatch.hip and engine_tv.hip
-//   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit
+//   engine_mk_tv.hip      the multi-key TV kernels (multi-key programmable bootstrapping) and their launchers     ("mk tv")
+//   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit (-DG2_TV=1: its TV form)
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
 // only under the TFHE_EMIT_* macro of the unit that launches them (templates are instantiated where they are launched).
@@ -413,9 +414,22 @@ void name_kernel(tfhe_ctx *c, const char *fmt, ...) __attribute__((format(printf
 // A multi-output TV batch (tfhe_bootstrap_tv_multi_batch) adds `bodies`, [R][n_out]: the kernels also write the body coefficients
 // j N / n_out of each rotation there (kernels_common.hpp: store_bodies); NULL for a plain TV batch.
 struct TvPtrs { const int32_t *tv; const int32_t *index; int32_t *bodies = nullptr; int32_t n_out = 1; };
+// a TV batch's arguments: the family's struct and the tables of the batch's (or the part's) rows
+template <class A>
+static WithTv<A> with_tv(const A &a, const TvPtrs &tv)
+{
+    WithTv<A> t;
+    static_cast<A &>(t) = a;
+    t.tv = tv.tv;
+    t.tv_index = tv.index;
+    t.bodies = tv.bodies;
+    t.n_out = tv.n_out;
+    return t;
+}
 int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, const TvPtrs *tv = nullptr);
 int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out, hipStream_t s);
-int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, int32_t *out, hipStream_t s);
+int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out,
+                            hipStream_t s);
 // engine_gates.hip
 int32_t enter_stream(tfhe_ctx *c, hipStream_t s);
 int32_t leave_stream(tfhe_ctx *c, hipStream_t s);
@@ -439,7 +453,13 @@ int32_t run_int_level(tfhe_ctx *c, const IntLevel &L);
 int32_t launch_trivial(tfhe_ctx *c, size_t T, const int32_t *d_in0, const int32_t *d_ts, const int32_t *d_td, const uint8_t *d_top, int32_t *d_out,
                        int words, hipStream_t s);
 // engine_multikey.hip
-int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s);
+// (tv != NULL: the multi-key TV kernels, the same kernel family, geometry and LDS as a mu batch; "+tv" in tfhe_last_kernel_name)
+int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s, const TvPtrs *tv = nullptr);
+// engine_mk_tv.hip: one launch of a multi-key TV kernel with the instantiation and geometry launch_mk_blind_rotate decided (no DIAG
+// form: the multi-key TV entry points refuse measure_margin)
+int32_t mk_tv_launch_anyn(tfhe_ctx *c, const WithTv<anyn::Args> &a, unsigned nblk, unsigned nt, size_t lds, hipStream_t s);
+int32_t mk_tv_launch_w2(tfhe_ctx *c, const WithTv<MkBrArgs> &a, int rw, unsigned nblk, size_t lds, hipStream_t s);
+int32_t mk_tv_launch_general(tfhe_ctx *c, const WithTv<MkGenArgs> &a, int rw, bool accg, unsigned nblk, size_t lds, hipStream_t s);
 int32_t run_mk_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t B, const int32_t *d_in0, const int32_t *d_in1, const int32_t *d_in2,
                      int32_t *d_out, const int32_t *ia, const int32_t *ib, const int32_t *ic, const int32_t *io, hipStream_t s);
 // br_launch.hpp: one launch of each single-key blind-rotation family with the instantiation and geometry launch_blind_rotate_part

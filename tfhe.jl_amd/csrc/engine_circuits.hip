@@ -455,18 +455,26 @@ static int32_t multi_int_level(tfhe_ctx *c, const IntLevel &L)
     return TFHE_OK;
 }
 
-static int32_t int_level(tfhe_ctx *c, const char *who, const IntLevel &L)
+// mk: tfhe_mk_lut_level / tfhe_mk_linear_level, on the multi-key wire table (tfhe_mk_wires_alloc: one device) of a multi-key context
+static int32_t int_level(tfhe_ctx *c, const char *who, bool mk, const IntLevel &L)
 {
     const bool lut = L.tv != nullptr;
     if (L.B < 0 || (L.B > 0 && (!L.term_start || !L.out))) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL argument or negative B", who);
-    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key", who);
+    if (!mk && c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key", who);
+    if (mk && c->P.parties == 1) return c->set_err(TFHE_ERR_STATE, "%s: context is single-key", who);
     if (c->multi() ? c->num_wires <= 0 : !c->d_wires) return c->set_err(TFHE_ERR_STATE, "%s: no wire table allocated", who);
-    if (!c->multi() && c->wires_parties) return c->set_err(TFHE_ERR_STATE, "%s: the wire table has multi-key rows (tfhe_mk_wires_alloc)", who);
+    if (!mk && !c->multi() && c->wires_parties) return c->set_err(TFHE_ERR_STATE, "%s: the wire table has multi-key rows (tfhe_mk_wires_alloc)", who);
+    if (mk && !c->wires_parties)
+        return c->set_err(TFHE_ERR_STATE, "%s: the wire table has single-key rows (tfhe_wires_alloc): allocate it with tfhe_mk_wires_alloc", who);
     const tfhe_ctx *dev0 = c->multi() ? c->kids[0] : c;        // (options and keys are the same on every device of a context)
     if (lut && dev0->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the TV kernels have no DIAG instantiation)", who);
+    if (mk && lut && (c->mk_parties != c->wires_parties || c->mk_ks_parties != c->mk_parties))
+        return c->set_err(TFHE_ERR_STATE, "%s: the wire table holds %d-party rows, the bootstrapping key is for %d parties and the keyswitch key for %d",
+                          who, c->wires_parties, c->mk_parties, c->mk_ks_parties);
     if (L.B == 0) return TFHE_OK;
     { const int32_t rcv = validate_int_level(c, who, c->num_wires, c->P.N, L); if (rcv) return rcv; }
-    if (lut && (!dev0->have_bk || !dev0->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: bootstrapping/keyswitch key not loaded", who);
+    if (!mk && lut && (!dev0->have_bk || !dev0->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: bootstrapping/keyswitch key not loaded", who);
+    if (mk && lut && (!c->have_mk_bk || !c->have_mk_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
     if (c->multi()) return multi_int_level(c, L);
     HIP_TRY(c, hipSetDevice(c->device));
     return run_int_level(c, L);
@@ -478,7 +486,7 @@ int32_t tfhe_lut_level(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32
     ENTER_CTX(c);
     if (B > 0 && !tv) return c->set_err(TFHE_ERR_INVALID_ARG, "lut_level: NULL test polynomials");
     static const int32_t kNoTable = 0;      // (B == 0 with tv NULL: nothing to run, but the call is still the LUT form)
-    return int_level(c, "lut_level", IntLevel{tv ? tv : &kNoTable, n_tv, tv_index, n_out, term_start, term_wire, term_coef, cst, out, B});
+    return int_level(c, "lut_level", false, IntLevel{tv ? tv : &kNoTable, n_tv, tv_index, n_out, term_start, term_wire, term_coef, cst, out, B});
 }
 ABI_CATCH(c, "tfhe_lut_level")
 
@@ -486,6 +494,25 @@ int32_t tfhe_linear_level(tfhe_ctx *c, const int32_t *term_start, const int32_t 
                           const int32_t *out, int64_t B) try
 {
     ENTER_CTX(c);
-    return int_level(c, "linear_level", IntLevel{nullptr, 0, nullptr, 1, term_start, term_wire, term_coef, cst, out, B});
+    return int_level(c, "linear_level", false, IntLevel{nullptr, 0, nullptr, 1, term_start, term_wire, term_coef, cst, out, B});
 }
 ABI_CATCH(c, "tfhe_linear_level")
+
+// tfhe_lut_level / tfhe_linear_level on the multi-key wire table: rows of P n + 1 words, the multi-key rotation and keyswitch
+int32_t tfhe_mk_lut_level(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out, const int32_t *term_start,
+                          const int32_t *term_wire, const int32_t *term_coef, const int32_t *cst, const int32_t *out, int64_t B) try
+{
+    ENTER_CTX(c);
+    if (B > 0 && !tv) return c->set_err(TFHE_ERR_INVALID_ARG, "mk_lut_level: NULL test polynomials");
+    static const int32_t kNoTable = 0;
+    return int_level(c, "mk_lut_level", true, IntLevel{tv ? tv : &kNoTable, n_tv, tv_index, n_out, term_start, term_wire, term_coef, cst, out, B});
+}
+ABI_CATCH(c, "tfhe_mk_lut_level")
+
+int32_t tfhe_mk_linear_level(tfhe_ctx *c, const int32_t *term_start, const int32_t *term_wire, const int32_t *term_coef, const int32_t *cst,
+                             const int32_t *out, int64_t B) try
+{
+    ENTER_CTX(c);
+    return int_level(c, "mk_linear_level", true, IntLevel{nullptr, 0, nullptr, 1, term_start, term_wire, term_coef, cst, out, B});
+}
+ABI_CATCH(c, "tfhe_mk_linear_level")

@@ -398,15 +398,17 @@ int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t
 }
 
 // mk_keyswitch (mk_internals.jl:397-411): per party a single-key keyswitch of its mask column with b = 0, the b words chained
-// through the output (stream-ordered).  ext = the context's extracted samples [R][P N + 1], out: [.][P n + 1].  Sample g is
+// through the output (stream-ordered).  ext = the extracted samples [R][P N + 1] (the context's ext, or tv_ext for a multi-output
+// TV batch), out: [.][P n + 1].  Sample g is
 // ext[e0[g]] (+ ext[e1[g]] + (0, 1/8) for MUX, gates.jl:174: the b part enters once, with party 0) written to row dst[g]
 // (e1, dst NULL: no second operand, identity), as launch_keyswitch.
-int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t B, const int32_t *e0, const int32_t *e1, const int32_t *dst, int32_t *out, hipStream_t s)
+int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t B, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out,
+                            hipStream_t s)
 {
     const int NP = c->mk_parties, n = c->P.n, nw = NP * n + 1, Nn = c->P.N, ew = NP * Nn + 1;
     if (c->ks_mode == 4) {
         Ks4Args a4;
-        a4.ext = (const int32_t *)c->ext.p; a4.e0 = e0; a4.e1 = e1; a4.dst = dst; a4.out = out;
+        a4.ext = ext; a4.e0 = e0; a4.e1 = e1; a4.dst = dst; a4.out = out;
         a4.n = n; a4.kN = Nn; a4.G = (int)B; a4.wtiles = c->ks4_wtiles;
         a4.in_stride = ew; a4.in_b = NP * Nn; a4.out_stride = nw; a4.out_b = NP * n;
         for (int p = 0; p < NP; p++) {
@@ -421,7 +423,7 @@ int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t B, const int32_t *e0, const int3
     } else if (c->ks_mode == 1) {
         // any base / length: the gather kernel per party
         KsArgs k1;
-        k1.ext = (const int32_t *)c->ext.p; k1.e0 = e0; k1.e1 = e1; k1.dst = dst; k1.out = out;
+        k1.ext = ext; k1.e0 = e0; k1.e1 = e1; k1.dst = dst; k1.out = out;
         k1.n = n; k1.kN = c->P.N; k1.t = c->P.ks_t; k1.log2_base = c->P.ks_log2_base;
         k1.in_stride = ew; k1.in_b = NP * c->P.N; k1.out_stride = nw; k1.out_b = NP * n;
         for (int p = 0; p < NP; p++) {
@@ -431,7 +433,7 @@ int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t B, const int32_t *e0, const int3
         }
     } else {
         Ks3Args k3;
-        k3.ext = (const int32_t *)c->ext.p; k3.e0 = e0; k3.e1 = e1; k3.dst = dst; k3.out = out;
+        k3.ext = ext; k3.e0 = e0; k3.e1 = e1; k3.dst = dst; k3.out = out;
         k3.n = n; k3.kN = Nn; k3.t = c->P.ks_t; k3.log2_base = 2; k3.stride = c->ks_stride; k3.G = (int)B;
         k3.in_stride = ew; k3.in_b = NP * Nn; k3.out_stride = nw; k3.out_b = NP * n;
         k3.in_off = 0; k3.out_off = 0; k3.ksp = c->d_mk_ksp;

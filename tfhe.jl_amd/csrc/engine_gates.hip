@@ -202,7 +202,7 @@ int32_t launch_prologue(tfhe_ctx *c, size_t R, const int32_t *d_in0, const int32
 int32_t launch_linear_prologue(tfhe_ctx *c, bool lut, size_t B, const int32_t *d_start, const int32_t *d_wire, const int32_t *d_coef,
                                const int32_t *d_cst, const int32_t *d_out, hipStream_t s)
 {
-    const int n = c->P.n, log2_2N = ilog2i(2 * c->P.N);
+    const int n = (int)c->wire_words() - 1, log2_2N = ilog2i(2 * c->P.N);      // (rows of the table: n + 1 words, P n + 1 multi-key)
     if (lut)
         hipLaunchKernelGGL(linear_prologue_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, (const int32_t *)c->d_wires, d_start, d_wire, d_coef,
                            d_cst, d_out, (int32_t *)c->bara.p, n, log2_2N);
@@ -517,10 +517,12 @@ ABI_CATCH(c, "tfhe_gates_batch_wait")
 // the R n_out samples are keyswitched through launch_keyswitch's maps (e0, dst) into out.  *samples receives the extracted samples,
 // [R n_out][k N + 1] (what a call without keyswitch hands back).  Timing events 1 - 3 if `events`: rotation, then shift + keyswitch.
 // Callers: bootstrap_rows (host buffers: identity maps into io[3]) and run_lut_level (the wire table: dst = the level's output wires).
+// On a multi-key context (P.parties > 1) the same with the multi-key rotation and keyswitch: samples of P N + 1 words in, P n + 1 out.
 static int32_t rotate_rows(tfhe_ctx *c, size_t R, int32_t mu, const TvPtrs *tv, int32_t n_out, const int32_t *e0, const int32_t *dst,
                            int32_t *out, const int32_t **samples, bool events, hipStream_t s)
 {
-    const int kNn = c->P.k * c->P.N;
+    const bool mk = c->P.parties != 1;
+    const int kNn = mk ? c->mk_parties * c->P.N : c->P.k * c->P.N;
     const size_t G = R * (size_t)n_out;                                          // output samples
     const bool multi_out = n_out > 1;
     HIP_TRY(c, c->ext.reserve(R * (kNn + 1) * 4));
@@ -536,7 +538,7 @@ static int32_t rotate_rows(tfhe_ctx *c, size_t R, int32_t mu, const TvPtrs *tv, 
     }
     *samples = multi_out ? (const int32_t *)c->tv_ext.p : (const int32_t *)c->ext.p;
     if (events) HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    int32_t rc = launch_blind_rotate(c, R, mu, s, tv ? &tvd : nullptr);
+    int32_t rc = mk ? launch_mk_blind_rotate(c, R, s, tv ? &tvd : nullptr) : launch_blind_rotate(c, R, mu, s, tv ? &tvd : nullptr);
     if (rc) return rc;
     if (events) HIP_TRY(c, hipEventRecord(c->ev[2], s));
     if (multi_out) {
@@ -546,7 +548,7 @@ static int32_t rotate_rows(tfhe_ctx *c, size_t R, int32_t mu, const TvPtrs *tv, 
         HIP_TRY(c, hipGetLastError());
     }
     if (e0) {
-        rc = launch_keyswitch(c, G, e0, nullptr, dst, *samples, out, s);
+        rc = mk ? launch_mk_keyswitch(c, G, e0, nullptr, dst, *samples, out, s) : launch_keyswitch(c, G, e0, nullptr, dst, *samples, out, s);
         if (rc) return rc;
     }
     if (events) HIP_TRY(c, hipEventRecord(c->ev[3], s));
@@ -558,12 +560,16 @@ struct TvHost { const int32_t *tv; int32_t n_tv; const int32_t *index; };
 
 // tfhe_bootstrap_batch (tv == NULL), tfhe_bootstrap_tv_batch (n_out = 1) and tfhe_bootstrap_tv_multi_batch on a device context or,
 // row-split, on the kids of a multi-device one: upload, modulus switch, rotate_rows with identity maps, download.  out is
-// [B][n_out][width].  The shift belongs to the keyswitch phase of the timing events.
+// [B][n_out][width].  The shift belongs to the keyswitch phase of the timing events.  A multi-key context (tfhe_mk_bootstrap_tv_batch,
+// tfhe_mk_bootstrap_tv_multi_batch) takes rows of P n + 1 words and returns P n + 1 (P N + 1 without keyswitch).
 static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const TvHost *tv, int32_t n_out, const int32_t *in, int32_t *out, int64_t B,
                               int32_t with_keyswitch)
 {
+    const bool mk = c->P.parties != 1;
     if (c->multi()) {
-        const size_t wi = (size_t)c->P.n + 1, wo = (with_keyswitch ? wi : (size_t)c->P.k * c->P.N + 1) * (size_t)n_out;
+        if (mk && !c->kids[0]->have_mk_bk) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
+        const int NP = mk ? c->kids[0]->mk_parties : 1;
+        const size_t wi = (size_t)NP * c->P.n + 1, wo = (with_keyswitch ? wi : (size_t)(mk ? NP : c->P.k) * c->P.N + 1) * (size_t)n_out;
         return multi_rows(c, B, [&](tfhe_ctx *k, int64_t s0, int64_t cnt) {
             alloc_checkpoint();
             CallGuard kid_guard(k);
@@ -573,11 +579,19 @@ static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const Tv
             return bootstrap_rows(k, who, mu, tv ? &part : nullptr, n_out, in + (size_t)s0 * wi, out + (size_t)s0 * wo, cnt, with_keyswitch);
         });
     }
-    if (!c->have_bk || (with_keyswitch && !c->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: key not loaded", who);
+    if (mk) {
+        if (!c->have_mk_bk || (with_keyswitch && !c->have_mk_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
+        // (the keyswitch loops over the bootstrapping key's parties: a keyswitch key loaded for fewer would be read past its end)
+        if (with_keyswitch && c->mk_ks_parties != c->mk_parties)
+            return c->set_err(TFHE_ERR_STATE, "%s: the bootstrapping key was loaded for %d parties, the keyswitch key for %d: load both for the same parties",
+                              who, c->mk_parties, c->mk_ks_parties);
+    } else if (!c->have_bk || (with_keyswitch && !c->have_ks)) {
+        return c->set_err(TFHE_ERR_NO_KEY, "%s: key not loaded", who);
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }
-    const int n = c->P.n, kNn = c->P.k * c->P.N;
+    const int n = mk ? c->mk_parties * c->P.n : c->P.n, kNn = mk ? c->mk_parties * c->P.N : c->P.k * c->P.N;      // (n: mask words of a sample)
     const size_t in_bytes = (size_t)B * (n + 1) * 4, G = (size_t)B * n_out;      // G: output samples
     HIP_TRY(c, c->io[0].reserve(in_bytes));
     HIP_TRY(c, hipMemcpyAsync(c->io[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
@@ -669,7 +683,7 @@ int32_t run_int_level(tfhe_ctx *c, const IntLevel &L)
         return leave_stream(c, s);
     }
     const bool events = c->timing_events != 0;
-    HIP_TRY(c, c->bara.reserve(B * (size_t)(c->P.n + 1) * 4));
+    HIP_TRY(c, c->bara.reserve(B * c->wire_words() * 4));
     if (events) HIP_TRY(c, hipEventRecord(c->ev[0], s));
     rc = launch_linear_prologue(c, true, B, d + o_start, d + o_wire, d + o_coef, d_cst, nullptr, s);
     if (rc) return rc;
@@ -695,7 +709,8 @@ ABI_CATCH(c, "tfhe_bootstrap_batch")
 
 // Programmable bootstrapping: tfhe_bootstrap_batch with row g's test polynomial tv[tv_index[g]] instead of (mu, ..., mu), and n_out
 // samples per row, extracted at the coefficients j N / n_out (tfhe_bootstrap_tv_batch: n_out = 1).
-static int32_t bootstrap_tv_rows(tfhe_ctx *c, const char *who, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out,
+// mk: the multi-key form (tfhe_mk_bootstrap_tv*_batch), on a multi-key context only.
+static int32_t bootstrap_tv_rows(tfhe_ctx *c, const char *who, bool mk, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out,
                                  const int32_t *in, int32_t *out, int64_t B, int32_t with_keyswitch)
 {
     if (B < 0 || (B > 0 && (!in || !out || !tv))) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL argument or negative B", who);
@@ -707,7 +722,8 @@ static int32_t bootstrap_tv_rows(tfhe_ctx *c, const char *who, const int32_t *tv
             if (tv_index[g] < 0 || tv_index[g] >= n_tv)
                 return c->set_err(TFHE_ERR_INVALID_ARG, "%s: tv_index[%lld] = %d is outside [0, %d)", who, (long long)g, tv_index[g], n_tv);
     if (B == 0) return TFHE_OK;
-    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key", who);
+    if (!mk && c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key", who);
+    if (mk && c->P.parties == 1) return c->set_err(TFHE_ERR_STATE, "%s: context is single-key", who);
     if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the TV kernels have no DIAG instantiation)", who);
     const TvHost th{tv, n_tv, tv_index};
     return bootstrap_rows(c, who, 0, &th, n_out, in, out, B, with_keyswitch);
@@ -718,7 +734,7 @@ int32_t tfhe_bootstrap_tv_batch(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, co
 {
     ENTER_CTX(c);
     if (!c) return TFHE_ERR_INVALID_ARG;
-    return bootstrap_tv_rows(c, "bootstrap_tv_batch", tv, n_tv, tv_index, 1, in, out, B, with_keyswitch);
+    return bootstrap_tv_rows(c, "bootstrap_tv_batch", false, tv, n_tv, tv_index, 1, in, out, B, with_keyswitch);
 }
 ABI_CATCH(c, "tfhe_bootstrap_tv_batch")
 
@@ -727,9 +743,29 @@ int32_t tfhe_bootstrap_tv_multi_batch(tfhe_ctx *c, const int32_t *tv, int32_t n_
 {
     ENTER_CTX(c);
     if (!c) return TFHE_ERR_INVALID_ARG;
-    return bootstrap_tv_rows(c, "bootstrap_tv_multi_batch", tv, n_tv, tv_index, n_out, in, out, B, with_keyswitch);
+    return bootstrap_tv_rows(c, "bootstrap_tv_multi_batch", false, tv, n_tv, tv_index, n_out, in, out, B, with_keyswitch);
 }
 ABI_CATCH(c, "tfhe_bootstrap_tv_multi_batch")
+
+// Multi-key programmable bootstrapping: tfhe_bootstrap_tv_batch / tfhe_bootstrap_tv_multi_batch on samples [P n + 1] under the multi-key
+// keys (mk_internals.jl:464-495 with row g's test polynomial for the body, then mk_keyswitch)
+int32_t tfhe_mk_bootstrap_tv_batch(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, const int32_t *in, int32_t *out, int64_t B,
+                                   int32_t with_keyswitch) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    return bootstrap_tv_rows(c, "mk_bootstrap_tv_batch", true, tv, n_tv, tv_index, 1, in, out, B, with_keyswitch);
+}
+ABI_CATCH(c, "tfhe_mk_bootstrap_tv_batch")
+
+int32_t tfhe_mk_bootstrap_tv_multi_batch(tfhe_ctx *c, const int32_t *tv, int32_t n_tv, const int32_t *tv_index, int32_t n_out, const int32_t *in,
+                                         int32_t *out, int64_t B, int32_t with_keyswitch) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    return bootstrap_tv_rows(c, "mk_bootstrap_tv_multi_batch", true, tv, n_tv, tv_index, n_out, in, out, B, with_keyswitch);
+}
+ABI_CATCH(c, "tfhe_mk_bootstrap_tv_multi_batch")
 
 int32_t tfhe_keyswitch_batch(tfhe_ctx *c, const int32_t *in, int32_t *out, int64_t B) try
 {

@@ -7,10 +7,13 @@
 
 // The multi-key blind rotations of R samples: bara [R][P n + 1] -> ext [R][P N + 1], mu = encode_message(1, 8).  Picks the kernel
 // by parameter set and batch size (the tuned 2-party kernel, the shipped 4- / 8-party two-wave kernels, the any-party kernel,
-// the any-N kernel) and launches it on stream s; tfhe_last_kernel_name names it.
-int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s)
+// the any-N kernel) and launches it on stream s; tfhe_last_kernel_name names it.  With tv, rotation w starts its body from
+// X^{-barb} tv->tv[tv->index[w]] (the multi-key TV kernels, engine_mk_tv.hip and the mk_g2_tv objects: same family, geometry and LDS;
+// "+tv" in the name); tv->bodies as launch_blind_rotate.
+int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s, const TvPtrs *tv)
 {
     const int NP = c->mk_parties, n = c->P.n, Nn = c->P.N /* (1024 in every tuned branch below) */;
+    if (tv && c->measure_margin) return c->set_err(TFHE_ERR_STATE, "mk_bootstrap_tv: no DIAG instantiation of the multi-key TV kernels (measure_margin is on)");
     MkBrArgs a;
     int32_t rc = prepare_diag(c, R, s, a.diag);
     if (rc) return rc;
@@ -40,7 +43,10 @@ int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s)
         }
         const size_t ldsa = anyn::lds_bytes(Nn, spec_lds ? 3 : 0);
         const unsigned nt = (unsigned)anyn::threads_for(Nn);
-        if (dg) {
+        if (tv) {
+            rc = mk_tv_launch_anyn(c, with_tv(g, *tv), (unsigned)R, nt, ldsa, s);
+            if (rc) return rc;
+        } else if (dg) {
             if (ldsa > 64 * 1024) LDS_TRY(c, ldsa, anyn::mk_blind_rotate_kernel<true>);
             hipLaunchKernelGGL((anyn::mk_blind_rotate_kernel<true>), dim3((unsigned)R), dim3(nt), ldsa, s, g);
         } else {
@@ -61,7 +67,10 @@ int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s)
                 LDS_TRY(c, lds2, mk_blind_rotate_kernel_w2<LL, DG, RWV>); \
             hipLaunchKernelGGL((mk_blind_rotate_kernel_w2<LL, DG, RWV>), dim3(nblk), dim3(128 * RWV), lds2, s, a);  \
         } while (0)
-        if (dg) LAUNCH_MK2(4, true, 1);
+        if (tv) {
+            rc = mk_tv_launch_w2(c, with_tv(a, *tv), rw, nblk, lds2, s);
+            if (rc) return rc;
+        } else if (dg) LAUNCH_MK2(4, true, 1);
         else if (rw == 2) LAUNCH_MK2(4, false, 2);
         else LAUNCH_MK2(4, false, 1);
 #undef LAUNCH_MK2
@@ -96,7 +105,8 @@ int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s)
             HIP_TRY(c, c->mk_acc.reserve((size_t)nblk * rw * (NP + 1) * kImg * sizeof(int32_t)));
             ga.acc = (int32_t *)c->mk_acc.p;
         }
-        HIP_TRY(c, tfhe_launch_mk_g2(NP, dg, rw, acc_lds, nblk, ldsg2, s, ga));
+        if (tv) HIP_TRY(c, tfhe_launch_mk_g2_tv(NP, rw, nblk, ldsg2, s, with_tv(ga, *tv)));
+        else HIP_TRY(c, tfhe_launch_mk_g2(NP, dg, rw, acc_lds, nblk, ldsg2, s, ga));
         name_kernel(c, acc_lds ? "mk_blind_rotate_kernel_g2<%d,%d,acc=lds>" : "mk_blind_rotate_kernel_g2<%d,%d>", NP, c->P.bs_l);
 #endif
     } else {
@@ -126,12 +136,16 @@ int32_t launch_mk_blind_rotate(tfhe_ctx *c, size_t R, hipStream_t s)
             if (accg) hipLaunchKernelGGL((mk_blind_rotate_kernel_general<DG, RWV, true>), dim3(nblk), dim3(64 * RWV), ldsg, s, ga); \
             else hipLaunchKernelGGL((mk_blind_rotate_kernel_general<DG, RWV, false>), dim3(nblk), dim3(64 * RWV), ldsg, s, ga); \
         } while (0)
-        if (dg) LAUNCH_MKG(true, 1);
+        if (tv) {
+            rc = mk_tv_launch_general(c, with_tv(ga, *tv), rw, accg, nblk, ldsg, s);
+            if (rc) return rc;
+        } else if (dg) LAUNCH_MKG(true, 1);
         else if (rw == 2) LAUNCH_MKG(false, 2);
         else LAUNCH_MKG(false, 1);
 #undef LAUNCH_MKG
         name_kernel(c, accg ? "mk_blind_rotate_kernel_general(P=%d,L=%d,acc=global)" : "mk_blind_rotate_kernel_general(P=%d,L=%d)", NP, c->P.bs_l);
     }
+    if (tv) c->last_kernel += "+tv";
     HIP_TRY(c, hipGetLastError());
     return TFHE_OK;
 }
@@ -186,7 +200,7 @@ int32_t tfhe_mk_gate_nand_batch(tfhe_ctx *c, const int32_t *in0, const int32_t *
     rc = launch_mk_blind_rotate(c, (size_t)B, s);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    rc = launch_mk_keyswitch(c, (size_t)B, d_gate, nullptr, nullptr, (int32_t *)c->io[3].p, s);
+    rc = launch_mk_keyswitch(c, (size_t)B, d_gate, nullptr, nullptr, (const int32_t *)c->ext.p, (int32_t *)c->io[3].p, s);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[3], s));
     HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, bytes, hipMemcpyDeviceToHost, s));
@@ -284,7 +298,7 @@ int32_t run_mk_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64
     }
     if (!no_ev) HIP_TRY(c, hipEventRecord(c->ev[2], s));
     if (G > 0) {
-        rc = launch_mk_keyswitch(c, G, d_e0, d_e1, d_dst, d_out, s);
+        rc = launch_mk_keyswitch(c, G, d_e0, d_e1, d_dst, (const int32_t *)c->ext.p, d_out, s);
         if (rc) return rc;
     }
     if (!no_ev) HIP_TRY(c, hipEventRecord(c->ev[3], s));

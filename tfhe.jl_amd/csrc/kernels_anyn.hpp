@@ -274,7 +274,7 @@ __global__ __launch_bounds__(512) void TV_KERNEL(blind_rotate_kernel)(TV_ARGS(Ar
 // Three spectrum accumulators are live whatever P is: a'_s of a non-party source is fed by its own digits only and nobody
 // else reads acc[s] in this step, so it is finished right after source s.
 template <bool MARGIN>
-__global__ __launch_bounds__(512) void mk_blind_rotate_kernel(Args P)
+__global__ __launch_bounds__(512) void TV_KERNEL(mk_blind_rotate_kernel)(TV_ARGS(Args) P)
 {
     unsigned long long dg_t0 = 0, dg_r0 = 0;
     diag_begin<MARGIN>(dg_t0, dg_r0);
@@ -297,10 +297,11 @@ __global__ __launch_bounds__(512) void mk_blind_rotate_kernel(Args P)
 
     {
         const int barb = bara[(size_t)NP * P.n] & (2 * N - 1);
+        const int32_t *tvp = kTV ? tv_of(P, w, N) : nullptr;
         for (int e = tid; e < (NP + 1) * N; e += nt) {
             const int c = e >> P.log2N, j = e & (N - 1);
             const int idx = (j + barb) & (2 * N - 1);
-            acc[e] = c < NP ? 0 : (idx & N) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
+            acc[e] = c < NP ? 0 : kTV ? tv_coef(tvp, idx, N) : (idx & N) ? (int32_t)(0u - (uint32_t)P.mu) : P.mu;
         }
     }
     __syncthreads();
@@ -358,6 +359,7 @@ __global__ __launch_bounds__(512) void mk_blind_rotate_kernel(Args P)
         else ext[(size_t)c * N + N - j] = (int32_t)(0u - (uint32_t)v);
     }
     if (tid == 0) ext[(size_t)NP * N] = acc[(size_t)NP * N];
+    store_bodies(P, w, tid, acc + (size_t)NP * N, N);
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0);
 }
 

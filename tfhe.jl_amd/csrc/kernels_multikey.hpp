@@ -180,7 +180,7 @@ __device__ __forceinline__ void mk2_party_steps(int lane_in, const MkBrArgs &P, 
 // RW rotations per workgroup advance in lockstep (the barriers are workgroup-wide): rotations that read the same key
 // values at the same time share one trip beyond L2 (the 2-party key is 197 MB as spectra).
 template <int L, bool MARGIN = false, int RW = 2>
-__global__ __launch_bounds__(128 * RW, 2) void mk_blind_rotate_kernel_w2(MkBrArgs P)
+__global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(mk_blind_rotate_kernel_w2)(TV_ARGS(MkBrArgs) P)
 {
     // Round 6: the register part of the twist in tan form, forward and inverse, with OPAQUE constants (load_tan16): 16.54 -> 16.28 ms per
     // 1024 gates on one device (forward only: 16.36).  Round 5 tried the same with compile-time constants and lost 23 % to scalar spills.
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(128 * RW, 2) void mk_blind_rotate_kernel_w2(MkBrArg
     if (lane == 0) pair_flags[wv] = 0;
     // acc = (0, ..., 0, X^{-barb} * mu)       mk_internals.jl:491-492, 72-79
     if (wv == 0) { init_zero_poly(lane, acc_lds); init_zero_poly(lane, acc_lds + kImg); }
-    else init_body_poly(lane, bara[NP * P.n] & (2 * kN - 1), P.mu, acc_lds + 2 * kImg);
+    else init_body(lane, bara[NP * P.n] & (2 * kN - 1), P, w, acc_lds + 2 * kImg);
     __syncthreads();
     wave_priority_begin(P.prio_steps);
     Tan16 tk;
@@ -234,6 +234,7 @@ __global__ __launch_bounds__(128 * RW, 2) void mk_blind_rotate_kernel_w2(MkBrArg
     int32_t *ext = P.ext + w * (NP * kN + 1);
     extract_mask_poly(lane_e, acc_lds + wv * kImg, ext + wv * kN);                // wave c extracts mask column c
     if (wv == 0 && lane_e == 0) ext[NP * kN] = acc_lds[NP * kImg + kMir];
+    if (wv == 0) store_bodies(P, w, lane_e, acc_lds + NP * kImg + kMir, kN);
 }
 
 // ---- multi-key blind rotation, any number of parties (2..8) and any decomposition length (<= 8) ------------
@@ -263,7 +264,7 @@ struct MkGenArgs {
 // of every polynomial per step, L2-resident) is a tenth of the step's key traffic.  A wave reads back only what it wrote
 // itself; the workgroup-scope fence at the end of a step orders those stores before the next step's loads.
 template <bool MARGIN = false, int RW = 1, bool ACCG = false>
-__global__ __launch_bounds__(64 * RW, 1) void mk_blind_rotate_kernel_general(MkGenArgs P)
+__global__ __launch_bounds__(64 * RW, 1) void TV_KERNEL(mk_blind_rotate_kernel_general)(TV_ARGS(MkGenArgs) P)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int NP = P.parties, L = P.L;
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(64 * RW, 1) void mk_blind_rotate_kernel_general(MkG
     for (int q = 0; q < 8; q++) tw1f[q] = P.T.tw1f[q * 64 + lane];
     tw2_lds[lane] = P.T.tw2[lane];
     for (int s = 0; s < NP; s++) init_zero_poly(lane, acc_lds + s * kImg);
-    init_body_poly(lane, bara[(size_t)NP * P.n] & (2 * kN - 1), P.mu, acc_lds + NP * kImg);
+    init_body(lane, bara[(size_t)NP * P.n] & (2 * kN - 1), P, w, acc_lds + NP * kImg);
     auto acc_fence = [&]() {
         if (ACCG) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -363,6 +364,7 @@ __global__ __launch_bounds__(64 * RW, 1) void mk_blind_rotate_kernel_general(MkG
     int32_t *ext = P.ext + w * ((size_t)NP * kN + 1);
     for (int c = 0; c < NP; c++) extract_mask_poly(lane, acc_lds + c * kImg, ext + (size_t)c * kN);
     if (lane == 0) ext[(size_t)NP * kN] = acc_lds[NP * kImg + kMir];
+    store_bodies(P, w, lane, acc_lds + NP * kImg + kMir, kN);
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0, lane == 0);
 }
 
@@ -495,7 +497,7 @@ __device__ __forceinline__ void g2_party_steps(const MkGenArgs &P, const int32_t
 // chip still holds 1024 rotations.  The step then needs no workgroup-scope fence and no trip to L2 for the accumulators.
 // (8 parties: nine images do not fit; the accumulators stay in global memory.)
 template <int NP, int L, bool MARGIN = false, int RW = 2, bool ACCL = false>
-__global__ __launch_bounds__(128 * RW, 2) void mk_blind_rotate_kernel_g2(MkGenArgs P)
+__global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(mk_blind_rotate_kernel_g2)(TV_ARGS(MkGenArgs) P)
 {
     unsigned long long dg_t0 = 0, dg_r0 = 0;
     diag_begin<MARGIN>(dg_t0, dg_r0);
@@ -522,7 +524,7 @@ __global__ __launch_bounds__(128 * RW, 2) void mk_blind_rotate_kernel_g2(MkGenAr
         if (wib == 0) tw2_lds[lane0] = P.T.tw2[lane0];
         // acc = (0, ..., 0, X^{-barb} * mu)       mk_internals.jl:491-492, 72-79 : the polynomials are shared out by parity
         for (int s = wv; s < NP; s += 2) init_zero_poly(lane0, acc + s * kImg);
-        if (wv == (NP & 1)) init_body_poly(lane0, load_uniform_i32(bara + (size_t)NP * P.n) & (2 * kN - 1), P.mu, acc + NP * kImg);
+        if (wv == (NP & 1)) init_body(lane0, load_uniform_i32(bara + (size_t)NP * P.n) & (2 * kN - 1), P, w, acc + NP * kImg);
     }
     if constexpr (!ACCL) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
@@ -542,4 +544,5 @@ __global__ __launch_bounds__(128 * RW, 2) void mk_blind_rotate_kernel_g2(MkGenAr
     int32_t *ext = P.ext + w * ((size_t)NP * kN + 1);
     for (int c = wv; c < NP; c += 2) extract_mask_poly(lane_e, acc + c * kImg, ext + (size_t)c * kN);
     if (wv == 0 && lane_e == 0) ext[(size_t)NP * kN] = acc[NP * kImg + kMir];
+    if (wv == 0) store_bodies(P, w, lane_e, acc + NP * kImg + kMir, kN);
 }

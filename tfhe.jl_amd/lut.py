@@ -23,10 +23,17 @@ circuit through two conversions:
     passed to Circuit.lut as a raw table; its output is an operand of any gate.
 The coefficients of a combination are the caller's choice, as with LweSampleArray arithmetic: a term of coefficient c multiplies its
 sample's noise by |c|, and nothing checks that the sum still decodes.
+
+Under an MKCloudKey the same holds for multi-key samples int32 [P n + 1] (mk_lut_encrypt, mk_lut_decrypt; Engine.mk_bootstrap_tv,
+tfhe_mk_bootstrap_tv_batch): the multi-key blind rotation starts its body from the test polynomial, and the result is keyswitched
+back to the parties' LWE keys.  programmable_bootstrap and programmable_bootstrap_multi then return int32 arrays rather than
+LweSampleArrays, and Circuit runs its LUT and linear nodes on the multi-key wire table.  The multi-key bootstrap is noisier than the
+single-key one: under the shipped 2-party set p = 2 is the safe message space.
 """
 import numpy as np
 
 from .lwe import LweSampleArray, lwe_encrypt_many, lwe_phase
+from .mk_keys import MKCloudKey, MKLweSample, mk_encrypt_torus, mk_phase
 from .numeric import wrap32
 
 
@@ -78,6 +85,29 @@ def lut_decrypt(secret_key, samples, p):
     return lut_decode(lwe_phase(data, secret_key.key), p)
 
 
+def mk_lut_encrypt(rng, secret_keys, m, p):
+    """Messages m of Z_p as multi-key samples under the parties' secret keys (mk_encrypt at the phases lut_encode(m, p)):
+    int32 [B][P n + 1]."""
+    m = np.atleast_1d(np.asarray(m, np.int64))
+    if m.min(initial=0) < 0 or m.max(initial=0) >= p:
+        raise ValueError(f"messages must lie in [0, {p})")
+    return mk_encrypt_torus(rng, secret_keys, lut_encode(m, p).astype(np.int64))
+
+
+def mk_lut_decrypt(secret_keys, flat, p):
+    """The messages of Z_p of multi-key samples int32 [B][P n + 1] (mk_phase, lut_decode)."""
+    return lut_decode(mk_phase(secret_keys, flat), p)
+
+
+def _samples(data):
+    """An LweSampleArray, a list of MKLweSample (as Circuit.run takes them) or int32 rows, as int32 rows."""
+    if isinstance(data, LweSampleArray):
+        return data.data
+    if isinstance(data, (list, tuple)) and data and all(isinstance(x, MKLweSample) for x in data):
+        return np.stack([x.flat() for x in data])
+    return np.asarray(data, np.int32)
+
+
 def make_test_vector(f, p, N, q=None):
     """The test polynomial of x -> f(x), Z_p -> Z_q (q defaults to p): v[j] = lut_encode(f(floor(j p / N)), q), int32 [N].
     2 <= p <= N / 2, both powers of two."""
@@ -96,12 +126,15 @@ def programmable_bootstrap(ck, samples, tables_or_functions, index=None, p=8, q=
     `tables_or_functions`: one or a list of callables Z_p -> Z_q (made into test polynomials by make_test_vector) or int32
     test polynomials [N]; `index[g]` picks row g's (None: the first for every row).  p, q: powers of two, 2 <= p <= N/2; an input
     phase must lie within +-1/(4p) of its message's centre.  Returns an LweSampleArray of messages in Z_q (keyswitched back to
-    the LWE key unless with_keyswitch is False, then [B][k N + 1] words under the extracted TLWE key)."""
+    the LWE key unless with_keyswitch is False, then [B][k N + 1] words under the extracted TLWE key).  Under an MKCloudKey the
+    samples are multi-key (int32 [B][P n + 1] or a list of MKLweSample), and the result is int32 [B][P n + 1] ([B][P N + 1] without
+    keyswitch), the form every multi-key gate function returns."""
     eng = ck.engine(device)
     items = tables_or_functions if isinstance(tables_or_functions, (list, tuple)) else [tables_or_functions]
     tables = np.stack([make_test_vector(t, p, eng.N, q) if callable(t) else np.asarray(t, np.int32) for t in items])
-    data = samples.data if isinstance(samples, LweSampleArray) else np.asarray(samples, np.int32)
-    return LweSampleArray(eng.bootstrap_tv(tables, data, index=index, with_keyswitch=with_keyswitch))
+    if isinstance(ck, MKCloudKey):
+        return eng.mk_bootstrap_tv(tables, np.atleast_2d(_samples(samples)), index=index, with_keyswitch=with_keyswitch)
+    return LweSampleArray(eng.bootstrap_tv(tables, _samples(samples), index=index, with_keyswitch=with_keyswitch))
 
 
 def make_multi_test_vector(fs, p, N, q=None):
@@ -123,7 +156,8 @@ def programmable_bootstrap_multi(ck, samples, fs_or_tables, p, q=None, index=Non
     extracted TLWE key).
 
     `fs_or_tables`: a list of K callables Z_p -> Z_q (one packed table, make_multi_test_vector), a list of such lists with the same
-    K (`index[g]` picks row g's, None: the first), or int32 packed tables [N] / [n_tv][N], for which `n_out` gives K."""
+    K (`index[g]` picks row g's, None: the first), or int32 packed tables [N] / [n_tv][N], for which `n_out` gives K.  Under an
+    MKCloudKey the samples are multi-key, int32 [B][P n + 1], and the K results are int32 arrays."""
     eng = ck.engine(device)
     items = list(fs_or_tables) if isinstance(fs_or_tables, (list, tuple)) else [fs_or_tables]
     if items and all(callable(f) for f in items):
@@ -140,6 +174,8 @@ def programmable_bootstrap_multi(ck, samples, fs_or_tables, p, q=None, index=Non
     if len(ks) != 1:
         raise ValueError(f"the number of outputs is ambiguous: {sorted(ks) or 'not given'} (pass n_out with raw tables)")
     K = ks.pop()
-    data = samples.data if isinstance(samples, LweSampleArray) else np.asarray(samples, np.int32)
-    out = eng.bootstrap_tv_multi(np.stack(tables), data, K, index=index, with_keyswitch=with_keyswitch)
+    if isinstance(ck, MKCloudKey):
+        out = eng.mk_bootstrap_tv_multi(np.stack(tables), np.atleast_2d(_samples(samples)), K, index=index, with_keyswitch=with_keyswitch)
+        return [np.ascontiguousarray(out[:, j]) for j in range(K)]
+    out = eng.bootstrap_tv_multi(np.stack(tables), _samples(samples), K, index=index, with_keyswitch=with_keyswitch)
     return [LweSampleArray(np.ascontiguousarray(out[:, j])) for j in range(K)]

@@ -160,17 +160,23 @@ class MKLweSample:
 
 def mk_encrypt(rng, secret_keys, message):
     """mk_api.jl:111-126.  A bool -> flat int32 [P*n+1]; an array of bools -> int32 [B][P*n+1]."""
+    bits = np.atleast_1d(np.asarray(message, bool))
+    mu = np.where(bits, encode_message(1, 8), encode_message(-1, 8)).astype(np.int64)
+    flat = mk_encrypt_torus(rng, secret_keys, mu)
+    return flat[0] if np.ndim(message) == 0 else flat
+
+
+def mk_encrypt_torus(rng, secret_keys, mu):
+    """mk_encrypt of the Torus32 phases mu (int64 [B]) instead of +-1/8: int32 [B][P*n+1] (tfhe_jl_amd.lut: mk_lut_encrypt)."""
     p = secret_keys[0].params
     P, n = len(secret_keys), p.lwe_size
-    bits = np.atleast_1d(np.asarray(message, bool))
-    B = bits.size
-    mu = np.where(bits, encode_message(1, 8), encode_message(-1, 8)).astype(np.int64)
+    mu = np.asarray(mu, np.int64).reshape(-1)
+    B = mu.size
     a = rand_uniform_torus32(rng, B, P, n)
     s = np.stack([sk.key.key for sk in secret_keys]).astype(np.int64)           # [P][n]
     noise = rand_gaussian_torus32(rng, 0, p.lwe_noise_stddev, B).astype(np.int64)
     b = wrap32(mu + noise + np.einsum("bpn,pn->b", a.astype(np.int64), s))
-    flat = np.concatenate([a.reshape(B, P * n), b[:, None]], axis=1).astype(np.int32)
-    return flat[0] if np.ndim(message) == 0 else flat
+    return np.concatenate([a.reshape(B, P * n), b[:, None]], axis=1).astype(np.int32)
 
 
 def mk_phase(secret_keys, flat):

@@ -3,9 +3,12 @@
 object (kernel-side HIP-event times, roofline fraction of the blind-rotate kernel, decrypt check, rounding margin
 and in-kernel clock from the DIAG instantiation of the same kernel).
 
-  python tools/run_config.py --config 1|2host|3|4a|4b|5|k2 [--reps R] [--gates B] [--no-diag]
+  python tools/run_config.py --config 1|2host|3|4a|4b|5|k2|mk4|mk8|mkpbs5|mkpbs4|mkpbs8 [--reps R] [--gates B] [--no-diag]
 
-Also the program profiled for configs 4a / 4b / 5 (tools/profile.sh <tag> tools/run_config.py --config 4a)."""
+Also the program profiled for configs 4a / 4b / 5 / mkpbs5 (tools/profile.sh <tag> tools/run_config.py --config 4a).
+mkpbs5 / mkpbs4 / mkpbs8: multi-key programmable bootstrapping at 2 / 4 / 8 parties (full-size sets), 1024 rows: the TV rotation
+(tfhe_mk_bootstrap_tv_batch) interleaved with the NAND rotation (tfhe_mk_gates_batch) of the same rows, a single lookup against a
+single gate, and the failures of the identity lookup of fresh inputs per message space p = 2, 4, 8."""
 import argparse
 import json
 import os
@@ -77,9 +80,46 @@ def single_key(params, B, reps, seed, want_diag, label):
     return res
 
 
+def mk_pbs(config, B, reps):
+    """Multi-key programmable bootstrapping against the multi-key NAND of the same rows (module docstring)."""
+    from tfhe_jl_amd.lut import make_test_vector, mk_lut_decrypt, mk_lut_encrypt
+    p = {"mkpbs5": tfhe.mktfhe_parameters_2party, "mkpbs4": tfhe.mktfhe_parameters_4party, "mkpbs8": tfhe.mktfhe_parameters_8party}[config]
+    P = 2 if config == "mkpbs5" else p.max_parties
+    mrng = np.random.default_rng(321)
+    sks = [tfhe.SecretKey(mrng, p) for _ in range(P)]
+    shared = tfhe.SharedKey(mrng, p)
+    mck = tfhe.MKCloudKey([tfhe.CloudKeyPart(mrng, s, shared) for s in sks], expand="host" if P == 2 else "device")
+    em = mck.engine(0)
+    apply_options(em)
+    x = tfhe.mk_encrypt(mrng, sks, mrng.integers(0, 2, B).astype(bool))
+    y = tfhe.mk_encrypt(mrng, sks, mrng.integers(0, 2, B).astype(bool))
+    ops = np.zeros(B, np.uint8)
+    tv = make_test_vector(lambda v: v, 2, p.tlwe_polynomial_degree)
+    em.mk_gates_batch(ops, x, y)
+    em.mk_bootstrap_tv(tv, x)
+    nand, lut, nand1, lut1 = [], [], [], []
+    for _ in range(reps):
+        em.mk_gates_batch(ops, x, y); nand.append(em.last_timing_ms(0))
+        em.mk_bootstrap_tv(tv, x); lut.append(em.last_timing_ms(0))
+    kernel = em.last_kernel_name()
+    for _ in range(reps):
+        t0 = time.perf_counter(); em.mk_gates_batch(ops[:1], x[:1], y[:1]); nand1.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); em.mk_bootstrap_tv(tv, x[:1]); lut1.append(time.perf_counter() - t0)
+    fails = {}
+    for q in (2, 4, 8):
+        m = mrng.integers(0, q, B)
+        out = em.mk_bootstrap_tv(make_test_vector(lambda v: v, q, p.tlwe_polynomial_degree), mk_lut_encrypt(mrng, sks, m, q))
+        fails[f"p{q}"] = int((mk_lut_decrypt(sks, out, q) != m).sum())
+    mck.close()
+    return {"config": f"{config}: {P}-party multi-key PBS against NAND", "rows": B, "kernel": kernel,
+            "tv_rotation_ms": float(np.median(lut)), "nand_rotation_ms": float(np.median(nand)),
+            "single_lookup_ms": float(np.median(lut1)) * 1e3, "single_gate_ms": float(np.median(nand1)) * 1e3,
+            "identity_lookup_failures": fails}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", required=True, choices=["1", "2host", "3", "4a", "4b", "5", "k2", "mk4", "mk8"])
+    ap.add_argument("--config", required=True, choices=["1", "2host", "3", "4a", "4b", "5", "k2", "mk4", "mk8", "mkpbs5", "mkpbs4", "mkpbs8"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--gates", type=int, default=0)
     ap.add_argument("--no-diag", action="store_true")
@@ -124,6 +164,8 @@ def main():
                "rotations": rotations, "blind_rotate_ms": eng.last_timing_ms(0), "keyswitch_ms": eng.last_timing_ms(1),
                "rot_per_s": rotations / eng.last_timing_ms(0) * 1e3, "host_wall_ms": wall * 1e3}
         ck.close()
+    elif a.config.startswith("mkpbs"):
+        res = mk_pbs(a.config, a.gates or 1024, max(a.reps, 5))
     elif a.config in ("mk4", "mk8"):   # full-size 4- / 8-party sets (mk_api.jl:16-34), key expanded on the device
         p = tfhe.mktfhe_parameters_4party if a.config == "mk4" else tfhe.mktfhe_parameters_8party
         if a.lwe_size:
