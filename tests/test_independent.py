@@ -20,6 +20,12 @@ Two independent anchors, both written here from the reference's text alone, in e
     w = #{i: s_i = 1} steps:   |phase(extracted) -+ mu|  <=  w (h/2)(1 + |K|)  +  6 sqrt(w (h^2/12)(1 + |K|)).
     (The zero-mean formula sigma^2 = (n/2)(kN/2 + 1) 4^(31 - l beta)/3 misses the first term, which dominates.)  At the
     sizes used here the bound is 2 - 7 % of mu = 2^29; the worst case w h (1 + N) is useless at n = 500 (it exceeds mu).
+
+What is anchored: here, bootstrap(mu, x) with the constant test vector, the single-key gates and mk_gate_nand.  `Schoolbook` also holds
+rotate(v, x) for an arbitrary test polynomial, extract_at(acc, c) and bootstrap_tv, `MKSchoolbook` mk_rotate / mk_extract_at /
+mk_keyswitch / mk_bootstrap_tv / mk_gate (every opcode); bootstrap_wo_keyswitch and mk_gate_nand are written on top of them, so the tests
+of this file guard them.  tests/test_independent_pbs.py uses them to anchor programmable bootstrapping (single- and multi-output), the
+LUT / linear levels, their multi-key forms, the multi-key gate set and the test-only checkers of tests/pbs_ref/.
 """
 import numpy as np
 import pytest
@@ -59,8 +65,14 @@ class Schoolbook:
 
     def __init__(self, n, N, k, l, beta, t, gamma, bk, ks=None):
         self.n, self.N, self.k, self.l, self.beta, self.t, self.gamma = n, N, k, l, beta, t, gamma
+        self._assert_exact((k + 1) * l)                                        # extern_mul sums (k + 1) l products before it wraps
         self.bk = np.asarray(bk, np.int64).reshape(n, l, k + 1, k + 1, N)      # key[i].samples[p, j].a[c]
         self.ks = None if ks is None else np.asarray(ks, np.int64).reshape(k * N, t, (1 << gamma) - 1, n + 1)
+
+    def _assert_exact(self, products):
+        """|digit| <= 2^(beta - 1), |key word| <= 2^31, N terms per coefficient, `products` products summed before a wrap: the
+        int64 sums of extern_mul never overflow."""
+        assert (self.beta - 1) + 31 + (self.N.bit_length() - 1) + (products - 1).bit_length() < 63, (self.beta, self.N, products)
 
     def decode(self, phase, space):                                              # numeric-functions.jl:30-33
         log2 = space.bit_length() - 1
@@ -83,35 +95,63 @@ class Schoolbook:
                     out[c] += negacyclic(d, self.bk[i, p, j, c], N)
         return [wrap32(o) for o in out]
 
-    def bootstrap_wo_keyswitch(self, mu, x):                                     # bootstrap.jl:69-82
+    def modswitch(self, words):                                                  # bootstrap.jl:74-75
+        return [self.decode(v, 2 * self.N) for v in words]
+
+    def rotate(self, v, x):
+        """The final accumulator [(k + 1)][N] of blind_rotate_and_extract (bootstrap.jl:50-57) for an arbitrary Int32 test
+        polynomial v, after the modulus switch of bootstrap_wo_keyswitch (bootstrap.jl:74-75)."""
         n, N, k = self.n, self.N, self.k
-        bara = [self.decode(v, 2 * N) for v in x[:n]]
-        barb = self.decode(x[n], 2 * N)
-        acc = [np.zeros(N, np.int64) for _ in range(k)] + [monomial(np.full(N, mu, np.int64), -barb, N)]
+        bara, barb = self.modswitch(x[:n]), self.decode(x[n], 2 * N)
+        acc = [np.zeros(N, np.int64) for _ in range(k)] + [wrap32(monomial(np.asarray(v, np.int64), -barb, N))]     # bootstrap.jl:54-56
         for i in range(n):                                                       # bootstrap.jl:32-39
             if bara[i] == 0:
                 continue
             temp = [wrap32(monomial(a, bara[i], N) - a) for a in acc]            # bootstrap.jl:21
             prod = self.extern_mul(temp, i)
             acc = [wrap32(a + q) for a, q in zip(acc, prod)]                     # bootstrap.jl:22
-        ext = np.empty(k * N + 1, np.int64)                                      # tlwe.jl:55-59: reverse, then X^(N+1)... = a'[0] = p[0], a'[m] = -p[N-m]
-        for c in range(k):
-            ext[c * N] = acc[c][0]
-            ext[c * N + 1: (c + 1) * N] = -acc[c][:0:-1]
-        ext[k * N] = acc[k][0]
+        return acc
+
+    @staticmethod
+    def extract_mask(p, c):
+        """The N LWE mask words that a mask polynomial p gives to the sample extracted at coefficient c.  The TLWE phase is
+        body - sum_i p_i s_i (tlwe.jl: tlwe_phase); its coefficient c is body[c] - sum_u s[u] (X^u p)[c], so word u is coefficient c
+        of X^u p.  With p extended to the 2N-antiperiodic sequence P[m] (P[m] = p[m], P[m + N] = -p[m]) that is P[(c - u) mod 2N].
+        c = 0 is tlwe_extract_sample's reverse_polynomial (tlwe.jl:55-59, polynomials.jl:32-35): p[0], -p[N-1], ..., -p[1]."""
+        N = len(p)
+        P = np.concatenate([p, -np.asarray(p, np.int64)])
+        return P[(c - np.arange(N)) % (2 * N)]
+
+    def extract_at(self, acc, c):
+        """tlwe_extract_sample (tlwe.jl:55-59) generalised from coefficient 0 to c: [k N + 1]."""
+        k, N = len(acc) - 1, self.N
+        ext = np.empty(k * N + 1, np.int64)
+        for i in range(k):
+            ext[i * N:(i + 1) * N] = self.extract_mask(acc[i], c)
+        ext[k * N] = acc[k][c]
         return wrap32(ext)
 
+    def bootstrap_wo_keyswitch(self, mu, x):                                     # bootstrap.jl:69-82
+        return self.extract_at(self.rotate(np.full(self.N, mu, np.int64), x), 0)
+
     def keyswitch(self, u):                                                      # keyswitch.jl:45-80
-        n, kN, t, gamma = self.n, self.k * self.N, self.t, self.gamma
-        res = np.zeros(n + 1, np.int64)
-        res[n] = u[kN]
-        abar = wrap32(np.asarray(u[:kN], np.int64) + (1 << (32 - (1 + gamma * t))))
-        for i in range(kN):
-            for j in range(1, t + 1):
-                d = (int(abar[i]) >> (32 - j * gamma)) & ((1 << gamma) - 1)
-                if d:
-                    res -= self.ks[i, j - 1, d - 1]
+        return self._keyswitch(u, self.ks, self.k * self.N)
+
+    def _keyswitch(self, u, ks, kN):
+        n, t, gamma = self.n, self.t, self.gamma
+        abar = wrap32(np.asarray(u[:kN], np.int64) + (1 << (32 - (1 + gamma * t))))             # keyswitch.jl:61-62
+        d = (abar[:, None] >> (32 - gamma * np.arange(1, t + 1))) & ((1 << gamma) - 1)           # digit j of word i, keyswitch.jl:66-67
+        i, j = np.nonzero(d)                                                                     # zero digits subtract nothing (:68)
+        res = -ks[i, j, d[i, j] - 1].sum(axis=0)                                                 # < 2^13 rows of |word| <= 2^31: exact
+        res[n] += u[kN]
         return wrap32(res)
+
+    def bootstrap_tv(self, v, x, n_out=1, with_keyswitch=True):
+        """One rotation, n_out samples: sample j is the accumulator extracted at coefficient j N / n_out, keyswitched
+        (bootstrap.jl:92-95) if asked: [n_out][n + 1] or [n_out][k N + 1]."""
+        acc = self.rotate(v, x)
+        ext = [self.extract_at(acc, j * (self.N // n_out)) for j in range(n_out)]
+        return np.stack([self.keyswitch(e) for e in ext] if with_keyswitch else ext)
 
     def bootstrap(self, mu, x):                                                  # bootstrap.jl:92-95
         return self.keyswitch(self.bootstrap_wo_keyswitch(mu, x))
@@ -382,6 +422,7 @@ class MKSchoolbook(Schoolbook):
 
     def __init__(self, n, N, l, beta, t, gamma, parties, bk, ks):
         self.n, self.N, self.k, self.l, self.beta, self.t, self.gamma, self.P = n, N, 1, l, beta, t, gamma, parties
+        self._assert_exact(l * parties + l)                                      # mk_extern_mul sums up to l P + l products before it wraps
         self.mbk = np.asarray(bk, np.int64).reshape(parties, n, 2 * l * parties + 2 * l, N)
         self.mks = np.asarray(ks, np.int64).reshape(parties, N, t, (1 << gamma) - 1, n + 1)
 
@@ -406,32 +447,76 @@ class MKSchoolbook(Schoolbook):
         out.append(wrap32(body))
         return out
 
-    def mk_gate_nand(self, xs, ys):
+    def mk_rotate(self, v, x):
+        """The final accumulator [(P + 1)][N] of mk_blind_rotate_and_extract (mk_internals.jl:488-493) for an arbitrary Int32 test
+        polynomial v, after the modulus switch of mk_bootstrap_wo_keyswitch (:502-503)."""
         n, N, P = self.n, self.N, self.P
-        temp = wrap32(-xs.astype(np.int64) - ys.astype(np.int64))               # mk_gates.jl:8-11
-        temp[P * n] = int(wrap32(temp[P * n] + 2**29))
-        bara = [[self.decode(temp[i * n + j], 2 * N) for j in range(n)] for i in range(P)]
-        barb = self.decode(temp[P * n], 2 * N)
-        acc = [np.zeros(N, np.int64) for _ in range(P)] + [monomial(np.full(N, 2**29, np.int64), -barb, N)]
+        bara = [self.modswitch(x[i * n:(i + 1) * n]) for i in range(P)]
+        barb = self.decode(x[P * n], 2 * N)
+        acc = [np.zeros(N, np.int64) for _ in range(P)] + [wrap32(monomial(np.asarray(v, np.int64), -barb, N))]     # :491-492
         for i in range(P):                                                       # party-major: mk_internals.jl:475-476
             for j in range(n):
-                if bara[i][j] == 0:
+                if bara[i][j] == 0:                                              # :478-480
                     continue
                 rot = [wrap32(monomial(a, bara[i][j], N) - a) for a in acc]      # mk_mux_rotate :464-470
                 prod = self.mk_extern_mul(rot, self.mbk[i, j], i)
                 acc = [wrap32(a + q) for a, q in zip(acc, prod)]
+        return acc
+
+    def mk_extract_at(self, acc, c):
+        """mk_tlwe_extract_sample (mk_internals.jl:88-95) generalised from coefficient 0 to c: one extracted mask column per party,
+        then the body: [P N + 1]."""
+        return self.extract_at(acc, c)                                           # the P party polynomials take the place of the k mask ones
+
+    def mk_keyswitch(self, ext):                                                 # mk_internals.jl:397-411
+        n, N, P = self.n, self.N, self.P
         res = np.zeros(P * n + 1, np.int64)
-        res[P * n] = acc[P][0]                                                   # mk_tlwe_extract_sample :88-95, then mk_keyswitch
+        res[P * n] = ext[P * N]                                                  # mk_lwe_noiseless_trivial(sample.b) (:405)
         for p in range(P):
-            u = np.empty(N + 1, np.int64)
-            u[0] = acc[p][0]
-            u[1:N] = -acc[p][:0:-1]
-            u[N] = 0                                                             # b = 0 per party (:399-401)
-            self.ks, self.k = self.mks[p], 1
-            part = self.keyswitch(wrap32(u))
+            u = np.append(ext[p * N:(p + 1) * N], 0)                             # b = 0 per party (:399-401)
+            part = self._keyswitch(u, self.mks[p], N)
             res[p * n:(p + 1) * n] = part[:n]
-            res[P * n] += part[n]
+            res[P * n] += part[n]                                                # reduce(+, part.b) (:409)
         return wrap32(res)
+
+    def mk_bootstrap_tv(self, v, x, n_out=1, with_keyswitch=True):
+        acc = self.mk_rotate(v, x)
+        ext = [self.mk_extract_at(acc, j * (self.N // n_out)) for j in range(n_out)]
+        return np.stack([self.mk_keyswitch(e) for e in ext] if with_keyswitch else ext)
+
+    def mk_bootstrap_wo_keyswitch(self, mu, x):                                  # mk_internals.jl:498-509
+        return self.mk_extract_at(self.mk_rotate(np.full(self.N, mu, np.int64), x), 0)
+
+    def mk_gate_nand(self, xs, ys):                                              # mk_gates.jl:7-12
+        return self.mk_gate("NAND", xs, ys, None)
+
+    def mk_gate(self, name, x, y=None, z=None):
+        """Every opcode of tfhe_mk_gates_batch on multi-key rows [P n + 1].  mk_gates.jl holds NAND alone (:7-12): the trivial sample
+        of 1/8 minus x minus y, then mk_bootstrap with mu = 1/8.  The other opcodes are gates.jl's forms (the lines _AFFINE cites: the
+        x2 of XOR / XNOR is gates.jl:52 and :64, MUX is gates.jl:163-177) with the same substitution: MKLweSample arithmetic word by
+        word (mk_internals.jl: + / - / * on a and b), mk_bootstrap_wo_keyswitch for bootstrap_wo_keyswitch, mk_keyswitch for keyswitch."""
+        w = self.P * self.n
+        x, y, z = (None if v is None else np.asarray(v, np.int64) for v in (x, y, z))
+        mu = 2**29
+        if name in _AFFINE:
+            const, sx, sy = _AFFINE[name]
+            t = wrap32(sx * x + sy * y)
+            t[w] = wrap32(t[w] + const)
+            return self.mk_keyswitch(self.mk_bootstrap_wo_keyswitch(mu, t))     # mk_bootstrap, mk_internals.jl:512-515
+        if name == "NOT":
+            return wrap32(-x)
+        if name == "COPY":
+            return wrap32(x)
+        if name in ("CONST0", "CONST1"):
+            r = np.zeros(w + 1, np.int64)
+            r[w] = mu if name == "CONST1" else -mu
+            return r
+        assert name == "MUX"                                                     # gates.jl:163-177
+        t1 = wrap32(x + y); t1[w] = wrap32(t1[w] - mu)                           # :166
+        t2 = wrap32(-x + z); t2[w] = wrap32(t2[w] - mu)                          # :170
+        u1, u2 = self.mk_bootstrap_wo_keyswitch(mu, t1), self.mk_bootstrap_wo_keyswitch(mu, t2)
+        t3 = wrap32(u1 + u2); t3[-1] = wrap32(t3[-1] + mu)                       # :174, in the extracted dimension P N + 1
+        return self.mk_keyswitch(t3)                                             # :176: ONE keyswitch
 
 
 def _mk_setup(tfhe, parties, l, beta, n, seed, N=1024, t=8, gamma=2):
