@@ -397,6 +397,44 @@ int32_t tfhe_mk_lut_level(tfhe_ctx *ctx, const int32_t *tv, int32_t n_tv, const 
 int32_t tfhe_mk_linear_level(tfhe_ctx *ctx, const int32_t *term_start, const int32_t *term_wire, const int32_t *term_coef,
                              const int32_t *cst, const int32_t *out, int64_t B);
 
+/* ---- leveled mode: external products and CMUX trees on the caller's own samples (additions within ABI v7) ------------
+ * The blind rotation applies the external product to the bootstrapping key alone.  These entry points apply it to TGSW and TLWE
+ * samples the caller made: a 2^depth-entry table of TLWE samples is folded by depth levels of CMUXes d0 + C (.) (d1 - d0) (the
+ * form of bootstrap.jl:19-23) down to the entry that `depth` TGSW-encrypted address bits name, at 2^depth - 1 external products
+ * and no blind rotation; the result can leave as an LWE sample under the gate key and go into tfhe_gates_batch.
+ * Formats: TLWE sample int32 [k+1][N] = a[0..k-1], b (tlwe.jl:34-41); TGSW sample int32 [l][k+1][k+1][N] = samples[p, j].a[c]
+ * (tgsw.jl:25-32), exactly one entry of the bootstrapping key's canonical form.  One kernel (csrc/kernels_leveled.hpp) serves every
+ * parameter set a context accepts; tfhe_last_kernel_name reports "cmux_level_kernel(N=..,k=..,l=..)".
+ * Exactness: as the rotation, (k+1) l digit-by-selector products are summed in Float64 before the one rounding per coefficient:
+ * "exact_domain" (tfhe_get_option) applies unchanged, with the selector words in the place of the key words.
+ * All three follow the one-caller-at-a-time rule and return TFHE_ERR_STATE on a multi-key context and on a multi-device context
+ * (leveled operations on several devices are out of scope: use one device context per GPU); the two batch calls also with
+ * measure_margin on (no DIAG form of the kernel).  tfhe_last_timing_ms: 0 = the CMUX levels, 1 = the keyswitch, 2 = both. */
+
+/* forward_transform(::TGswSample) (tgsw.jl:120-121) for S samples, host int32 [S][l][k+1][k+1][N]: the selector set the two calls
+ * below index.  Replaces any earlier set (the context is quiesced first).  TFHE_ERR_INVALID_ARG: NULL or S < 1; TFHE_ERR_NOMEM: the
+ * set does not fit the device's free memory (nothing is loaded then). */
+int32_t tfhe_tgsw_load(tfhe_ctx *ctx, const int32_t *tgsw, int64_t S);
+
+/* tgsw_extern_mul(accum, gsw) (tgsw.jl:125-129) for B rows: tlwe_out[g] = selector[sel[g]] (.) tlwe_in[g].  tlwe_in / tlwe_out: host
+ * int32 [B][k+1][N]; sel: host int32 [B] in [0, S).  TFHE_ERR_NO_KEY: no selector set; TFHE_ERR_INVALID_ARG: a selector out of
+ * range (checked before anything is uploaded). */
+int32_t tfhe_extern_mul_batch(tfhe_ctx *ctx, const int32_t *tlwe_in, const int32_t *sel, int32_t *tlwe_out, int64_t B);
+
+/* CMUX tree.  data: host int32 [T][2^depth][k+1][N], T tables shared by the rows; row g folds table table_index[g] (host int32 [B] in
+ * [0, T); NULL = table 0 for every row).  Level v (0 = the lowest address bit) replaces each pair (d0, d1) = entries (2i, 2i + 1)
+ * by d0 + selector[sel[g][v]] (.) (d1 - d0)  (tgsw.jl:99-129, bootstrap.jl:19-23); sel: host int32 [B][depth] in [0, S).  After
+ * depth levels one sample is left, entry sum_v bit_v 2^v of the table when selector sel[g][v] encrypts bit_v.
+ * out_form 0: the TLWE sample, out int32 [B][k+1][N]; 1: tlwe_extract_sample at coefficient 0 (tlwe.jl:55-59), [B][k*N+1];
+ * 2: that keyswitched (keyswitch.jl:45-80), [B][n+1], an LWE sample under the gate key.
+ * Workspace: two device buffers of B 2^(depth-1) and B 2^(depth-2) TLWE samples plus the T tables, grown on demand and kept; the
+ * sizes are compared with the device's free memory BEFORE anything is allocated: TFHE_ERR_NOMEM if they do not fit, the context
+ * stays usable.  TFHE_ERR_INVALID_ARG: NULL buffer, depth outside 1 ... 12, T < 1, out_form outside 0 ... 2, a selector or table index
+ * out of range (all checked in O(B depth) before anything is uploaded); TFHE_ERR_NO_KEY: no selector set, or out_form 2 without
+ * the keyswitch key. */
+int32_t tfhe_cmux_tree_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, const int32_t *table_index, int32_t depth,
+                             const int32_t *sel, int32_t *out, int64_t B, int32_t out_form);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Timing of the most recent batch call on ctx, from HIP events recorded on the stream the kernels

@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -451,6 +451,68 @@ bootstrap_tv(g::GpuCloudKey, tables::AbstractMatrix{Int32}, d::GpuLweArray, inde
 function bootstrap_tv_multi(g::GpuCloudKey, tables::AbstractMatrix{Int32}, d::GpuLweArray, n_out::Integer, index=nothing)
     out = lut_on_device(g, tables, d, n_out, index)          # row g's output j is out[(g - 1) n_out + j]
     [GpuLweArray(g, out[j:n_out:end]) for j in 1:n_out]
+end
+
+"""
+    tgsw_load!(gck, tgsw::Array{Int32})
+
+The selector set of `extern_mul` / `cmux_tree` (tfhe_tgsw_load): `forward_transform(::TGswSample)` (tgsw.jl:120-121) of `S` TGSW
+samples given as Int32 `N x (k+1) x (k+1) x l x S` (column-major: the C layout [S][l][k+1][k+1][N], `samples[p, j].a[c]` of
+tgsw.jl:25-32).  Replaces any earlier set.
+"""
+function tgsw_load!(gck::GpuCloudKey, tgsw::Array{Int32})
+    p = gck.params
+    per = p.tlwe_polynomial_degree * (p.tlwe_mask_size + 1)^2 * p.bs_decomp_length
+    (length(tgsw) > 0 && length(tgsw) % per == 0) || error("tfhe_mi355x: TGSW samples must hold a positive multiple of ", per, " words")
+    GC.@preserve tgsw @locked gck.ctx check(gck.ctx, ccall((:tfhe_tgsw_load, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64), gck.ctx, tgsw, Int64(length(tgsw) ÷ per)))
+    gck
+end
+
+"""
+    extern_mul(gck, tlwe::Array{Int32,3}, sel)  ->  Array{Int32,3}
+
+`tgsw_extern_mul(accum, gsw)` (tgsw.jl:125-129) for a batch (tfhe_extern_mul_batch): sample `g` of `tlwe` (Int32 `N x (k+1) x B`) times
+loaded selector `sel[g]` (1-based).
+"""
+function extern_mul(gck::GpuCloudKey, tlwe::Array{Int32,3}, sel)
+    p = gck.params
+    size(tlwe)[1:2] == (p.tlwe_polynomial_degree, p.tlwe_mask_size + 1) || error("tfhe_mi355x: TLWE samples must be N x (k+1) x B")
+    B = size(tlwe, 3)
+    idx = Int32.(collect(sel) .- 1)
+    length(idx) == B || error("tfhe_mi355x: one selector per sample")
+    out = similar(tlwe)
+    B == 0 && return out
+    GC.@preserve tlwe idx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_extern_mul_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64), gck.ctx, tlwe, idx, out, Int64(B)))
+    out
+end
+
+"""
+    cmux_tree(gck, data::Array{Int32,4}, sel::AbstractMatrix, table_index=nothing; out_form=2)
+
+CMUX-tree lookup (tfhe_cmux_tree_batch): `data` holds `T` tables of `2^depth` TLWE samples (Int32 `N x (k+1) x 2^depth x T`), `sel` is
+`depth x B` (1-based indices into the loaded selectors, row 1 = the lowest address bit), `table_index` 1-based or `nothing` (first
+table).  Every level replaces the pairs `(d0, d1)` by `d0 + C ⊡ (d1 - d0)` (bootstrap.jl:19-23 with tgsw.jl:125-129).  `out_form` 2
+returns `Vector{LweSample}` under the gate key (tlwe.jl:55-59, keyswitch.jl:45-80), 1 the extracted samples of size `k N`, 0 the TLWE
+samples as Int32 `N x (k+1) x B`.
+"""
+function cmux_tree(gck::GpuCloudKey, data::Array{Int32,4}, sel::AbstractMatrix, table_index=nothing; out_form::Integer=2)
+    p = gck.params
+    N, k = p.tlwe_polynomial_degree, p.tlwe_mask_size
+    depth, B = size(sel)
+    1 <= depth <= 12 || error("tfhe_mi355x: depth = ", depth, " (1 ... 12)")
+    size(data)[1:3] == (N, k + 1, 1 << depth) || error("tfhe_mi355x: tables must be N x (k+1) x 2^depth x T")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    s = Matrix{Int32}(sel .- 1)
+    idx = table_index === nothing ? nothing : Int32.(collect(table_index) .- 1)
+    width = out_form == 2 ? p.lwe_size : k * N
+    out = out_form == 0 ? Array{Int32}(undef, N, k + 1, B) : Array{Int32}(undef, width + 1, B)
+    B == 0 && return out_form == 0 ? out : LweSample[]
+    GC.@preserve data s idx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_cmux_tree_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Int32),
+        gck.ctx, data, Int64(size(data, 4)), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), Int32(depth), s, out, Int64(B), Int32(out_form)))
+    out_form == 0 ? out : unflatten(out, LweParams(width))
 end
 
 # page-locked Int32 matrix (tfhe_host_alloc): the copies of a streamed batch are then single DMA transfers that overlap kernels

@@ -17,6 +17,7 @@ from .circuit import Circuit
 from .lut import (lut_encode, lut_decode, lut_encrypt, lut_decrypt, make_test_vector, programmable_bootstrap, make_multi_test_vector,
                   programmable_bootstrap_multi, make_gate_test_vector, GATE_BIT_TO_Z2)
 from .serialize import save_cloud_key, load_cloud_key
+from .leveled import tlwe_encrypt, tlwe_trivial, tlwe_phase, tgsw_encrypt_bits, table_to_tlwe, cmux_lookup
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
 
 __all__ = [
@@ -30,5 +31,6 @@ __all__ = [
     "mk_gate_orny", "mk_gate_oryn", "mk_gate_mux", "mk_gate_not", "mk_gate_constant", "mk_gates_batch",
     "Circuit", "lut_encode", "lut_decode", "lut_encrypt", "lut_decrypt", "make_test_vector", "programmable_bootstrap",
     "make_multi_test_vector", "programmable_bootstrap_multi", "make_gate_test_vector", "GATE_BIT_TO_Z2",
+    "tlwe_encrypt", "tlwe_trivial", "tlwe_phase", "tgsw_encrypt_bits", "table_to_tlwe", "cmux_lookup",
     "save_cloud_key", "load_cloud_key", "Engine", "EngineError", "OPCODES", "LIB_PATH", "pinned_empty",
 ]

@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "tfhe_get_option", "tfhe_ctx_synchronize", "tfhe_mk_gates_batch", "tfhe_mk_wires_alloc", "tfhe_mk_gates_level",
     "tfhe_bootstrap_tv_batch", "tfhe_bootstrap_tv_multi_batch", "tfhe_lut_level", "tfhe_linear_level",
     "tfhe_mk_bootstrap_tv_batch", "tfhe_mk_bootstrap_tv_multi_batch", "tfhe_mk_lut_level", "tfhe_mk_linear_level",
+    "tfhe_tgsw_load", "tfhe_extern_mul_batch", "tfhe_cmux_tree_batch",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -145,6 +146,10 @@ def load():
         lib.tfhe_mk_bootstrap_tv_multi_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, i64, i32]
         lib.tfhe_mk_lut_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64]
         lib.tfhe_mk_linear_level.argtypes = [vp, vp, vp, vp, vp, vp, i64]
+    if hasattr(lib, "tfhe_tgsw_load"):
+        lib.tfhe_tgsw_load.argtypes = [vp, vp, i64]
+        lib.tfhe_extern_mul_batch.argtypes = [vp, vp, vp, vp, i64]
+        lib.tfhe_cmux_tree_batch.argtypes = [vp, vp, i64, vp, i32, vp, vp, i64, i32]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -411,6 +416,51 @@ class Engine:
             raise ValueError("keyswitch input must be [B][k*N+1]")
         out = np.empty((B, self.n + 1), np.int32)
         self._check(self._lib.tfhe_keyswitch_batch(self._h, _ptr(x), _ptr(out), B))
+        return out
+
+    # ---- leveled mode: external products and CMUX trees on the caller's own TGSW / TLWE samples ----
+    def tgsw_load(self, tgsw):
+        """The selector set of extern_mul / cmux_tree (tfhe_tgsw_load): int32 [S][l][k+1][k+1][N], S TGSW samples in the bootstrap
+        key's canonical layout (leveled.tgsw_encrypt_bits makes them).  Replaces any earlier set."""
+        t = _i32c(tgsw)
+        per = self.params.bs_decomp_length * (self.k + 1) ** 2 * self.N
+        if t.size == 0 or t.size % per:
+            raise ValueError(f"TGSW samples have {t.size} words, expected a positive multiple of {per}")
+        self._check(self._lib.tfhe_tgsw_load(self._h, _ptr(t), t.size // per))
+
+    def extern_mul(self, tlwe, sel):
+        """out[g] = selector[sel[g]] (.) tlwe[g] (tfhe_extern_mul_batch; tgsw_extern_mul, tgsw.jl:125-129): int32 [B][k+1][N]."""
+        x = _i32c(tlwe)
+        if x.ndim != 3 or x.shape[1:] != (self.k + 1, self.N):
+            raise ValueError(f"TLWE samples must be [B][{self.k + 1}][{self.N}], got {x.shape}")
+        B = x.shape[0]
+        idx = _i32c(sel).reshape(-1)
+        if idx.size != B:
+            raise ValueError(f"sel must have one entry per row ({B}), got {idx.size}")
+        out = np.empty_like(x)
+        self._check(self._lib.tfhe_extern_mul_batch(self._h, _ptr(x), _ptr(idx), _ptr(out), B))
+        return out
+
+    def cmux_tree(self, data, sel, table_index=None, out_form=2):
+        """CMUX-tree lookup (tfhe_cmux_tree_batch).  data: int32 [T][2^depth][k+1][N] tables of TLWE samples; sel: int32 [B][depth]
+        indices into the loaded selector set, level 0 = the lowest address bit; table_index: [B] or None (table 0).  Row g's
+        result is entry sum_v bit_v 2^v of its table, as a TLWE sample [k+1][N] (out_form 0), extracted at coefficient 0 [k*N+1]
+        (1) or keyswitched to an LWE sample under the gate key [n+1] (2)."""
+        d = _i32c(data)
+        if d.ndim == 3:
+            d = d[None]
+        sel = _i32c(np.atleast_2d(sel))
+        B, depth = sel.shape
+        if d.ndim != 4 or d.shape[1:] != (1 << min(max(depth, 0), 30), self.k + 1, self.N):
+            raise ValueError(f"tables must be [T][2^{depth}][{self.k + 1}][{self.N}], got {d.shape}")
+        idx = None
+        if table_index is not None:
+            idx = _i32c(table_index).reshape(-1)
+            if idx.size != B:
+                raise ValueError(f"table_index must have one entry per row ({B}), got {idx.size}")
+        shape = {0: (B, self.k + 1, self.N), 1: (B, self.k * self.N + 1), 2: (B, self.n + 1)}.get(int(out_form), (0,))
+        out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
+        self._check(self._lib.tfhe_cmux_tree_batch(self._h, _ptr(d), d.shape[0], _ptr(idx), depth, _ptr(sel), _ptr(out), B, int(out_form)))
         return out
 
     # ---- levelised circuits on the device-resident wire table ----

@@ -12,6 +12,7 @@
 //   br_launch.hpp         the launch of each single-key blind-rotation family, compiled by engine_dispatch.hip and engine_tv.hip
 //   engine_mk_tv.hip      the multi-key TV kernels (multi-key programmable bootstrapping) and their launchers     ("mk tv")
 //   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit (-DG2_TV=1: its TV form)
+//   engine_leveled.hip    leveled mode: batched external products and CMUX trees on a caller's TGSW / TLWE samples  ("leveled")
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
 // only under the TFHE_EMIT_* macro of the unit that launches them (templates are instantiated where they are launched).
@@ -185,6 +186,11 @@ struct tfhe_ctx {
     DevBuf bara, ext, map, io[4], diag, abar, mk_acc, spec;
     DevBuf tv, tv_index;           // tfhe_bootstrap_tv_batch: the test polynomials and the table of each row
     DevBuf tv_bodies, tv_ext;      // tfhe_bootstrap_tv_multi_batch: [B][n_out] body coefficients, [B][n_out][kN+1] shifted extractions
+    // leveled mode (engine_leveled.hip): the selector set of tfhe_tgsw_load, [S][l][k+1][k+1][N/2] spectra in the any-N kernels'
+    // order whatever kernel family serves the blind rotation, and the workspaces of the CMUX levels (two ping-pong buffers of
+    // TLWE samples, the uploaded tables, spectrum accumulators that do not fit LDS)
+    cplx *d_tgsw = nullptr;        int64_t tgsw_count = 0;
+    DevBuf lvl_ws[2], lvl_data, lvl_spec;
     size_t diag_rows = 0;
     bool mk_force_general = false; // tfhe_set_option("mk_general", 1): use the any-P kernel for 2 parties too (cross-check)
     int n2048_rw = 0;              // N = 2048: rotations per workgroup advancing in lockstep (tfhe_set_option("n2048_rw", 0|1|2); 0 = one up to
@@ -406,6 +412,8 @@ static int32_t multi_rows(tfhe_ctx *c, int64_t B, F &&call)
 void shard_bounds_by_rotations(const uint8_t *opcodes, int64_t B, int shards, int64_t *bounds);
 // engine_keys.hip
 void quiesce(tfhe_ctx *c);
+// Int32 polynomials -> spectra in the any-N kernels' order, scaled 1/M (forward_transform(::TGswSample), tgsw.jl:120-121), on `s`
+int32_t tgsw_prepare(tfhe_ctx *c, const int32_t *d_polys, cplx *d_out, size_t npolys, hipStream_t s);
 // engine_dispatch.hip
 struct DiagArgs;
 int32_t prepare_diag(tfhe_ctx *c, size_t R, hipStream_t s, DiagArgs &d);

@@ -263,6 +263,56 @@ static int32_t launch_bk_prepare(tfhe_ctx *c, const int32_t *d_polys, cplx *d_ou
     return TFHE_OK;
 }
 
+// The leveled mode's selectors (engine_leveled.hip) are always in the any-N kernels' spectrum order: the CMUX level kernel is built on
+// their transform whatever kernel family serves this context's blind rotation.
+int32_t tgsw_prepare(tfhe_ctx *c, const int32_t *d_polys, cplx *d_out, size_t npolys, hipStream_t s)
+{
+    if (npolys == 0) return TFHE_OK;
+    const int log2N = ilog2i(c->P.N), M = c->P.N / 2;
+    const size_t ldsp = (size_t)anyn::padded_len(M > 0 ? M : 1) * sizeof(cplx);
+    if (ldsp > 64 * 1024) LDS_TRY(c, ldsp, anyn::bk_prepare_kernel);
+    hipLaunchKernelGGL(anyn::bk_prepare_kernel, dim3((unsigned)npolys), dim3((unsigned)anyn::threads_for(c->P.N)), ldsp, s, d_polys, d_out,
+                       (const cplx *)c->d_anyn_tab, (const cplx *)(c->d_anyn_tab + M), log2N, 1.0 / (double)(M > 0 ? M : 1));
+    HIP_TRY(c, hipGetLastError());
+    return TFHE_OK;
+}
+
+// S caller-made TGSW samples as the selector set of tfhe_extern_mul_batch / tfhe_cmux_tree_batch; replaces any earlier set
+int32_t tfhe_tgsw_load(tfhe_ctx *c, const int32_t *tgsw, int64_t S) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    if (!tgsw || S < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "tgsw_load: NULL pointer or no sample");
+    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "tgsw_load: context is multi-key (leveled operations are single-key)");
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "tgsw_load: multi-device context (leveled operations run on a one-device context)");
+    const size_t per = (size_t)c->P.bs_l * (c->P.k + 1) * (c->P.k + 1);
+    if ((double)S * (double)per > 2147483647.0) return c->set_err(TFHE_ERR_INVALID_ARG, "tgsw_load: S = %lld samples are more than one launch prepares", (long long)S);
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int32_t rcp = check_key_source(c, tgsw, "tgsw_load"); if (rcp) return rcp; }
+    const size_t npolys = (size_t)S * per, M = (size_t)(c->P.N / 2 > 0 ? c->P.N / 2 : 1), bytes_in = npolys * (size_t)c->P.N * 4;
+    quiesce(c);
+    if (c->d_tgsw) { (void)hipFree(c->d_tgsw); c->d_tgsw = nullptr; c->tgsw_count = 0; }
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+    if ((double)bytes_in + (double)npolys * (double)M * sizeof(cplx) > (double)free_b)
+        return c->set_err(TFHE_ERR_NOMEM, "tgsw_load: %lld samples do not fit the device's free memory", (long long)S);
+    HIP_TRY(c, hipMalloc((void **)&c->d_tgsw, npolys * M * sizeof(cplx)));
+    void *d_in = nullptr;
+    hipError_t e = hipMalloc(&d_in, bytes_in);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, tgsw, bytes_in, hipMemcpyDefault, c->stream);
+    int32_t rc = TFHE_OK;
+    if (e == hipSuccess) rc = tgsw_prepare(c, (const int32_t *)d_in, c->d_tgsw, npolys, c->stream);
+    if (e == hipSuccess && rc == TFHE_OK) e = hipStreamSynchronize(c->stream);
+    if (d_in) (void)hipFree(d_in);
+    if (e != hipSuccess || rc) {
+        (void)hipFree(c->d_tgsw); c->d_tgsw = nullptr;
+        return rc ? rc : c->set_err(TFHE_ERR_DEVICE, "tgsw_load: %s", hipGetErrorString(e));
+    }
+    c->tgsw_count = S;
+    return TFHE_OK;
+}
+ABI_CATCH(c, "tfhe_tgsw_load")
+
 static int32_t mk_load_bk_common(tfhe_ctx *c, const void *bk, int32_t parties, bool is_c128)
 {
     ENTER_CTX(c);

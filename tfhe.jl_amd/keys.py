@@ -79,6 +79,7 @@ class SecretKey:
         self.params = params
         self.key = LweKey(rng, params.lwe_size)
         self.cloud_keygen_seed = None     # set by CloudKey(keygen="device"): it regenerates the key's noise, so it lives HERE
+        self.tlwe_key = None              # set by CloudKey (both keygen modes): the TLWE key the leveled mode encrypts under (leveled.py)
 
 
 class CloudKey:
@@ -87,6 +88,7 @@ class CloudKey:
     def __init__(self, rng, secret_key: SecretKey, keygen="host", device=0, noise_seed=None):
         """keygen="host": numpy (the reference does this work on the host too); keygen="device": the key material is
         generated on GPU `device` (tfhe_keygen_cloud_key) and the context that made it stays loaded as `engine(device)`.
+        The TLWE key is kept as `secret_key.tlwe_key` (tlwe_encrypt / tgsw_encrypt_bits of leveled.py encrypt under it).
         The TLWE key bits and the two seed words that key the PUBLIC mask streams come from `rng`; the four words (128
         bits) that key the NOISE streams come from the operating system's generator (os.urandom) whatever `rng` is —
         numpy's generators are statistical, not cryptographic, and Philox, which the library expands this secret with, makes
@@ -97,6 +99,7 @@ class CloudKey:
         self.params = p
         self._engines = {}
         tlwe_key = TLweKey(rng, p.tlwe_polynomial_degree, p.tlwe_mask_size)
+        secret_key.tlwe_key = tlwe_key    # secret material stays on the secret side (no draw from rng: the streams are pinned)
         if keygen == "device":
             mask_words = rng.integers(0, 2**32, 2, dtype=np.uint64).astype(np.uint32)
             noise_words = (np.frombuffer(os.urandom(16), dtype=np.uint32) if noise_seed is None
