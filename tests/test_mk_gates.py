@@ -298,3 +298,70 @@ def test_mk_gates_two_devices(orc, tfhe, mk_full, devices):
     eng = K.ck.engine(devices)
     assert np.array_equal(eng.mk_gates_batch(ops, *ins), one)
     assert eng.last_rotation_count() == _rotations(ops)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which,parties,n", [("2party", 2, 24), ("4party", 3, 12)])
+def test_mk_keyswitch_families_agree(orc, tfhe, which, parties, n):
+    """The three keyswitch families under a multi-key keyswitch key, through every multi-key caller of the keyswitch launch.
+    Keyswitching is exact integer arithmetic in all three, so the tiled integer kernel (ks_variant 3) and the gather kernel (1)
+    equal the int8 MFMA default (4, anchored to the references by the tests above) word for word.  Every shipped multi-key set has
+    base 4, t = 8, N = 1024, so each variant really gets its own family.  One engine per variant, the option set before the key
+    is loaded:
+      (a) mk_gates_batch of 19 gates, half of the operand rows encryptions and half arbitrary words: NOT, COPY and CONST1 are
+          trivial, the other 16 fill one 16-sample tile of the tiled kernel; the MUXes take the two-operand (e1) path; with
+          three parties the third chains the body word a second time;
+      (b) the same gates as one mk_gates_level on a multi-key wire table, output wires distinct and in reverse order (dst);
+      (c) mk_bootstrap_tv_multi, 3 rows, n_out = 2, with keyswitch: the source is tv_ext, 6 samples in a partly filled tile;
+      (d) mk_gate_nand of the 19 rows: 19 samples cross the 16-sample tile and leave a partly filled one.
+    (b) equals (a); the NAND rows of (a) and all of (d) equal Oracle.mk_gate_nand."""
+    base = getattr(tfhe, "mktfhe_parameters_" + which)
+    p, rng, sks, ck, o = _mk_setup(tfhe, orc, base, parties, n, seed=130 + parties)
+    w = parties * n + 1
+    names = ["NAND", "MUX", "XOR", "NOT", "COPY", "CONST1", "AND", "NAND", "XOR", "AND",
+             "NAND", "MUX", "XOR", "AND", "NAND", "XOR", "AND", "NAND", "XOR"]
+    ops = np.array([OPS[s] for s in names], np.uint8)
+    B, half = ops.size, 10
+    assert B == 19 and names.count("MUX") == 2
+    ins = []
+    for _ in range(3):
+        enc = tfhe.mk_encrypt(rng, sks, rng.integers(0, 2, half).astype(bool))
+        raw = rng.integers(-2**31, 2**31, size=(B - half, w), dtype=np.int64).astype(np.int32)
+        ins.append(np.concatenate([enc, raw]))
+    ins[0][half, :4] = [2**31 - 1, -2**31, 2**20, 0]
+    tables = rng.integers(-2**31, 2**31, size=(2, 1024), dtype=np.int64).astype(np.int32)
+    tv_rows, tv_index = ins[0][[0, 1, half]], np.array([0, 1, 0], np.int32)
+    out_wires = np.arange(3 * B, 4 * B, dtype=np.int32)[::-1].copy()
+
+    got = {}
+    for variant in (4, 3, 1):
+        eng = tfhe._lib.Engine(p, 0)
+        try:
+            eng.set_option("ks_variant", variant)
+            eng.mk_load_bootstrap_key(ck.bootstrap_key, parties)
+            eng.mk_load_keyswitch_key(ck.keyswitch_key, parties)
+            a = eng.mk_gates_batch(ops, *ins)
+            assert eng.last_rotation_count() == _rotations(ops)
+            eng.mk_wires_alloc(4 * B)
+            eng.wires_upload(0, np.concatenate(ins))
+            idx = np.arange(B, dtype=np.int32)
+            eng.mk_gates_level(ops, idx, idx + B, idx + 2 * B, out_wires)
+            b = eng.wires_gather(out_wires)
+            c = eng.mk_bootstrap_tv_multi(tables, tv_rows, 2, tv_index, with_keyswitch=True)
+            d = eng.mk_gate_nand(ins[0], ins[1])
+            got[variant] = (a, b, c, d)
+        finally:
+            eng.close()
+    ck.close()
+
+    for variant in (3, 1):
+        for part, x, y in zip("abcd", got[variant], got[4]):
+            assert x.shape == y.shape and np.array_equal(x, y), (variant, part)
+    a, b, c, d = got[4]
+    assert c.shape == (3, 2, w)
+    assert np.array_equal(b, a)
+    nand = np.flatnonzero(ops == OPS["NAND"])
+    assert nand.size == 5
+    want = o.mk_gate_nand(ins[0], ins[1])
+    assert np.array_equal(a[nand], want[nand])
+    assert np.array_equal(d, want)

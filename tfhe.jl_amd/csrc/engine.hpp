@@ -2,8 +2,8 @@
 // declarations of the functions one section calls in another.  C ABI: include/tfhe_mi355x.h.
 //
 //   engine_context.hip    create / destroy, tables, sharding rule, host memory, last error            ("context")
-//   engine_keys.hip       bootstrapping / keyswitch key loaders, device keygen, RGSW.Expand            ("keys")
-//   engine_dispatch.hip   which blind-rotate / keyswitch kernel a batch takes, and its launch          ("dispatch")
+//   engine_keys.hip       bootstrapping / keyswitch key loaders (the keyswitch key record: KsKey below), device keygen, RGSW.Expand   ("keys")
+//   engine_dispatch.hip   which blind-rotate kernel a batch takes and its launch; launch_keyswitch, single- and multi-key   ("dispatch")
 //   engine_gates.hip      tfhe_gates_batch*, tfhe_bootstrap_batch, tfhe_keyswitch_batch, streaming     ("gates")
 //   engine_circuits.hip   wire table, tfhe_gates_level, rows between the devices of a context         ("circuits")
 //   engine_multikey.hip   tfhe_mk_gate_nand_batch, tfhe_mk_gates_batch and their kernels              ("multi-key")
@@ -106,6 +106,27 @@ struct PairXfer {
     unsigned next = 0;
 };
 
+// The keyswitch key of a context: ONE key, single-key (tfhe_load_keyswitch_key) or multi-key (tfhe_mk_load_keyswitch_key: the
+// parties' keys back to back), resident in the one layout its kernel family reads.  The loaders fill it, launch_keyswitch reads
+// it, release() frees it; a twin context holds a copy that it does not own (borrows_keys).
+struct KsKey {
+    int mode = 0;             // kernel family the key was laid out for (decided at load: pick_ks_mode); 0: no key loaded
+                              //   1 = gather: int32 [parties][kN][t][base-1][n+1], the canonical layout
+                              //   3 = tiled integer VALU: the same with every row padded to `stride` words
+                              //   4 = int8 MFMA (base 4, t = 8): i32x4 B fragments [parties][kN][wtiles][4 planes][64 lanes]
+    int parties = 1;          // 1: single-key
+    int kN = 0;               // mask words per party: k N single-key, N multi-key
+    void *p = nullptr;        // the resident layout
+    size_t per_party = 0;     // one party's share of p: words (modes 1, 3) or fragments (mode 4)
+    int stride = 0;           // mode 3: words per padded row (n + 1 rounded up to 4)
+    int wtiles = 0;           // mode 4: tiles of 32 output words
+};
+inline void release(KsKey &k)
+{
+    if (k.p) (void)hipFree(k.p);
+    k = KsKey{};
+}
+
 struct tfhe_ctx {
     tfhe_params P{};
     int device = 0;
@@ -128,7 +149,6 @@ struct tfhe_ctx {
     std::string last_kernel;             // blind-rotate kernel instantiation the last batch call launched
     int ks_slices_large = 2;     // K-split of the MFMA keyswitch for large batches (tfhe_set_option("ks_slices", 1|2|4))
     int ks_variant = 4;          // 1 = one workgroup per sample, 3 = tiled + sliced + XCD-aware integer VALU, 4 = int8 MFMA (default)
-    int ks_mode = 0;             // kernel family the loaded keyswitch key was laid out for (decided at load: pick_ks_mode)
     int64_t br_small = 1024;     // batches of at most this many rotations use the two-waves-per-rotation kernel (-1: never): what the chip holds at two waves per SIMD, 4 per CU (set at creation: 1024 on 256 CUs)
     int br_prio_pct = 90;        // a wave of the batched kernels lowers its issue priority 3 -> 0 over this share of its steps (0: off)
     int br_general = 0;          // tfhe_set_option("br_general", 1): every single-key blind rotation on blind_rotate_kernel_general (cross-check of the specialised kernels)
@@ -161,20 +181,16 @@ struct tfhe_ctx {
     // N = 512 with k = 1 (any l) has a tuned kernel of its own (kernels_n512.hpp) and its own key order
     bool n512() const { return !br_anyn && P.parties == 1 && P.N == 512 && P.k == 1; }
 
-    // keys (only the layout of the selected keyswitch kernel family stays resident)
+    // keys (only the layout of the selected keyswitch kernel family stays resident: KsKey)
     cplx *d_bk = nullptr;       size_t bk_polys = 0;
-    int32_t *d_ks = nullptr;    // canonical [kN][t][base-1][n+1]                   (ks_mode 1)
-    int32_t *d_ksp = nullptr;   int ks_stride = 0;   // row-padded copy             (ks_mode 3)
-    void *d_ks4 = nullptr;      int ks4_wtiles = 0;  // MFMA B fragments            (ks_mode 4: base 4, t = 8)
-    void *d_mk_ks4 = nullptr;   size_t mk_ks4_frags = 0;
-    bool have_bk = false, have_ks = false;
+    KsKey ks;                      // the one keyswitch key of the context, single- or multi-key
+    bool have_bk = false;
+    bool have_ks() const { return ks.mode != 0 && ks.parties == 1; }
     // multi-key
     cplx *d_mk_bk = nullptr;
-    int32_t *d_mk_ksp = nullptr;   // [P] row-padded keyswitch keys back to back
-    size_t mk_ksp_words = 0;       // words per party in d_mk_ksp
-    int mk_parties = 0;            // parties of the loaded multi-key bootstrapping key
-    int mk_ks_parties = 0;         // ... and of the loaded multi-key keyswitch key (tfhe_mk_gate_nand_batch needs them equal)
-    bool have_mk_bk = false, have_mk_ks = false;
+    int mk_parties = 0;            // parties of the loaded multi-key bootstrapping key (the keyswitch key's: ks.parties; the gates need them equal)
+    bool have_mk_bk = false;
+    bool have_mk_ks() const { return ks.mode != 0 && ks.parties > 1; }
 
     // device-resident wire table for levelised circuits: int32 [num_wires][n+1], or [num_wires][P n+1] for a multi-key table
     // (tfhe_mk_wires_alloc: wires_parties = P, fixed when the table is allocated; 0 = single-key rows)
@@ -435,9 +451,8 @@ static WithTv<A> with_tv(const A &a, const TvPtrs &tv)
     return t;
 }
 int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, const TvPtrs *tv = nullptr);
+// the keyswitch of G samples under the context's key (c->ks), single- or multi-key
 int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out, hipStream_t s);
-int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out,
-                            hipStream_t s);
 // engine_gates.hip
 int32_t enter_stream(tfhe_ctx *c, hipStream_t s);
 int32_t leave_stream(tfhe_ctx *c, hipStream_t s);

@@ -364,10 +364,10 @@ int32_t tfhe_mk_gates_level(tfhe_ctx *c, const uint8_t *opcodes, const int32_t *
     if (c->P.parties == 1) return c->set_err(TFHE_ERR_STATE, "mk_gates_level: context is single-key");
     if (!c->d_wires) return c->set_err(TFHE_ERR_STATE, "mk_gates_level: no wire table allocated");
     if (!c->wires_parties) return c->set_err(TFHE_ERR_STATE, "mk_gates_level: the wire table has single-key rows (tfhe_wires_alloc): allocate it with tfhe_mk_wires_alloc");
-    if (!c->have_mk_bk || !c->have_mk_ks) return c->set_err(TFHE_ERR_NO_KEY, "mk_gates_level: multi-key keys not loaded");
-    if (c->mk_parties != c->wires_parties || c->mk_ks_parties != c->mk_parties)
+    if (!c->have_mk_bk || !c->have_mk_ks()) return c->set_err(TFHE_ERR_NO_KEY, "mk_gates_level: multi-key keys not loaded");
+    if (c->mk_parties != c->wires_parties || c->ks.parties != c->mk_parties)
         return c->set_err(TFHE_ERR_STATE, "mk_gates_level: the wire table has rows for %d parties, the keys loaded now are for %d (bootstrapping) / %d (keyswitch)",
-                          c->wires_parties, c->mk_parties, c->mk_ks_parties);
+                          c->wires_parties, c->mk_parties, c->ks.parties);
     { const int32_t rcv = validate_level(c, c->num_wires, opcodes, a, b, cc, out, B); if (rcv) return rcv; }
     HIP_TRY(c, hipSetDevice(c->device));
     return run_mk_gates(c, "mk_gates_level", opcodes, B, c->d_wires, c->d_wires, c->d_wires, c->d_wires, a ? a : out, b ? b : out, cc ? cc : out, out,
@@ -468,13 +468,13 @@ static int32_t int_level(tfhe_ctx *c, const char *who, bool mk, const IntLevel &
         return c->set_err(TFHE_ERR_STATE, "%s: the wire table has single-key rows (tfhe_wires_alloc): allocate it with tfhe_mk_wires_alloc", who);
     const tfhe_ctx *dev0 = c->multi() ? c->kids[0] : c;        // (options and keys are the same on every device of a context)
     if (lut && dev0->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the TV kernels have no DIAG instantiation)", who);
-    if (mk && lut && (c->mk_parties != c->wires_parties || c->mk_ks_parties != c->mk_parties))
+    if (mk && lut && (c->mk_parties != c->wires_parties || c->ks.parties != c->mk_parties))
         return c->set_err(TFHE_ERR_STATE, "%s: the wire table holds %d-party rows, the bootstrapping key is for %d parties and the keyswitch key for %d",
-                          who, c->wires_parties, c->mk_parties, c->mk_ks_parties);
+                          who, c->wires_parties, c->mk_parties, c->ks.parties);
     if (L.B == 0) return TFHE_OK;
     { const int32_t rcv = validate_int_level(c, who, c->num_wires, c->P.N, L); if (rcv) return rcv; }
-    if (!mk && lut && (!dev0->have_bk || !dev0->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: bootstrapping/keyswitch key not loaded", who);
-    if (mk && lut && (!c->have_mk_bk || !c->have_mk_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
+    if (!mk && lut && (!dev0->have_bk || !dev0->have_ks())) return c->set_err(TFHE_ERR_NO_KEY, "%s: bootstrapping/keyswitch key not loaded", who);
+    if (mk && lut && (!c->have_mk_bk || !c->have_mk_ks())) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
     if (c->multi()) return multi_int_level(c, L);
     HIP_TRY(c, hipSetDevice(c->device));
     return run_int_level(c, L);

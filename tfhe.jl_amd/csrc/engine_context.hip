@@ -315,15 +315,11 @@ void tfhe_ctx_destroy(tfhe_ctx *c)
     if (c->done_pending && c->done_ev) (void)hipEventSynchronize(c->done_ev);      // a call still running on a caller's stream
     if (c->d_tables) (void)hipFree(c->d_tables);
     if (c->d_anyn_tab) (void)hipFree(c->d_anyn_tab);
-    if (c->borrows_keys) c->d_bk = nullptr, c->d_ks = nullptr, c->d_ksp = nullptr, c->d_ks4 = nullptr;      // the owner frees them
+    if (c->borrows_keys) c->d_bk = nullptr, c->ks = KsKey{};      // the owner frees them
     if (c->d_bk) (void)hipFree(c->d_bk);
-    if (c->d_ks) (void)hipFree(c->d_ks);
-    if (c->d_ksp) (void)hipFree(c->d_ksp);
-    if (c->d_ks4) (void)hipFree(c->d_ks4);
+    release(c->ks);
     if (c->d_wires) (void)hipFree(c->d_wires);
-    if (c->d_mk_ks4) (void)hipFree(c->d_mk_ks4);
     if (c->d_mk_bk) (void)hipFree(c->d_mk_bk);
-    if (c->d_mk_ksp) (void)hipFree(c->d_mk_ksp);
     if (c->d_tgsw) (void)hipFree(c->d_tgsw);
     c->lvl_ws[0].release(); c->lvl_ws[1].release(); c->lvl_data.release(); c->lvl_spec.release();
     c->bara.release(); c->ext.release(); c->map.release(); c->diag.release(); c->abar.release(); c->mk_acc.release(); c->spec.release(); c->tv.release(); c->tv_index.release(); c->tv_bodies.release(); c->tv_ext.release();

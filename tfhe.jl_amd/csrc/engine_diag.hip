@@ -359,7 +359,7 @@ int32_t tfhe_set_option(tfhe_ctx *c, const char *name, int64_t value) try
     if (!strcmp(name, "ks_variant")) {
         if (value != 1 && value != 3 && value != 4) return c->set_err(TFHE_ERR_INVALID_ARG, "set_option: ks_variant must be 1, 3 or 4");
         // only the selected family's key layout is kept on the device: choose before loading the keyswitch key
-        if ((c->have_ks || c->have_mk_ks) && (int)value != c->ks_variant)
+        if (c->ks.mode != 0 && (int)value != c->ks_variant)
             return c->set_err(TFHE_ERR_STATE, "set_option: ks_variant must be chosen before the keyswitch key is loaded (reload the key after changing it)");
         c->ks_variant = (int)value;
         return TFHE_OK;

@@ -1,4 +1,5 @@
-// engine_dispatch.hip — dispatch: which blind-rotate / keyswitch kernel a batch takes (by parameter set and batch size) and its launch
+// engine_dispatch.hip — dispatch: which blind-rotate kernel a batch takes (by parameter set and batch size) and its launch; the one
+// keyswitch launch of every caller, single- and multi-key (launch_keyswitch, on the family the loaded key was laid out for)
 #define TFHE_EMIT_KEYSWITCH_KERNELS
 #include "engine.hpp"
 #include "br_launch.hpp"
@@ -347,101 +348,64 @@ int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, co
     return TFHE_OK;
 }
 
-int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst,
-                                const int32_t *ext, int32_t *out, hipStream_t s)
+// The keyswitch of G samples under the context's key (c->ks; keyswitch.jl:45-80, mk_keyswitch: mk_internals.jl:397-411).  ext = the
+// extracted samples, [R][P kN + 1] (the context's ext, or tv_ext for a multi-output TV batch), out: [.][P n + 1], P = the key's
+// parties.  Sample g is ext[e0[g]] (+ ext[e1[g]] + (0, 1/8) for MUX, gates.jl:174) written to row dst[g] (e1, dst NULL: no second
+// operand, identity).  Party p is a single-key keyswitch of its mask column [p kN, (p+1) kN) into [p n, (p+1) n); the b word enters
+// once, with party 0, and is chained through the output by the others (stream-ordered).  A single key is P = 1, kN = k N.
+template <class A>
+static A ks_args(const tfhe_ctx *c, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out)
 {
-    KsArgs k;
-    k.ext = ext;
-    k.ks = c->d_ks;
-    k.e0 = e0; k.e1 = e1; k.dst = dst;
-    k.out = out;
-    k.n = c->P.n; k.kN = c->P.k * c->P.N; k.t = c->P.ks_t; k.log2_base = c->P.ks_log2_base;
-    const int n1 = c->P.n + 1;
-    k.in_stride = k.kN + 1; k.in_off = 0; k.in_b = k.kN; k.out_stride = n1; k.out_off = 0; k.out_b = c->P.n; k.add_b = 1;
-    if (c->ks_mode == 4) {
-        Ks4Args a4;
-        a4.ext = ext; a4.bmat = (const i32x4 *)c->d_ks4; a4.e0 = e0; a4.e1 = e1; a4.dst = dst; a4.out = out;
-        a4.n = c->P.n; a4.kN = k.kN; a4.G = (int)G; a4.wtiles = c->ks4_wtiles;
-        a4.in_stride = k.kN + 1; a4.in_off = 0; a4.in_b = k.kN; a4.out_stride = n1; a4.out_off = 0; a4.out_b = c->P.n; a4.add_b = 1;
-        // split the mask words over several blocks, partial sums combined with exact integer atomics: 16 slices for
-        // small batches (latency), 2 for large ones (two waves per SIMD so that one wave's MFMAs overlap the other's
-        // A-fragment generation and LDS reads)
-        a4.kslices = (k.kN % 512 != 0) ? 1 : (G <= 512 ? 16 : c->ks_slices_large);
-        if (a4.kslices > 1) {
-            Ks3Args i3;
-            i3.ext = ext; i3.e0 = e0; i3.e1 = e1; i3.dst = dst; i3.out = out; i3.kN = k.kN; i3.n = c->P.n;
-            i3.in_stride = a4.in_stride; i3.in_b = a4.in_b; i3.out_stride = n1; i3.out_b = c->P.n;
-            hipLaunchKernelGGL(ks3_init_kernel, dim3((unsigned)G), dim3(256), 0, s, i3);
-        }
-        a4.Gpad = (int)((G + 63) / 64 * 64);
-        HIP_TRY(c, c->abar.reserve((size_t)(k.kN / 4) * a4.Gpad * 16));
-        a4.abar_t = (const i32x4 *)c->abar.p;
-        hipLaunchKernelGGL(ks4_digits_kernel, dim3((unsigned)(a4.Gpad / 32), (unsigned)(k.kN / 128)), dim3(128), 0, s, a4, (i32x4 *)c->abar.p);
-        hipLaunchKernelGGL(keyswitch_kernel_v4, dim3((unsigned)((G + 255) / 256), (unsigned)c->ks4_wtiles, (unsigned)a4.kslices), dim3(256), 0, s, a4);
-        HIP_TRY(c, hipGetLastError());
-        return TFHE_OK;
-    }
-    if (c->ks_mode == 3) {
-        Ks3Args a3;
-        a3.ext = ext; a3.ksp = c->d_ksp; a3.e0 = e0; a3.e1 = e1; a3.dst = dst; a3.out = out;
-        a3.n = c->P.n; a3.kN = k.kN; a3.t = c->P.ks_t; a3.log2_base = 2; a3.stride = c->ks_stride; a3.G = (int)G;
-        a3.in_stride = k.kN + 1; a3.in_off = 0; a3.in_b = k.kN; a3.out_stride = n1; a3.out_off = 0; a3.out_b = c->P.n;
-        hipLaunchKernelGGL(ks3_init_kernel, dim3((unsigned)G), dim3(256), 0, s, a3);
-        const unsigned tiles = (unsigned)((G + KS3_G - 1) / KS3_G);
-        hipLaunchKernelGGL(keyswitch_kernel_v3, dim3(tiles * KS3_SLICES, (unsigned)((c->ks_stride + 511) / 512)), dim3(128), 0, s, a3);
-        HIP_TRY(c, hipGetLastError());
-        return TFHE_OK;
-    }
-    hipLaunchKernelGGL(keyswitch_kernel, dim3((unsigned)G, (unsigned)((n1 + 256 * KS1_WPT - 1) / (256 * KS1_WPT))), dim3(256), 0, s, k);     // any base, t, n
-    HIP_TRY(c, hipGetLastError());
-    return TFHE_OK;
+    const int P = c->ks.parties, kN = c->ks.kN, n = c->P.n;
+    A a{};                       // (value-initialised: every launch passes defined bytes, whatever fields its kernel reads)
+    a.ext = ext; a.e0 = e0; a.e1 = e1; a.dst = dst; a.out = out;
+    a.n = n; a.kN = kN;
+    a.in_stride = P * kN + 1; a.in_off = 0; a.in_b = P * kN; a.out_stride = P * n + 1; a.out_off = 0; a.out_b = P * n;
+    return a;
 }
 
-// mk_keyswitch (mk_internals.jl:397-411): per party a single-key keyswitch of its mask column with b = 0, the b words chained
-// through the output (stream-ordered).  ext = the extracted samples [R][P N + 1] (the context's ext, or tv_ext for a multi-output
-// TV batch), out: [.][P n + 1].  Sample g is
-// ext[e0[g]] (+ ext[e1[g]] + (0, 1/8) for MUX, gates.jl:174: the b part enters once, with party 0) written to row dst[g]
-// (e1, dst NULL: no second operand, identity), as launch_keyswitch.
-int32_t launch_mk_keyswitch(tfhe_ctx *c, size_t B, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out,
-                            hipStream_t s)
+int32_t launch_keyswitch(tfhe_ctx *c, size_t G, const int32_t *e0, const int32_t *e1, const int32_t *dst, const int32_t *ext, int32_t *out, hipStream_t s)
 {
-    const int NP = c->mk_parties, n = c->P.n, nw = NP * n + 1, Nn = c->P.N, ew = NP * Nn + 1;
-    if (c->ks_mode == 4) {
-        Ks4Args a4;
-        a4.ext = ext; a4.e0 = e0; a4.e1 = e1; a4.dst = dst; a4.out = out;
-        a4.n = n; a4.kN = Nn; a4.G = (int)B; a4.wtiles = c->ks4_wtiles;
-        a4.in_stride = ew; a4.in_b = NP * Nn; a4.out_stride = nw; a4.out_b = NP * n;
-        for (int p = 0; p < NP; p++) {
-            a4.in_off = p * Nn; a4.out_off = p * n; a4.add_b = (p == 0); a4.kslices = 1;
-            a4.Gpad = (int)((B + 63) / 64 * 64);
-            HIP_TRY(c, c->abar.reserve((size_t)(Nn / 4) * a4.Gpad * 16));
-            a4.abar_t = (const i32x4 *)c->abar.p;
-            hipLaunchKernelGGL(ks4_digits_kernel, dim3((unsigned)(a4.Gpad / 32), (unsigned)(Nn / 128)), dim3(128), 0, s, a4, (i32x4 *)c->abar.p);
-            a4.bmat = (const i32x4 *)c->d_mk_ks4 + (size_t)p * c->mk_ks4_frags;
-            hipLaunchKernelGGL(keyswitch_kernel_v4, dim3((unsigned)((B + 255) / 256), (unsigned)c->ks4_wtiles), dim3(256), 0, s, a4);
+    const KsKey &K = c->ks;
+    const int P = K.parties, kN = K.kN, n = c->P.n;
+    if (K.mode == 4) {
+        Ks4Args a = ks_args<Ks4Args>(c, e0, e1, dst, ext, out);
+        a.G = (int)G; a.wtiles = K.wtiles;
+        // a single key splits the mask words over several blocks, partial sums combined with exact integer atomics: 16 slices for
+        // small batches (latency), 2 for large ones (two waves per SIMD so that one wave's MFMAs overlap the other's
+        // A-fragment generation and LDS reads); the parties of a multi-key key chain their b words, unsliced
+        a.kslices = (P > 1 || kN % 512 != 0) ? 1 : (G <= 512 ? 16 : c->ks_slices_large);
+        if (a.kslices > 1) {
+            const Ks3Args i3 = ks_args<Ks3Args>(c, e0, e1, dst, ext, out);
+            hipLaunchKernelGGL(ks3_init_kernel, dim3((unsigned)G), dim3(256), 0, s, i3);
         }
-    } else if (c->ks_mode == 1) {
-        // any base / length: the gather kernel per party
-        KsArgs k1;
-        k1.ext = ext; k1.e0 = e0; k1.e1 = e1; k1.dst = dst; k1.out = out;
-        k1.n = n; k1.kN = c->P.N; k1.t = c->P.ks_t; k1.log2_base = c->P.ks_log2_base;
-        k1.in_stride = ew; k1.in_b = NP * c->P.N; k1.out_stride = nw; k1.out_b = NP * n;
-        for (int p = 0; p < NP; p++) {
-            k1.in_off = p * c->P.N; k1.out_off = p * n; k1.add_b = (p == 0);
-            k1.ks = c->d_ks + (size_t)p * c->mk_ksp_words;
-            hipLaunchKernelGGL(keyswitch_kernel, dim3((unsigned)B, (unsigned)((n + 1 + 256 * KS1_WPT - 1) / (256 * KS1_WPT))), dim3(256), 0, s, k1);
+        a.Gpad = (int)((G + 63) / 64 * 64);
+        HIP_TRY(c, c->abar.reserve((size_t)(kN / 4) * a.Gpad * 16));
+        a.abar_t = (const i32x4 *)c->abar.p;
+        for (int p = 0; p < P; p++) {
+            a.in_off = p * kN; a.out_off = p * n; a.add_b = (p == 0);
+            a.bmat = (const i32x4 *)K.p + (size_t)p * K.per_party;
+            hipLaunchKernelGGL(ks4_digits_kernel, dim3((unsigned)(a.Gpad / 32), (unsigned)(kN / 128)), dim3(128), 0, s, a, (i32x4 *)c->abar.p);
+            hipLaunchKernelGGL(keyswitch_kernel_v4, dim3((unsigned)((G + 255) / 256), (unsigned)K.wtiles, (unsigned)a.kslices), dim3(256), 0, s, a);
         }
-    } else {
-        Ks3Args k3;
-        k3.ext = ext; k3.e0 = e0; k3.e1 = e1; k3.dst = dst; k3.out = out;
-        k3.n = n; k3.kN = Nn; k3.t = c->P.ks_t; k3.log2_base = 2; k3.stride = c->ks_stride; k3.G = (int)B;
-        k3.in_stride = ew; k3.in_b = NP * Nn; k3.out_stride = nw; k3.out_b = NP * n;
-        k3.in_off = 0; k3.out_off = 0; k3.ksp = c->d_mk_ksp;
-        hipLaunchKernelGGL(ks3_init_kernel, dim3((unsigned)B), dim3(256), 0, s, k3);
-        const unsigned tiles = (unsigned)((B + KS3_G - 1) / KS3_G);
-        for (int p = 0; p < NP; p++) {
-            k3.in_off = p * Nn; k3.out_off = p * n; k3.ksp = c->d_mk_ksp + (size_t)p * c->mk_ksp_words;
-            hipLaunchKernelGGL(keyswitch_kernel_v3, dim3(tiles * KS3_SLICES, (unsigned)((c->ks_stride + 511) / 512)), dim3(128), 0, s, k3);
+    } else if (K.mode == 3) {
+        Ks3Args a = ks_args<Ks3Args>(c, e0, e1, dst, ext, out);
+        a.t = c->P.ks_t; a.log2_base = 2; a.stride = K.stride; a.G = (int)G;
+        a.ksp = (const int32_t *)K.p;
+        hipLaunchKernelGGL(ks3_init_kernel, dim3((unsigned)G), dim3(256), 0, s, a);
+        const unsigned tiles = (unsigned)((G + KS3_G - 1) / KS3_G);
+        for (int p = 0; p < P; p++) {
+            a.in_off = p * kN; a.out_off = p * n;
+            a.ksp = (const int32_t *)K.p + (size_t)p * K.per_party;
+            hipLaunchKernelGGL(keyswitch_kernel_v3, dim3(tiles * KS3_SLICES, (unsigned)((K.stride + 511) / 512)), dim3(128), 0, s, a);
+        }
+    } else {      // any base, t, n: the gather kernel
+        KsArgs a = ks_args<KsArgs>(c, e0, e1, dst, ext, out);
+        a.t = c->P.ks_t; a.log2_base = c->P.ks_log2_base;
+        for (int p = 0; p < P; p++) {
+            a.in_off = p * kN; a.out_off = p * n; a.add_b = (p == 0);
+            a.ks = (const int32_t *)K.p + (size_t)p * K.per_party;
+            hipLaunchKernelGGL(keyswitch_kernel, dim3((unsigned)G, (unsigned)((n + 1 + 256 * KS1_WPT - 1) / (256 * KS1_WPT))), dim3(256), 0, s, a);
         }
     }
     HIP_TRY(c, hipGetLastError());

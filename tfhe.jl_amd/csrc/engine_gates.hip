@@ -99,7 +99,7 @@ int32_t run_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t 
     }
     if ((need0 && !d_in0) || (need1 && !d_in1) || (need2 && !d_in2))
         return c->set_err(TFHE_ERR_INVALID_ARG, "%s: an operand array required by the opcodes is NULL", who);
-    if (R > 0 && (!c->have_bk || !c->have_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: bootstrapping/keyswitch key not loaded", who);
+    if (R > 0 && (!c->have_bk || !c->have_ks())) return c->set_err(TFHE_ERR_NO_KEY, "%s: bootstrapping/keyswitch key not loaded", who);
     {
         const int32_t rc0 = enter_stream(c, s);
         if (rc0) return rc0;
@@ -262,8 +262,7 @@ static int32_t ensure_twin(tfhe_ctx *c)
         c->twin_stream.store(t->stream, std::memory_order_release);
     }
     tfhe_ctx *t = c->twin;
-    t->d_bk = c->d_bk; t->bk_polys = c->bk_polys; t->d_ks = c->d_ks; t->d_ksp = c->d_ksp; t->ks_stride = c->ks_stride;
-    t->d_ks4 = c->d_ks4; t->ks4_wtiles = c->ks4_wtiles; t->ks_mode = c->ks_mode; t->have_bk = c->have_bk; t->have_ks = c->have_ks;
+    t->d_bk = c->d_bk; t->bk_polys = c->bk_polys; t->have_bk = c->have_bk; t->ks = c->ks;
     t->ks_slices_large = c->ks_slices_large; t->ks_variant = c->ks_variant; t->br_small = c->br_small; t->br_prio_pct = c->br_prio_pct;
     t->br_tiny = c->br_tiny; t->br_rt_l = c->br_rt_l; t->timing_events = c->timing_events; t->br_split = c->br_split; t->br_general = c->br_general; t->n2048_rw = c->n2048_rw; t->v3_rw = c->v3_rw; t->k2_rw = c->k2_rw; t->w2_rw = c->w2_rw;
     t->br_anyn = c->br_anyn; t->anyn_spec = c->anyn_spec; t->k2_w3 = c->k2_w3; t->n512_rw = c->n512_rw; t->n512_w2 = c->n512_w2;
@@ -310,7 +309,7 @@ int32_t tfhe_gates_batch(tfhe_ctx *c, const uint8_t *opcodes, const int32_t *in0
     if ((need[0] && !in0) || (need[1] && !in1) || (need[2] && !in2))
         return c->set_err(TFHE_ERR_INVALID_ARG, "gates_batch: an operand array required by the opcodes is NULL");
     if (c->pipeline_min >= 0 && B >= c->pipeline_min && B >= 2 && !c->borrows_keys && !c->measure_margin && c->P.parties == 1 &&
-        c->have_bk && c->have_ks) {
+        c->have_bk && c->have_ks()) {
         // two halves, two streams: [upload B | compute A] then [compute B | download A] overlap
         int64_t bounds[3];
         shard_bounds_by_rotations(opcodes, B, 2, bounds);
@@ -439,7 +438,7 @@ int32_t tfhe_gates_batch_submit(tfhe_ctx *c, const uint8_t *opcodes, const int32
         return TFHE_OK;
     }
     // contexts that cannot run two batches side by side (multi-key, diagnostics, a borrowed key) run this one now
-    if (c->multi() || c->P.parties != 1 || c->measure_margin || c->borrows_keys || !c->have_bk || !c->have_ks)
+    if (c->multi() || c->P.parties != 1 || c->measure_margin || c->borrows_keys || !c->have_bk || !c->have_ks())
         return tfhe_gates_batch(c, opcodes, in0, in1, in2, out, B);
     HIP_TRY(c, hipSetDevice(c->device));
     bool need[3] = {false, false, false};
@@ -548,7 +547,7 @@ static int32_t rotate_rows(tfhe_ctx *c, size_t R, int32_t mu, const TvPtrs *tv, 
         HIP_TRY(c, hipGetLastError());
     }
     if (e0) {
-        rc = mk ? launch_mk_keyswitch(c, G, e0, nullptr, dst, *samples, out, s) : launch_keyswitch(c, G, e0, nullptr, dst, *samples, out, s);
+        rc = launch_keyswitch(c, G, e0, nullptr, dst, *samples, out, s);
         if (rc) return rc;
     }
     if (events) HIP_TRY(c, hipEventRecord(c->ev[3], s));
@@ -580,12 +579,12 @@ static int32_t bootstrap_rows(tfhe_ctx *c, const char *who, int32_t mu, const Tv
         });
     }
     if (mk) {
-        if (!c->have_mk_bk || (with_keyswitch && !c->have_mk_ks)) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
-        // (the keyswitch loops over the bootstrapping key's parties: a keyswitch key loaded for fewer would be read past its end)
-        if (with_keyswitch && c->mk_ks_parties != c->mk_parties)
+        if (!c->have_mk_bk || (with_keyswitch && !c->have_mk_ks())) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
+        // (the keyswitch addresses rows by ITS key's parties, the rotation writes them by the bootstrapping key's: they must agree)
+        if (with_keyswitch && c->ks.parties != c->mk_parties)
             return c->set_err(TFHE_ERR_STATE, "%s: the bootstrapping key was loaded for %d parties, the keyswitch key for %d: load both for the same parties",
-                              who, c->mk_parties, c->mk_ks_parties);
-    } else if (!c->have_bk || (with_keyswitch && !c->have_ks)) {
+                              who, c->mk_parties, c->ks.parties);
+    } else if (!c->have_bk || (with_keyswitch && !c->have_ks())) {
         return c->set_err(TFHE_ERR_NO_KEY, "%s: key not loaded", who);
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -778,7 +777,7 @@ int32_t tfhe_keyswitch_batch(tfhe_ctx *c, const int32_t *in, int32_t *out, int64
         const size_t wi = (size_t)c->P.k * c->P.N + 1, wo = (size_t)c->P.n + 1;
         return multi_rows(c, B, [&](tfhe_ctx *k, int64_t s0, int64_t cnt) { return tfhe_keyswitch_batch(k, in + (size_t)s0 * wi, out + (size_t)s0 * wo, cnt); });
     }
-    if (!c->have_ks) return c->set_err(TFHE_ERR_NO_KEY, "keyswitch_batch: keyswitch key not loaded");
+    if (!c->have_ks()) return c->set_err(TFHE_ERR_NO_KEY, "keyswitch_batch: keyswitch key not loaded");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }

@@ -1,4 +1,5 @@
-// engine_keys.hip — keys: bootstrapping / keyswitch key loaders (single- and multi-key), key generation and RGSW.Expand on the device
+// engine_keys.hip — keys: bootstrapping / keyswitch key loaders (single- and multi-key; the keyswitch loaders fill the context's one
+// KsKey record), key generation and RGSW.Expand on the device
 #define TFHE_EMIT_KEYPREP_KERNELS
 #include "engine.hpp"
 #include "kernels_keygen.hpp"
@@ -29,7 +30,7 @@ void quiesce(tfhe_ctx *c)
         // every caller of quiesce is about to free or replace key buffers: the twin borrows them, so it must not keep the old
         // addresses (ensure_twin re-points it at the owner's current keys before its next use)
         tfhe_ctx *t = c->twin;
-        t->d_bk = nullptr; t->d_ks = nullptr; t->d_ksp = nullptr; t->d_ks4 = nullptr; t->have_bk = false; t->have_ks = false;
+        t->d_bk = nullptr; t->have_bk = false; t->ks = KsKey{};
     }
 }
 
@@ -105,23 +106,30 @@ int32_t tfhe_load_bootstrap_key_c128(tfhe_ctx *c, const double *bk_spectra) try
 }
 ABI_CATCH(c, "tfhe_load_bootstrap_key_c128")
 
+// rows of n + 1 words in one party's canonical keyswitch key, [kN][t][base-1] (keyswitch.jl:45-80)
+static size_t ks_row_count(const tfhe_params &p, int kN)
+{
+    return (size_t)kN * p.ks_t * ((1u << p.ks_log2_base) - 1);
+}
 static size_t ks_word_count(const tfhe_params &p)
 {
-    return (size_t)p.k * p.N * p.ks_t * ((1u << p.ks_log2_base) - 1) * (size_t)(p.n + 1);
+    return ks_row_count(p, p.k * p.N) * (size_t)(p.n + 1);
 }
 
-// Which keyswitch kernel family serves this context (decided when the key is loaded, so that only that family's key
-// layout stays resident): 4 = int8 MFMA (base 4, t = 8), 3 = tiled integer VALU (base 4, t multiple of 4), 1 = gather.
-static int pick_ks_mode(const tfhe_ctx *c)
+// Which keyswitch kernel family serves a key of kN mask words per party (decided when the key is loaded, so that only that
+// family's key layout stays resident): 4 = int8 MFMA (base 4, t = 8), 3 = tiled integer VALU (base 4, t a multiple of 4), 1 = the
+// gather kernel for every other base and length (keyswitch.jl:45-80 takes any).
+static int pick_ks_mode(const tfhe_ctx *c, int kN)
 {
-    const int kNn = c->P.k * c->P.N;
-    const bool ok4 = c->P.ks_log2_base == 2 && c->P.ks_t == 8 && kNn % 128 == 0;
-    const bool ok3 = c->P.ks_log2_base == 2 && c->P.ks_t % 4 == 0 && kNn % KS3_SLICES == 0 && kNn / KS3_SLICES <= 128;
+    const bool ok4 = c->P.ks_log2_base == 2 && c->P.ks_t == 8 && kN % 128 == 0;
+    const bool ok3 = c->P.ks_log2_base == 2 && c->P.ks_t % 4 == 0 && kN % KS3_SLICES == 0 && kN / KS3_SLICES <= 128;
     if (c->ks_variant == 4 && ok4) return 4;
     if (c->ks_variant >= 3 && ok3) return 3;
     return 1;
 }
 
+// Both keyswitch loaders fill c->ks and nothing else; its mode is set last, so a load that failed half-way leaves "no key" (and
+// whatever it allocated to the next release).
 int32_t tfhe_load_keyswitch_key(tfhe_ctx *c, const int32_t *ks) try
 {
     ENTER_CTX(c);
@@ -131,47 +139,47 @@ int32_t tfhe_load_keyswitch_key(tfhe_ctx *c, const int32_t *ks) try
     if (c->multi()) return fan_out(c, all_kids(c), [&](int k) { return tfhe_load_keyswitch_key(c->kids[(size_t)k], ks); });
     HIP_TRY(c, hipSetDevice(c->device));
     { const int32_t rcp = check_key_source(c, ks, "load_keyswitch_key"); if (rcp) return rcp; }
-    const size_t bytes = ks_word_count(c->P) * sizeof(int32_t);
-    c->have_ks = false;
+    const int kNn = c->P.k * c->P.N;
+    const size_t n1 = (size_t)c->P.n + 1, rows = ks_row_count(c->P, kNn), bytes = rows * n1 * sizeof(int32_t);
     quiesce(c);
-    if (c->d_ks) { (void)hipFree(c->d_ks); c->d_ks = nullptr; }
-    if (c->d_ksp) { (void)hipFree(c->d_ksp); c->d_ksp = nullptr; }
-    if (c->d_ks4) { (void)hipFree(c->d_ks4); c->d_ks4 = nullptr; }
+    release(c->ks);
+    KsKey &K = c->ks;
+    K.kN = kNn;
     int32_t *d_canon = nullptr;
     HIP_TRY(c, hipMalloc((void **)&d_canon, bytes));
-    const int mode = pick_ks_mode(c);
+    const int mode = pick_ks_mode(c, kNn);
     auto body = [&]() -> int32_t {
         // host pointer, or a device buffer (tfhe_keygen_cloud_key).  On the context's stream, like everything that consumes
         // d_canon below: a device-to-device hipMemcpy is NOT synchronous with the host and runs on the NULL stream, which
         // this context's non-blocking stream does not wait for
         HIP_TRY(c, hipMemcpyAsync(d_canon, ks, bytes, hipMemcpyDefault, c->stream));
         if (mode == 3) {   // row-padded copy: stride = n+1 rounded up to 4 words so that rows are 16-byte aligned
-            const size_t n1 = (size_t)c->P.n + 1, stride = (n1 + 3) & ~(size_t)3;
-            const size_t rows = ks_word_count(c->P) / n1;
-            HIP_TRY(c, hipMalloc((void **)&c->d_ksp, rows * stride * 4));
-            HIP_TRY(c, hipMemsetAsync(c->d_ksp, 0, rows * stride * 4, c->stream));
-            HIP_TRY(c, hipMemcpy2DAsync(c->d_ksp, stride * 4, d_canon, n1 * 4, n1 * 4, rows, hipMemcpyDeviceToDevice, c->stream));
+            const size_t stride = (n1 + 3) & ~(size_t)3;
+            HIP_TRY(c, hipMalloc(&K.p, rows * stride * 4));
+            HIP_TRY(c, hipMemsetAsync(K.p, 0, rows * stride * 4, c->stream));
+            HIP_TRY(c, hipMemcpy2DAsync(K.p, stride * 4, d_canon, n1 * 4, n1 * 4, rows, hipMemcpyDeviceToDevice, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            c->ks_stride = (int)stride;
+            K.stride = (int)stride;
+            K.per_party = rows * stride;
         } else if (mode == 4) {
-            const int kNn = c->P.k * c->P.N, wtiles = (c->P.n + 1 + 31) / 32;
+            const int wtiles = (c->P.n + 1 + 31) / 32;
             const size_t frags = (size_t)kNn * wtiles * 4 * 64;
-            HIP_TRY(c, hipMalloc(&c->d_ks4, frags * 16));
+            HIP_TRY(c, hipMalloc(&K.p, frags * 16));
             hipLaunchKernelGGL(ks4_prepare_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), 0, c->stream, (const int32_t *)d_canon,
-                               (i32x4 *)c->d_ks4, c->P.n, kNn, wtiles);
+                               (i32x4 *)K.p, c->P.n, kNn, wtiles);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            c->ks4_wtiles = wtiles;
+            K.wtiles = wtiles;
+            K.per_party = frags;
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream));      // the caller's buffer is free again, the key is complete for any stream
         return TFHE_OK;
     };
     const int32_t rc = body();
-    if (rc == TFHE_OK && mode == 1) c->d_ks = d_canon;       // the gather kernel reads the canonical layout
+    if (rc == TFHE_OK && mode == 1) { K.p = d_canon; K.per_party = rows * n1; }      // the gather kernel reads the canonical layout
     else (void)hipFree(d_canon);
     if (rc) return rc;
-    c->ks_mode = mode;
-    c->have_ks = true;
+    K.mode = mode;
     return TFHE_OK;
 }
 ABI_CATCH(c, "tfhe_load_keyswitch_key")
@@ -481,43 +489,38 @@ int32_t tfhe_mk_load_keyswitch_key(tfhe_ctx *c, const int32_t *ks, int32_t parti
     if (c->multi()) return fan_out(c, all_kids(c), [&](int k) { return tfhe_mk_load_keyswitch_key(c->kids[(size_t)k], ks, parties); });
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n1 = (size_t)c->P.n + 1, stride = (n1 + 3) & ~(size_t)3;
-    const size_t rows = (size_t)c->P.N * c->P.ks_t * ((1u << c->P.ks_log2_base) - 1);   // per party (k = 1)
-    c->have_mk_ks = false;
+    const size_t rows = ks_row_count(c->P, c->P.N);      // per party (k = 1)
     quiesce(c);
-    if (c->d_mk_ksp) { (void)hipFree(c->d_mk_ksp); c->d_mk_ksp = nullptr; }
-    if (c->d_mk_ks4) { (void)hipFree(c->d_mk_ks4); c->d_mk_ks4 = nullptr; }
-    if (c->d_ks) { (void)hipFree(c->d_ks); c->d_ks = nullptr; }
-    // the kernel family by keyswitch shape, as for a single key (pick_ks_mode): int8 MFMA for base 4 / t = 8, the tiled integer
-    // kernel for base 4 / t a multiple of 4, the gather kernel for every other base and length (keyswitch.jl:45-80 takes any)
-    const bool ok3 = c->P.ks_log2_base == 2 && c->P.ks_t % 4 == 0 && c->P.N % KS3_SLICES == 0 && c->P.N / KS3_SLICES <= 128;
-    const bool ok4 = c->P.ks_log2_base == 2 && c->P.ks_t == 8 && c->P.N % 128 == 0;
-    const int mode = (c->ks_variant == 4 && ok4) ? 4 : (c->ks_variant >= 3 && ok3) ? 3 : 1;
+    release(c->ks);
+    KsKey &K = c->ks;
+    K.parties = parties;
+    K.kN = c->P.N;
+    // (every copy and kernel of a loader runs on the context's own stream: nothing here depends on what the NULL stream orders)
+    const int mode = pick_ks_mode(c, c->P.N);
     if (mode == 1) {
         // canonical layout, the parties' keys back to back
-        HIP_TRY(c, hipMalloc((void **)&c->d_ks, (size_t)parties * rows * n1 * 4));
-        HIP_TRY(c, hipMemcpyAsync(c->d_ks, ks, (size_t)parties * rows * n1 * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMalloc(&K.p, (size_t)parties * rows * n1 * 4));
+        HIP_TRY(c, hipMemcpyAsync(K.p, ks, (size_t)parties * rows * n1 * 4, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->mk_ksp_words = rows * n1;
-    } else
-    if (mode == 3) {
-        // (every copy and kernel of a loader runs on the context's own stream: nothing here depends on what the NULL stream orders)
-        HIP_TRY(c, hipMalloc((void **)&c->d_mk_ksp, (size_t)parties * rows * stride * 4));
-        HIP_TRY(c, hipMemsetAsync(c->d_mk_ksp, 0, (size_t)parties * rows * stride * 4, c->stream));
-        HIP_TRY(c, hipMemcpy2DAsync(c->d_mk_ksp, stride * 4, ks, n1 * 4, n1 * 4, (size_t)parties * rows, hipMemcpyHostToDevice, c->stream));
+        K.per_party = rows * n1;
+    } else if (mode == 3) {
+        HIP_TRY(c, hipMalloc(&K.p, (size_t)parties * rows * stride * 4));
+        HIP_TRY(c, hipMemsetAsync(K.p, 0, (size_t)parties * rows * stride * 4, c->stream));
+        HIP_TRY(c, hipMemcpy2DAsync(K.p, stride * 4, ks, n1 * 4, n1 * 4, (size_t)parties * rows, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->mk_ksp_words = rows * stride;
-        c->ks_stride = (int)stride;
+        K.per_party = rows * stride;
+        K.stride = (int)stride;
     } else {   // MFMA fragments per party (keyswitch_kernel_v4)
         const int wtiles = (c->P.n + 1 + 31) / 32;
         const size_t frags = (size_t)c->P.N * wtiles * 4 * 64, words = rows * n1;
         int32_t *d_tmp = nullptr;
         HIP_TRY(c, hipMalloc((void **)&d_tmp, words * 4));
         auto body = [&]() -> int32_t {
-            HIP_TRY(c, hipMalloc(&c->d_mk_ks4, (size_t)parties * frags * 16));
+            HIP_TRY(c, hipMalloc(&K.p, (size_t)parties * frags * 16));
             for (int p = 0; p < parties; p++) {
                 HIP_TRY(c, hipMemcpyAsync(d_tmp, ks + (size_t)p * words, words * 4, hipMemcpyHostToDevice, c->stream));
                 hipLaunchKernelGGL(ks4_prepare_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), 0, c->stream, (const int32_t *)d_tmp,
-                                   (i32x4 *)c->d_mk_ks4 + (size_t)p * frags, c->P.n, c->P.N, wtiles);
+                                   (i32x4 *)K.p + (size_t)p * frags, c->P.n, c->P.N, wtiles);
                 HIP_TRY(c, hipGetLastError());
                 HIP_TRY(c, hipStreamSynchronize(c->stream));
             }
@@ -526,13 +529,10 @@ int32_t tfhe_mk_load_keyswitch_key(tfhe_ctx *c, const int32_t *ks, int32_t parti
         const int32_t rc = body();
         (void)hipFree(d_tmp);        // also on the error path
         if (rc) return rc;
-        c->mk_ks4_frags = frags;
-        c->ks4_wtiles = wtiles;
+        K.per_party = frags;
+        K.wtiles = wtiles;
     }
-    c->ks_mode = mode;
-    c->mk_ks_parties = parties;
-    c->have_mk_ks = true;
+    K.mode = mode;
     return TFHE_OK;
 }
 ABI_CATCH(c, "tfhe_mk_load_keyswitch_key")
-

@@ -167,7 +167,7 @@ int32_t tfhe_cmux_tree_batch(tfhe_ctx *c, const int32_t *data, int64_t T, const 
     if (T < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "cmux_tree_batch: T = %lld (at least one table)", (long long)T);
     if (out_form < 0 || out_form > 2) return c->set_err(TFHE_ERR_INVALID_ARG, "cmux_tree_batch: out_form = %d (0 TLWE, 1 extracted, 2 key-switched)", out_form);
     if (!c->d_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "cmux_tree_batch: no selector set loaded (tfhe_tgsw_load)");
-    if (out_form == 2 && !c->have_ks) return c->set_err(TFHE_ERR_NO_KEY, "cmux_tree_batch: out_form 2 needs the keyswitch key");
+    if (out_form == 2 && !c->have_ks()) return c->set_err(TFHE_ERR_NO_KEY, "cmux_tree_batch: out_form 2 needs the keyswitch key");
     rc = check_selectors(c, "cmux_tree_batch", sel, B, depth);
     if (rc) return rc;
     if (table_index)

@@ -158,15 +158,15 @@ int32_t tfhe_mk_gate_nand_batch(tfhe_ctx *c, const int32_t *in0, const int32_t *
     if (B == 0) return TFHE_OK;
     if (c->multi()) {
         const tfhe_ctx *k0 = c->kids[0];
-        if (!k0->have_mk_bk || !k0->have_mk_ks) return c->set_err(TFHE_ERR_NO_KEY, "mk_gate_nand_batch: multi-key keys not loaded");
+        if (!k0->have_mk_bk || !k0->have_mk_ks()) return c->set_err(TFHE_ERR_NO_KEY, "mk_gate_nand_batch: multi-key keys not loaded");
         const size_t w = (size_t)k0->mk_parties * c->P.n + 1;
         return multi_rows(c, B, [&](tfhe_ctx *k, int64_t s0, int64_t cnt) { return tfhe_mk_gate_nand_batch(k, in0 + (size_t)s0 * w, in1 + (size_t)s0 * w, out + (size_t)s0 * w, cnt); });
     }
-    if (!c->have_mk_bk || !c->have_mk_ks) return c->set_err(TFHE_ERR_NO_KEY, "mk_gate_nand_batch: multi-key keys not loaded");
-    // (the keyswitch loops over the bootstrapping key's parties: a keyswitch key loaded for fewer would be read past its end)
-    if (c->mk_ks_parties != c->mk_parties)
+    if (!c->have_mk_bk || !c->have_mk_ks()) return c->set_err(TFHE_ERR_NO_KEY, "mk_gate_nand_batch: multi-key keys not loaded");
+    // (the keyswitch addresses rows by ITS key's parties, the rotation writes them by the bootstrapping key's: they must agree)
+    if (c->ks.parties != c->mk_parties)
         return c->set_err(TFHE_ERR_STATE, "mk_gate_nand_batch: the bootstrapping key was loaded for %d parties, the keyswitch key for %d: load both for the same parties",
-                          c->mk_parties, c->mk_ks_parties);
+                          c->mk_parties, c->ks.parties);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }
@@ -200,7 +200,7 @@ int32_t tfhe_mk_gate_nand_batch(tfhe_ctx *c, const int32_t *in0, const int32_t *
     rc = launch_mk_blind_rotate(c, (size_t)B, s);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    rc = launch_mk_keyswitch(c, (size_t)B, d_gate, nullptr, nullptr, (const int32_t *)c->ext.p, (int32_t *)c->io[3].p, s);
+    rc = launch_keyswitch(c, (size_t)B, d_gate, nullptr, nullptr, (const int32_t *)c->ext.p, (int32_t *)c->io[3].p, s);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[3], s));
     HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, bytes, hipMemcpyDeviceToHost, s));
@@ -298,7 +298,7 @@ int32_t run_mk_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64
     }
     if (!no_ev) HIP_TRY(c, hipEventRecord(c->ev[2], s));
     if (G > 0) {
-        rc = launch_mk_keyswitch(c, G, d_e0, d_e1, d_dst, (const int32_t *)c->ext.p, d_out, s);
+        rc = launch_keyswitch(c, G, d_e0, d_e1, d_dst, (const int32_t *)c->ext.p, d_out, s);
         if (rc) return rc;
     }
     if (!no_ev) HIP_TRY(c, hipEventRecord(c->ev[3], s));
@@ -311,13 +311,13 @@ int32_t run_mk_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64
     return leave_stream(c, s);
 }
 
-// multi-key keys loaded, for the same parties (a keyswitch key loaded for fewer would be read past its end)
+// multi-key keys loaded, for the same parties (the keyswitch addresses rows by its key's parties, the rotation by the bootstrapping key's)
 static int32_t mk_keys_ready(tfhe_ctx *c, const tfhe_ctx *k, const char *who)
 {
-    if (!k->have_mk_bk || !k->have_mk_ks) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
-    if (k->mk_ks_parties != k->mk_parties)
+    if (!k->have_mk_bk || !k->have_mk_ks()) return c->set_err(TFHE_ERR_NO_KEY, "%s: multi-key keys not loaded", who);
+    if (k->ks.parties != k->mk_parties)
         return c->set_err(TFHE_ERR_STATE, "%s: the bootstrapping key was loaded for %d parties, the keyswitch key for %d: load both for the same parties",
-                          who, k->mk_parties, k->mk_ks_parties);
+                          who, k->mk_parties, k->ks.parties);
     return TFHE_OK;
 }
 

@@ -18,8 +18,8 @@ struct KsArgs {
     const int32_t *dst;     // [G] output gate index (NULL: identity)
     int32_t *out;           // [B][out_stride]
     int32_t n, kN, t, log2_base;
-    // generalised addressing (single key: in_stride = kN+1, in_off = 0, in_b = kN, out_stride = n+1, out_off = 0, out_b = n;
-    // multi-key party p (mk_internals.jl:397-411): in_off = p*N, in_b = P*N, out_off = p*n, out_b = P*n)
+    // addressing, filled once for all three families by launch_keyswitch (ks_args): P parties of kN mask words, in_stride = P*kN+1,
+    // in_b = P*kN, out_stride = P*n+1, out_b = P*n; party p (mk_internals.jl:397-411): in_off = p*kN, out_off = p*n.  A single key is P = 1
     int32_t in_stride, in_off, in_b, out_stride, out_off, out_b;
     int32_t add_b;          // 1: out[out_b] = ext b (+ MUX constant) - sum; 0 (multi-key party > 0): accumulate into out[out_b]
 };
@@ -98,8 +98,7 @@ struct Ks3Args {
     const int32_t *e0, *e1, *dst;
     int32_t *out;           // [B][out_stride], pre-initialised to (0, ..., 0, b) by ks3_init_kernel
     int32_t n, kN, t, log2_base, stride, G;
-    // generalised addressing (single key: in_stride = kN+1, in_off = 0, in_b = kN, out_stride = n+1,
-    // out_off = 0, out_b = n; multi-key party p: in_off = p*N, out_off = p*n, out_b = P*n)
+    // addressing as in KsArgs
     int32_t in_stride, in_off, in_b, out_stride, out_off, out_b;
 };
 
@@ -139,7 +138,7 @@ __global__ __launch_bounds__(128, 2) void keyswitch_kernel_v3(Ks3Args P)
     const int slen = P.kN / KS3_SLICES;
     const int i0 = slice * slen;
     const int lb = P.log2_base, tl = P.t;
-    const int base1 = (1 << lb) - 1;              // == 3 (checked by the launcher)
+    const int base1 = (1 << lb) - 1;              // == 3 (pick_ks_mode gives this kernel base 4 only)
     const uint32_t prec_offset = 1u << (32 - (1 + lb * tl));                 // keyswitch.jl:58
     const int w0 = wchunk * 512 + tid * 4;        // first of this lane's 4 words
     const bool active = w0 < P.stride;
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(128, 2) void keyswitch_kernel_v3(Ks3Args P)
     for (int g = 0; g < G; g++) acc[g] = (u32x4)(0u);
 
     const size_t row_words = (size_t)P.stride;
-    const int stages = slen * (tl / JH);          // tl is a multiple of JH (checked by the launcher)
+    const int stages = slen * (tl / JH);          // tl is a multiple of JH (pick_ks_mode again)
     auto load_stage = [&](int st, u32x4 (&r)[JH][3]) {
         const int ii = st / (tl / JH), jh = st % (tl / JH);
         const int32_t *rows = P.ksp + ((size_t)(i0 + ii) * tl + jh * JH) * base1 * row_words + wl;
