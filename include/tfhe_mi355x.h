@@ -435,6 +435,47 @@ int32_t tfhe_extern_mul_batch(tfhe_ctx *ctx, const int32_t *tlwe_in, const int32
 int32_t tfhe_cmux_tree_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, const int32_t *table_index, int32_t depth,
                              const int32_t *sel, int32_t *out, int64_t B, int32_t out_form);
 
+/* ---- leveled mode under a multi-key cloud key (additions within ABI v7) ---------------------------------
+ * The same two operations on multi-key samples, with no blind rotation: the selectors are the parties' uni-encryptions of address
+ * bits (mk_tgsw_encrypt, RGSW.UniEnc, mk_internals.jl:185-227) expanded against all public keys (mk_tgsw_expand, :304-345), the
+ * product is mk_tgsw_extern_mul (:348-391) — which the reference applies to the bootstrapping key only — on the caller's own
+ * MKTLweSample (:46-57; tlwe_mask_size = 1, :89-90).  P = the parties of the loaded multi-key bootstrapping key, per = 2 l P + 2 l.
+ * One-device multi-key contexts only: TFHE_ERR_STATE on a single-key context (its calls are the three above, which in turn keep
+ * refusing a multi-key context), on a multi-device context, and with "measure_margin" on; TFHE_ERR_NO_KEY without the multi-key
+ * bootstrapping key or without a selector set.  Same exactness domain as the multi-key rotation: (P + 1) l products per rounding.
+ * tfhe_last_kernel_name: "mk_cmux_level_kernel(N=..,P=..,l=..[,spec=global])"; tfhe_last_timing_ms: 0 = levels, 1 = keyswitch, 2 = both.
+ *
+ * The selector set.  tgsw: host int32 [S][per][N], S expanded samples (MKTGswExpSample, :243-271), each laid out exactly as one
+ * (party, bit) entry of tfhe_mk_load_bootstrap_key_i32: x [l][P], y [l][P], c0 [l], c1 [l]; party_of: host int32 [S] in [0, P), the
+ * party whose expansion sample s is.  Forward-transformed once (forward_transform(::MKTGswExpSample), :291-301) into the any-N
+ * kernels' spectrum order whichever kernel family serves the rotation; replaces any earlier multi-key selector set; a multi-key
+ * bootstrapping key loaded later for ANOTHER party count drops it.  `parties` must equal P: TFHE_ERR_STATE otherwise.
+ * TFHE_ERR_INVALID_ARG: NULL pointer, S < 1, a party_of entry out of range (checked before anything is uploaded). */
+int32_t tfhe_mk_tgsw_load(tfhe_ctx *ctx, const int32_t *tgsw, const int32_t *party_of, int64_t S, int32_t parties);
+
+/* The same store built on the device from what the parties publish (mk_tgsw_expand, mk_internals.jl:304-345, for S samples): pub_b
+ * host int32 [P][l][N] (PublicKey.b, :116-139); c0, c1, d0, d1, f0, f1 host int32 [S][l][N], sample s uni-encrypted by party
+ * party_of[s].  The selectors are grouped by party and every group runs the expand path of tfhe_mk_expand_load_bootstrap_key with the
+ * group's size in the place of n.  expanded_out: NULL, or host int32 [S][per][N] receiving the expanded samples in the caller's
+ * order — word for word what a host expansion followed by tfhe_mk_tgsw_load holds. */
+int32_t tfhe_mk_tgsw_expand_load(tfhe_ctx *ctx, int32_t parties, const int32_t *pub_b, const int32_t *party_of, const int32_t *c0,
+                                 const int32_t *c1, const int32_t *d0, const int32_t *d1, const int32_t *f0, const int32_t *f1, int64_t S,
+                                 int32_t *expanded_out);
+
+/* tlwe_out[g] = mk_tgsw_extern_mul(tlwe_in[g], selector[sel[g]], party_of[sel[g]], P)  (mk_internals.jl:348-391) for B rows.  Rows: host
+ * int32 [B][P+1][N] = a_0 ... a_{P-1}, b (MKTLweSample, :46-57); sel: host int32 [B] in [0, S).  TFHE_ERR_INVALID_ARG: a selector out
+ * of range (checked before anything is uploaded). */
+int32_t tfhe_mk_extern_mul_batch(tfhe_ctx *ctx, const int32_t *tlwe_in, const int32_t *sel, int32_t *tlwe_out, int64_t B);
+
+/* CMUX tree on multi-key samples: tfhe_cmux_tree_batch's contract with data host int32 [T][2^depth][P+1][N].  Level v replaces each pair
+ * (d0, d1) by d0 + selector[sel[g][v]] (.) (d1 - d0): mk_mux_rotate (mk_internals.jl:464-471) without the monomial.  out_form 0: the
+ * MK TLWE sample, out int32 [B][P+1][N]; 1: mk_tlwe_extract_sample (:88-95), [B][P*N+1]; 2: that through mk_keyswitch (:397-411),
+ * [B][P*n+1], a multi-key LWE sample every tfhe_mk_gate* call accepts.  Depth 1 ... 12; two ping-pong workspaces whose sizes are
+ * compared with the device's free memory BEFORE anything is allocated (TFHE_ERR_NOMEM, the context stays usable).
+ * TFHE_ERR_INVALID_ARG as tfhe_cmux_tree_batch; TFHE_ERR_NO_KEY also for out_form 2 without the multi-key keyswitch key. */
+int32_t tfhe_mk_cmux_tree_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, const int32_t *table_index, int32_t depth,
+                                const int32_t *sel, int32_t *out, int64_t B, int32_t out_form);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Timing of the most recent batch call on ctx, from HIP events recorded on the stream the kernels

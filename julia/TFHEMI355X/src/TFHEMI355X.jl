@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -742,6 +742,71 @@ mk_gate_nand(mck::GpuMKCloudKey, x::MKLweSample, y::MKLweSample) = mk_nand_batch
 mk_gate_nand(mck::GpuMKCloudKey, xs::MKVec, ys::MKVec) = mk_nand_batch(mck, xs, ys)
 broadcasted(::typeof(mk_gate_nand), mck::GpuMKCloudKey, xs::MKVec, ys::MKVec) = mk_nand_batch(mck, xs, ys)
 broadcasted(::typeof(mk_gate_nand), mck::Base.RefValue{GpuMKCloudKey}, xs::MKVec, ys::MKVec) = mk_nand_batch(mck[], xs, ys)
+
+"""
+    mk_tgsw_load!(mck, tgsw::Array{Int32}, party_of)
+
+The selector set of `mk_extern_mul` / `mk_cmux_tree` (tfhe_mk_tgsw_load): `S` expanded RGSW samples (`mk_tgsw_expand`,
+src/mk_internals.jl:304-345) as Int32 `N x (2lP + 2l) x S` (column-major: the C layout [S][2lP + 2l][N], per sample `x[l][P]`,
+`y[l][P]`, `c0[l]`, `c1[l]` as in the multi-key bootstrapping key) and `party_of[s]` (1-based), the party sample `s` was expanded
+for.  Replaces any earlier set.
+"""
+function mk_tgsw_load!(mck::GpuMKCloudKey, tgsw::Array{Int32}, party_of)
+    p, P = mck.params, mck.parties
+    per = p.tlwe_polynomial_degree * (2 * p.bs_decomp_length * P + 2 * p.bs_decomp_length)
+    who = Int32.(collect(party_of) .- 1)
+    (length(who) > 0 && length(tgsw) == per * length(who)) || error("tfhe_mi355x: expanded samples must hold ", per, " words for each entry of party_of")
+    GC.@preserve tgsw who @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_tgsw_load, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int64, Int32), mck.ctx, tgsw, who, Int64(length(who)), Int32(P)))
+    mck
+end
+
+"""
+    mk_extern_mul(mck, tlwe::Array{Int32,3}, sel)  ->  Array{Int32,3}
+
+`mk_tgsw_extern_mul` (src/mk_internals.jl:348-391) for a batch (tfhe_mk_extern_mul_batch): MK TLWE sample `g` of `tlwe` (Int32
+`N x (P+1) x B`: the party masks, then the body) times loaded selector `sel[g]` (1-based).
+"""
+function mk_extern_mul(mck::GpuMKCloudKey, tlwe::Array{Int32,3}, sel)
+    p, P = mck.params, mck.parties
+    size(tlwe)[1:2] == (p.tlwe_polynomial_degree, P + 1) || error("tfhe_mi355x: MK TLWE samples must be N x (P+1) x B")
+    B = size(tlwe, 3)
+    idx = Int32.(collect(sel) .- 1)
+    length(idx) == B || error("tfhe_mi355x: one selector per sample")
+    out = similar(tlwe)
+    B == 0 && return out
+    GC.@preserve tlwe idx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_extern_mul_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64), mck.ctx, tlwe, idx, out, Int64(B)))
+    out
+end
+
+"""
+    mk_cmux_tree(mck, data::Array{Int32,4}, sel::AbstractMatrix, table_index=nothing; out_form=2)
+
+CMUX-tree lookup on multi-key samples (tfhe_mk_cmux_tree_batch): `cmux_tree` with tables Int32 `N x (P+1) x 2^depth x T`; every level
+is `d0 + C ⊡ (d1 - d0)`, the form of `mk_mux_rotate` (src/mk_internals.jl:464-471) without the monomial.  `out_form` 2 returns
+`Vector{MKLweSample}` (mk_tlwe_extract_sample :88-95, mk_keyswitch :397-411) that `mk_gate_nand` accepts, 1 the extracted samples as
+Int32 `(P N + 1) x B`, 0 the MK TLWE samples as Int32 `N x (P+1) x B`.
+"""
+function mk_cmux_tree(mck::GpuMKCloudKey, data::Array{Int32,4}, sel::AbstractMatrix, table_index=nothing; out_form::Integer=2)
+    p, P = mck.params, mck.parties
+    N, n = p.tlwe_polynomial_degree, p.lwe_size
+    depth, B = size(sel)
+    1 <= depth <= 12 || error("tfhe_mi355x: depth = ", depth, " (1 ... 12)")
+    size(data)[1:3] == (N, P + 1, 1 << depth) || error("tfhe_mi355x: tables must be N x (P+1) x 2^depth x T")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    s = Matrix{Int32}(sel .- 1)
+    idx = table_index === nothing ? nothing : Int32.(collect(table_index) .- 1)
+    width = out_form == 2 ? P * n : P * N
+    out = out_form == 0 ? Array{Int32}(undef, N, P + 1, B) : Array{Int32}(undef, width + 1, B)
+    B == 0 && return out_form == 2 ? MKLweSample[] : out
+    GC.@preserve data s idx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_cmux_tree_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Int32),
+        mck.ctx, data, Int64(size(data, 4)), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), Int32(depth), s, out, Int64(B), Int32(out_form)))
+    out_form == 2 || return out
+    params = LweParams(n)
+    [MKLweSample(params, reshape(out[1:n*P, g], n, P), out[n * P + 1, g], 0.) for g in 1:B]
+end
 
 """
     mk_bootstrap_tv(mck, tables, xs, index=nothing; with_keyswitch=true)  ->  Vector{MKLweSample}

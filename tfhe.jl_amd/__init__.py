@@ -18,6 +18,7 @@ from .lut import (lut_encode, lut_decode, lut_encrypt, lut_decrypt, make_test_ve
                   programmable_bootstrap_multi, make_gate_test_vector, GATE_BIT_TO_Z2)
 from .serialize import save_cloud_key, load_cloud_key
 from .leveled import tlwe_encrypt, tlwe_trivial, tlwe_phase, tgsw_encrypt_bits, table_to_tlwe, cmux_lookup
+from .leveled import mk_tlwe_trivial, mk_tlwe_encrypt, mk_tlwe_phase, mk_tgsw_uni_encrypt_bits, mk_tgsw_expand, mk_cmux_lookup
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
 
 __all__ = [

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "tfhe_bootstrap_tv_batch", "tfhe_bootstrap_tv_multi_batch", "tfhe_lut_level", "tfhe_linear_level",
     "tfhe_mk_bootstrap_tv_batch", "tfhe_mk_bootstrap_tv_multi_batch", "tfhe_mk_lut_level", "tfhe_mk_linear_level",
     "tfhe_tgsw_load", "tfhe_extern_mul_batch", "tfhe_cmux_tree_batch",
+    "tfhe_mk_tgsw_load", "tfhe_mk_tgsw_expand_load", "tfhe_mk_extern_mul_batch", "tfhe_mk_cmux_tree_batch",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -150,6 +151,11 @@ def load():
         lib.tfhe_tgsw_load.argtypes = [vp, vp, i64]
         lib.tfhe_extern_mul_batch.argtypes = [vp, vp, vp, vp, i64]
         lib.tfhe_cmux_tree_batch.argtypes = [vp, vp, i64, vp, i32, vp, vp, i64, i32]
+    if hasattr(lib, "tfhe_mk_tgsw_load"):
+        lib.tfhe_mk_tgsw_load.argtypes = [vp, vp, vp, i64, i32]
+        lib.tfhe_mk_tgsw_expand_load.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        lib.tfhe_mk_extern_mul_batch.argtypes = [vp, vp, vp, vp, i64]
+        lib.tfhe_mk_cmux_tree_batch.argtypes = [vp, vp, i64, vp, i32, vp, vp, i64, i32]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -461,6 +467,71 @@ class Engine:
         shape = {0: (B, self.k + 1, self.N), 1: (B, self.k * self.N + 1), 2: (B, self.n + 1)}.get(int(out_form), (0,))
         out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
         self._check(self._lib.tfhe_cmux_tree_batch(self._h, _ptr(d), d.shape[0], _ptr(idx), depth, _ptr(sel), _ptr(out), B, int(out_form)))
+        return out
+
+    # ---- leveled mode under a multi-key cloud key: expanded RGSW selectors, MK TLWE samples [P+1][N] ----
+    def mk_tgsw_load(self, tgsw, party_of):
+        """The multi-key selector set (tfhe_mk_tgsw_load): int32 [S][2lP + 2l][N], S expanded RGSW samples laid out as the entries of
+        the multi-key bootstrapping key (leveled.mk_tgsw_expand makes them), and party_of [S], the party each was expanded for.
+        Replaces any earlier set."""
+        P = self._mk_width("mk_tgsw_load")
+        t, who = _i32c(tgsw), _i32c(party_of).reshape(-1)
+        per = (2 * self.params.bs_decomp_length * P + 2 * self.params.bs_decomp_length) * self.N
+        if who.size == 0 or t.size != who.size * per:
+            raise ValueError(f"expanded samples have {t.size} words, expected {per} for each of the {who.size} entries of party_of")
+        self._check(self._lib.tfhe_mk_tgsw_load(self._h, _ptr(t), _ptr(who), who.size, P))
+
+    def mk_tgsw_expand_load(self, pub_b, party_of, c0, c1, d0, d1, f0, f1, want_expanded=False):
+        """The same selector set expanded on the device (tfhe_mk_tgsw_expand_load).  pub_b: [P][l][N]; party_of: [S]; c0 .. f1: [S][l][N],
+        sample s uni-encrypted by party party_of[s] (leveled.mk_tgsw_uni_encrypt_bits).  Returns the expanded samples
+        [S][2lP + 2l][N] if want_expanded."""
+        P, l = self._mk_width("mk_tgsw_expand_load"), self.params.bs_decomp_length
+        who = _i32c(party_of).reshape(-1)
+        S = who.size
+        arrs = [_i32c(a) for a in (pub_b, c0, c1, d0, d1, f0, f1)]
+        if arrs[0].shape != (P, l, self.N):
+            raise ValueError(f"public keys must be [{P}][{l}][{self.N}], got {arrs[0].shape}")
+        for a in arrs[1:]:
+            if S == 0 or a.shape != (S, l, self.N):
+                raise ValueError(f"uni-encryption arrays must be [{S}][{l}][{self.N}] with S >= 1, got {a.shape}")
+        out = np.empty((S, 2 * l * P + 2 * l, self.N), np.int32) if want_expanded else None
+        self._check(self._lib.tfhe_mk_tgsw_expand_load(self._h, P, _ptr(arrs[0]), _ptr(who), *[_ptr(a) for a in arrs[1:]], S, _ptr(out)))
+        return out
+
+    def mk_extern_mul(self, tlwe, sel):
+        """out[g] = mk_tgsw_extern_mul(tlwe[g], selector[sel[g]]) (tfhe_mk_extern_mul_batch; mk_internals.jl:348-391): int32 [B][P+1][N]."""
+        P = self._mk_width("mk_extern_mul")
+        x = _i32c(tlwe)
+        if x.ndim != 3 or x.shape[1:] != (P + 1, self.N):
+            raise ValueError(f"MK TLWE samples must be [B][{P + 1}][{self.N}], got {x.shape}")
+        B = x.shape[0]
+        idx = _i32c(sel).reshape(-1)
+        if idx.size != B:
+            raise ValueError(f"sel must have one entry per row ({B}), got {idx.size}")
+        out = np.empty_like(x)
+        self._check(self._lib.tfhe_mk_extern_mul_batch(self._h, _ptr(x), _ptr(idx), _ptr(out), B))
+        return out
+
+    def mk_cmux_tree(self, data, sel, table_index=None, out_form=2):
+        """CMUX-tree lookup on multi-key samples (tfhe_mk_cmux_tree_batch): cmux_tree with tables int32 [T][2^depth][P+1][N].  Row g's
+        result is an MK TLWE sample [P+1][N] (out_form 0), extracted at coefficient 0 [P*N+1] (1) or keyswitched to a multi-key LWE
+        sample [P*n+1] (2), an operand of every mk_gate."""
+        P = self._mk_width("mk_cmux_tree")
+        d = _i32c(data)
+        if d.ndim == 3:
+            d = d[None]
+        sel = _i32c(np.atleast_2d(sel))
+        B, depth = sel.shape
+        if d.ndim != 4 or d.shape[1:] != (1 << min(max(depth, 0), 30), P + 1, self.N):
+            raise ValueError(f"tables must be [T][2^{depth}][{P + 1}][{self.N}], got {d.shape}")
+        idx = None
+        if table_index is not None:
+            idx = _i32c(table_index).reshape(-1)
+            if idx.size != B:
+                raise ValueError(f"table_index must have one entry per row ({B}), got {idx.size}")
+        shape = {0: (B, P + 1, self.N), 1: (B, P * self.N + 1), 2: (B, P * self.n + 1)}.get(int(out_form), (0,))
+        out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
+        self._check(self._lib.tfhe_mk_cmux_tree_batch(self._h, _ptr(d), d.shape[0], _ptr(idx), depth, _ptr(sel), _ptr(out), B, int(out_form)))
         return out
 
     # ---- levelised circuits on the device-resident wire table ----

@@ -13,6 +13,7 @@
 //   engine_mk_tv.hip      the multi-key TV kernels (multi-key programmable bootstrapping) and their launchers     ("mk tv")
 //   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit (-DG2_TV=1: its TV form)
 //   engine_leveled.hip    leveled mode: batched external products and CMUX trees on a caller's TGSW / TLWE samples  ("leveled")
+//   engine_mk_leveled.hip the same under a multi-key cloud key: expanded RGSW selectors, MK TLWE samples          ("mk leveled")
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
 // only under the TFHE_EMIT_* macro of the unit that launches them (templates are instantiated where they are launched).
@@ -207,6 +208,11 @@ struct tfhe_ctx {
     // TLWE samples, the uploaded tables, spectrum accumulators that do not fit LDS)
     cplx *d_tgsw = nullptr;        int64_t tgsw_count = 0;
     DevBuf lvl_ws[2], lvl_data, lvl_spec;
+    // the multi-key leveled mode (engine_mk_leveled.hip; it shares the workspaces above): the selector set of tfhe_mk_tgsw_load /
+    // tfhe_mk_tgsw_expand_load, [S][2 l P + 2 l][N/2] spectra of expanded RGSW samples in the any-N kernels' order (P = mk_parties:
+    // a bootstrapping key loaded for another party count drops the set), and the party each sample was expanded for, [S] on the device
+    cplx *d_mk_tgsw = nullptr;     int64_t mk_tgsw_count = 0;
+    int32_t *d_mk_tgsw_party = nullptr;
     size_t diag_rows = 0;
     bool mk_force_general = false; // tfhe_set_option("mk_general", 1): use the any-P kernel for 2 parties too (cross-check)
     int n2048_rw = 0;              // N = 2048: rotations per workgroup advancing in lockstep (tfhe_set_option("n2048_rw", 0|1|2); 0 = one up to
@@ -430,6 +436,8 @@ void shard_bounds_by_rotations(const uint8_t *opcodes, int64_t B, int shards, in
 void quiesce(tfhe_ctx *c);
 // Int32 polynomials -> spectra in the any-N kernels' order, scaled 1/M (forward_transform(::TGswSample), tgsw.jl:120-121), on `s`
 int32_t tgsw_prepare(tfhe_ctx *c, const int32_t *d_polys, cplx *d_out, size_t npolys, hipStream_t s);
+// frees the multi-key selector set (the caller has quiesced the context)
+void mk_tgsw_drop(tfhe_ctx *c);
 // engine_dispatch.hip
 struct DiagArgs;
 int32_t prepare_diag(tfhe_ctx *c, size_t R, hipStream_t s, DiagArgs &d);
@@ -505,5 +513,9 @@ int32_t br_launch_k2(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hi
 int32_t br_launch_h2(tfhe_ctx *c, const WithTv<BrArgs> &a, const H2Tables &ht, const BrLaunch &g, hipStream_t s);
 int32_t br_launch_w2(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
 int32_t br_launch_v3(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
+// engine_leveled.hip: grows the workspaces of one leveled call, all or none, after comparing what they would grow by with the device's
+// free memory (TFHE_ERR_NOMEM before anything is allocated)
+struct LvlWant { DevBuf *buf; size_t bytes; };
+int32_t leveled_reserve(tfhe_ctx *c, const char *who, const LvlWant *want, int count);
 // engine_circuits.hip
 int32_t pull_wires(tfhe_ctx *c, int dst, const int32_t *wires, int64_t count);

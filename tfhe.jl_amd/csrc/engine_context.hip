@@ -321,6 +321,7 @@ void tfhe_ctx_destroy(tfhe_ctx *c)
     if (c->d_wires) (void)hipFree(c->d_wires);
     if (c->d_mk_bk) (void)hipFree(c->d_mk_bk);
     if (c->d_tgsw) (void)hipFree(c->d_tgsw);
+    mk_tgsw_drop(c);
     c->lvl_ws[0].release(); c->lvl_ws[1].release(); c->lvl_data.release(); c->lvl_spec.release();
     c->bara.release(); c->ext.release(); c->map.release(); c->diag.release(); c->abar.release(); c->mk_acc.release(); c->spec.release(); c->tv.release(); c->tv_index.release(); c->tv_bodies.release(); c->tv_ext.release();
     for (auto &b : c->io) b.release();

@@ -254,11 +254,12 @@ int32_t tfhe_keygen_cloud_key(tfhe_ctx *c, const int32_t *lwe_key, const int32_t
 }
 ABI_CATCH(c, "tfhe_keygen_cloud_key")
 
-// key preparation for whichever kernel family serves this context: Int32 polynomials -> spectra (`scale` folded in), on `s`
-static int32_t launch_bk_prepare(tfhe_ctx *c, const int32_t *d_polys, cplx *d_out, size_t npolys, double scale_if_tuned, bool key_scale, hipStream_t s)
+// key preparation for one kernel family (`any`: the any-N kernels' spectrum order, else the tuned N = 1024 kernels'): Int32 polynomials
+// -> spectra (`scale` folded in), on `s`
+static int32_t launch_bk_prepare(tfhe_ctx *c, bool any, const int32_t *d_polys, cplx *d_out, size_t npolys, double scale_if_tuned, bool key_scale, hipStream_t s)
 {
     if (npolys == 0) return TFHE_OK;
-    if (c->anyn()) {
+    if (any) {
         const int log2N = ilog2i(c->P.N), M = c->P.N / 2;
         const size_t ldsp = (size_t)anyn::padded_len(M > 0 ? M : 1) * sizeof(cplx);
         if (ldsp > 64 * 1024) LDS_TRY(c, ldsp, anyn::bk_prepare_kernel);
@@ -335,6 +336,7 @@ static int32_t mk_load_bk_common(tfhe_ctx *c, const void *bk, int32_t parties, b
     const size_t npolys = (size_t)parties * c->P.n * per;
     const size_t bytes_in = is_c128 ? npolys * M * sizeof(cplx) : npolys * N * 4;
     quiesce(c);
+    if (c->mk_parties != parties) mk_tgsw_drop(c);      // a selector set expanded for another party count
     if (c->d_mk_bk) { (void)hipFree(c->d_mk_bk); c->d_mk_bk = nullptr; c->have_mk_bk = false; }
     HIP_TRY(c, hipMalloc((void **)&c->d_mk_bk, npolys * M * sizeof(cplx)));
     void *d_in = nullptr;
@@ -349,7 +351,7 @@ static int32_t mk_load_bk_common(tfhe_ctx *c, const void *bk, int32_t parties, b
             hipLaunchKernelGGL(bk_permute_c128_kernel, dim3((unsigned)npolys), dim3(64), 0, c->stream, (const cplx *)d_in, c->d_mk_bk);
             HIP_TRY(c, hipGetLastError());
         } else {
-            const int32_t rcp = launch_bk_prepare(c, (const int32_t *)d_in, c->d_mk_bk, npolys, 1.0 / kM, true, c->stream);
+            const int32_t rcp = launch_bk_prepare(c, c->anyn(), (const int32_t *)d_in, c->d_mk_bk, npolys, 1.0 / kM, true, c->stream);
             if (rcp) return rcp;
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -375,7 +377,84 @@ int32_t tfhe_mk_load_bootstrap_key_c128(tfhe_ctx *c, const double *bk_spectra, i
 }
 ABI_CATCH(c, "tfhe_mk_load_bootstrap_key_c128")
 
-// RGSW.Expand on the device (mk_internals.jl:304-345, MKBootstrapKey :442-461): the parties' uni-encryptions and public
+// ---- RGSW.Expand on the device (mk_internals.jl:304-345) ------------------------------------------------------------------------
+// One party's uni-encryptions (`cnt` of them: its n key bits, MKBootstrapKey :442-461, or its share of a selector set,
+// tfhe_mk_tgsw_expand_load) expanded against all public keys into d_key [cnt][2 l P + 2 l][N].  The scratch is sized once for the
+// largest cnt of a call and reused party by party.
+struct MkExpandWork {
+    int32_t *d_in = nullptr, *d_dec = nullptr, *d_key = nullptr;      // the 6 uni-encryption arrays, the digit polynomials, the expanded slice
+    cplx *d_decs = nullptr, *d_fs = nullptr;                          // the digit spectra, the f0 / f1 spectra
+    std::vector<int32_t> h_dec;
+    void release()
+    {
+        if (d_in) (void)hipFree(d_in);
+        if (d_dec) (void)hipFree(d_dec);
+        if (d_key) (void)hipFree(d_key);
+        if (d_decs) (void)hipFree(d_decs);
+        if (d_fs) (void)hipFree(d_fs);
+        d_in = d_dec = d_key = nullptr; d_decs = d_fs = nullptr;
+    }
+};
+static int32_t mk_expand_alloc(tfhe_ctx *c, MkExpandWork &w, int P, size_t cap)
+{
+    const int l = c->P.bs_l;
+    const size_t N = (size_t)c->P.N, M = N / 2, per = (size_t)2 * l * P + 2 * l, ndec = (size_t)(P - 1) * l * l;
+    HIP_TRY(c, hipMalloc((void **)&w.d_in, 6 * cap * l * N * 4));
+    HIP_TRY(c, hipMalloc((void **)&w.d_dec, ndec * N * 4));
+    HIP_TRY(c, hipMalloc((void **)&w.d_decs, ndec * M * sizeof(cplx)));
+    HIP_TRY(c, hipMalloc((void **)&w.d_fs, 2 * cap * l * M * sizeof(cplx)));
+    HIP_TRY(c, hipMalloc((void **)&w.d_key, cap * per * N * 4));
+    alloc_checkpoint();
+    w.h_dec.resize(ndec * N);
+    return TFHE_OK;
+}
+// src: party i's c0, c1, d0, d1, f0, f1, host int32 [cnt][l][N] each; `any`: the any-N kernels' transform (else the tuned N = 1024 one).
+// Queued on `s`; the caller synchronises before the scratch is reused.
+static int32_t mk_expand_party(tfhe_ctx *c, MkExpandWork &w, bool any, int P, int i, int cnt, const int32_t *pub_b, const int32_t *const src[6], hipStream_t s)
+{
+    const int l = c->P.bs_l;
+    const size_t N = (size_t)c->P.N, M = N / 2;
+    const size_t nl = (size_t)cnt * l;                   // polys of this party in each of c0 .. f1
+    const size_t ndec = (size_t)(P - 1) * l * l;
+    // g^-1(b_q[jj] - b_i[jj])[u] for every other party q (tgsw.jl:99-117): [oq][u][jj][N]
+    int oq = 0;
+    for (int q = 0; q < P; q++) {
+        if (q == i) continue;
+        for (int jj = 0; jj < l; jj++) {
+            const int32_t *bq = pub_b + ((size_t)q * l + jj) * N, *bi = pub_b + ((size_t)i * l + jj) * N;
+            for (size_t t = 0; t < N; t++) {
+                const int32_t v = (int32_t)((uint32_t)bq[t] - (uint32_t)bi[t] + (uint32_t)c->g.offset);
+                for (int u = 0; u < l; u++) w.h_dec[(((size_t)oq * l + u) * l + jj) * N + t] = gadget_digit(v, u + 1, c->g);
+            }
+        }
+        oq++;
+    }
+    for (int a = 0; a < 6; a++)
+        HIP_TRY(c, hipMemcpyAsync(w.d_in + (size_t)a * nl * N, src[a], nl * N * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(w.d_dec, w.h_dec.data(), ndec * N * 4, hipMemcpyHostToDevice, s));
+    const int32_t *dc0 = w.d_in, *dc1 = w.d_in + nl * N, *dd0 = w.d_in + 2 * nl * N, *dd1 = w.d_in + 3 * nl * N, *df = w.d_in + 4 * nl * N;
+    int32_t rcp = launch_bk_prepare(c, any, (const int32_t *)w.d_dec, w.d_decs, ndec, 1.0, false, s);        // multiplier polynomials: unscaled
+    if (rcp) return rcp;
+    rcp = launch_bk_prepare(c, any, df, w.d_fs, 2 * nl, 1.0 / kM, true, s);                                // f0 then f1
+    if (rcp) return rcp;
+    if (any) {
+        anyn::MkExpandArgs A;
+        A.dec = w.d_decs; A.f = w.d_fs; A.d0 = dd0; A.key = w.d_key; A.wtab = c->d_anyn_tab; A.twist = c->d_anyn_tab + M;
+        A.n = cnt; A.l = l; A.parties = P; A.party = i; A.log2N = ilog2i(c->P.N);
+        const size_t ldsp = (size_t)anyn::padded_len(M > 0 ? (int)M : 1) * sizeof(cplx);
+        if (ldsp > 64 * 1024) LDS_TRY(c, ldsp, anyn::mk_expand_kernel);
+        hipLaunchKernelGGL(anyn::mk_expand_kernel, dim3((unsigned)cnt, (unsigned)(l * (P - 1)), 2), dim3((unsigned)anyn::threads_for(c->P.N)), ldsp, s, A);
+    } else {
+        MkExpandArgs A;
+        A.dec = w.d_decs; A.f = w.d_fs; A.d0 = dd0; A.key = w.d_key; A.T = c->T; A.n = cnt; A.l = l; A.parties = P; A.party = i;
+        hipLaunchKernelGGL(mk_expand_kernel, dim3((unsigned)cnt, (unsigned)(l * (P - 1)), 2), dim3(64), 0, s, A);
+    }
+    hipLaunchKernelGGL(mk_expand_copy_kernel, dim3((unsigned)cnt, (unsigned)l, 4), dim3(256), 0, s, dc0, dc1, dd0, dd1, w.d_key, cnt, l, P, i, (int)N);
+    HIP_TRY(c, hipGetLastError());
+    return TFHE_OK;
+}
+
+// RGSW.Expand of the bootstrapping key (MKBootstrapKey, mk_internals.jl:442-461): the parties' uni-encryptions and public
 // keys in, the expanded transformed bootstrapping key resident on the device out.
 int32_t tfhe_mk_expand_load_bootstrap_key(tfhe_ctx *c, int32_t parties, const int32_t *pub_b, const int32_t *c0, const int32_t *c1,
                                           const int32_t *d0, const int32_t *d1, const int32_t *f0, const int32_t *f1, int32_t *expanded_out) try
@@ -400,76 +479,30 @@ int32_t tfhe_mk_expand_load_bootstrap_key(tfhe_ctx *c, int32_t parties, const in
     const size_t nl = (size_t)n * l;                   // polys per party in each of c0 .. f1
     c->have_mk_bk = false;
     quiesce(c);
+    if (c->mk_parties != parties) mk_tgsw_drop(c);      // a selector set expanded for another party count
     if (c->d_mk_bk) { (void)hipFree(c->d_mk_bk); c->d_mk_bk = nullptr; }
     HIP_TRY(c, hipMalloc((void **)&c->d_mk_bk, npolys * M * sizeof(cplx)));
-    // scratch: the party's 6 uni-encryption arrays, the digit polynomials and their spectra, f0 / f1 spectra, the party's key slice
-    int32_t *d_in = nullptr, *d_dec = nullptr, *d_key = nullptr;
-    cplx *d_decs = nullptr, *d_fs = nullptr;
-    const size_t ndec = (size_t)(P - 1) * l * l;
-    auto cleanup = [&]() {
-        if (d_in) (void)hipFree(d_in);
-        if (d_dec) (void)hipFree(d_dec);
-        if (d_key) (void)hipFree(d_key);
-        if (d_decs) (void)hipFree(d_decs);
-        if (d_fs) (void)hipFree(d_fs);
-    };
+    MkExpandWork w;
     auto body = [&]() -> int32_t {
-        HIP_TRY(c, hipMalloc((void **)&d_in, 6 * nl * N * 4));
-        HIP_TRY(c, hipMalloc((void **)&d_dec, ndec * N * 4));
-        HIP_TRY(c, hipMalloc((void **)&d_decs, ndec * M * sizeof(cplx)));
-        HIP_TRY(c, hipMalloc((void **)&d_fs, 2 * nl * M * sizeof(cplx)));
-        HIP_TRY(c, hipMalloc((void **)&d_key, (size_t)n * per * N * 4));
-        alloc_checkpoint();
-        std::vector<int32_t> h_dec(ndec * N);
+        int32_t rcp = mk_expand_alloc(c, w, P, (size_t)n);
+        if (rcp) return rcp;
         hipStream_t s = c->stream;
         for (int i = 0; i < P; i++) {
-            // g^-1(b_q[jj] - b_i[jj])[u] for every other party q (tgsw.jl:99-117): [oq][u][jj][N]
-            int oq = 0;
-            for (int q = 0; q < P; q++) {
-                if (q == i) continue;
-                for (int jj = 0; jj < l; jj++) {
-                    const int32_t *bq = pub_b + ((size_t)q * l + jj) * N, *bi = pub_b + ((size_t)i * l + jj) * N;
-                    for (size_t t = 0; t < N; t++) {
-                        const int32_t v = (int32_t)((uint32_t)bq[t] - (uint32_t)bi[t] + (uint32_t)c->g.offset);
-                        for (int u = 0; u < l; u++) h_dec[(((size_t)oq * l + u) * l + jj) * N + t] = gadget_digit(v, u + 1, c->g);
-                    }
-                }
-                oq++;
-            }
             const int32_t *src[6] = {c0, c1, d0, d1, f0, f1};
-            for (int a = 0; a < 6; a++)
-                HIP_TRY(c, hipMemcpyAsync(d_in + (size_t)a * nl * N, src[a] + (size_t)i * nl * N, nl * N * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(d_dec, h_dec.data(), ndec * N * 4, hipMemcpyHostToDevice, s));
-            const int32_t *dc0 = d_in, *dc1 = d_in + nl * N, *dd0 = d_in + 2 * nl * N, *dd1 = d_in + 3 * nl * N, *df = d_in + 4 * nl * N;
-            int32_t rcp = launch_bk_prepare(c, (const int32_t *)d_dec, d_decs, ndec, 1.0, false, s);        // multiplier polynomials: unscaled
+            for (auto &a : src) a += (size_t)i * nl * N;
+            rcp = mk_expand_party(c, w, any, P, i, n, pub_b, src, s);
             if (rcp) return rcp;
-            rcp = launch_bk_prepare(c, df, d_fs, 2 * nl, 1.0 / kM, true, s);                              // f0 then f1
-            if (rcp) return rcp;
-            if (any) {
-                anyn::MkExpandArgs A;
-                A.dec = d_decs; A.f = d_fs; A.d0 = dd0; A.key = d_key; A.wtab = c->d_anyn_tab; A.twist = c->d_anyn_tab + M;
-                A.n = n; A.l = l; A.parties = P; A.party = i; A.log2N = ilog2i(c->P.N);
-                const size_t ldsp = (size_t)anyn::padded_len(M > 0 ? (int)M : 1) * sizeof(cplx);
-                if (ldsp > 64 * 1024) LDS_TRY(c, ldsp, anyn::mk_expand_kernel);
-                hipLaunchKernelGGL(anyn::mk_expand_kernel, dim3((unsigned)n, (unsigned)(l * (P - 1)), 2), dim3((unsigned)anyn::threads_for(c->P.N)), ldsp, s, A);
-            } else {
-                MkExpandArgs A;
-                A.dec = d_decs; A.f = d_fs; A.d0 = dd0; A.key = d_key; A.T = c->T; A.n = n; A.l = l; A.parties = P; A.party = i;
-                hipLaunchKernelGGL(mk_expand_kernel, dim3((unsigned)n, (unsigned)(l * (P - 1)), 2), dim3(64), 0, s, A);
-            }
-            hipLaunchKernelGGL(mk_expand_copy_kernel, dim3((unsigned)n, (unsigned)l, 4), dim3(256), 0, s, dc0, dc1, dd0, dd1, d_key, n, l, P, i, (int)N);
-            HIP_TRY(c, hipGetLastError());
-            rcp = launch_bk_prepare(c, (const int32_t *)d_key, c->d_mk_bk + (size_t)i * n * per * M, (size_t)n * per, 1.0 / kM, true, s);
+            rcp = launch_bk_prepare(c, any, (const int32_t *)w.d_key, c->d_mk_bk + (size_t)i * n * per * M, (size_t)n * per, 1.0 / kM, true, s);
             if (rcp) return rcp;
             if (expanded_out)
-                HIP_TRY(c, hipMemcpyAsync(expanded_out + (size_t)i * n * per * N, d_key, (size_t)n * per * N * 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(c, hipMemcpyAsync(expanded_out + (size_t)i * n * per * N, w.d_key, (size_t)n * per * N * 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));      // h_dec and the scratch buffers are reused by the next party
         }
         return TFHE_OK;
     };
     int32_t rc;
     {
-        auto guard = on_exit(cleanup);      // (also when body() ends in an exception: h_dec is gigabytes at hundreds of parties)
+        auto guard = on_exit([&] { w.release(); });      // (also when body() ends in an exception: h_dec is gigabytes at hundreds of parties)
         rc = body();
     }
     if (rc) return rc;
@@ -478,6 +511,137 @@ int32_t tfhe_mk_expand_load_bootstrap_key(tfhe_ctx *c, int32_t parties, const in
     return TFHE_OK;
 }
 ABI_CATCH(c, "tfhe_mk_expand_load_bootstrap_key")
+
+// ---- the selector set of the multi-key leveled mode (engine_mk_leveled.hip) -------------------------------------------------------
+void mk_tgsw_drop(tfhe_ctx *c)
+{
+    if (c->d_mk_tgsw) (void)hipFree(c->d_mk_tgsw);
+    if (c->d_mk_tgsw_party) (void)hipFree(c->d_mk_tgsw_party);
+    c->d_mk_tgsw = nullptr; c->d_mk_tgsw_party = nullptr; c->mk_tgsw_count = 0;
+}
+
+// what both loaders refuse before they touch the device; *per = polynomials of one expanded sample
+static int32_t mk_tgsw_check(tfhe_ctx *c, const char *who, const int32_t *party_of, int64_t S, int32_t parties, size_t *per)
+{
+    if (!party_of || S < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL pointer or no sample", who);
+    if (c->P.parties < 2) return c->set_err(TFHE_ERR_STATE, "%s: context is single-key (tfhe_tgsw_load is its selector loader)", who);
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "%s: multi-device context (leveled operations run on a one-device context)", who);
+    if (!c->have_mk_bk) return c->set_err(TFHE_ERR_NO_KEY, "%s: no multi-key bootstrapping key loaded (it fixes the party count)", who);
+    if (parties != c->mk_parties)
+        return c->set_err(TFHE_ERR_STATE, "%s: parties = %d, the multi-key bootstrapping key was loaded for %d", who, parties, c->mk_parties);
+    *per = (size_t)2 * c->P.bs_l * parties + 2 * c->P.bs_l;
+    if ((double)S * (double)*per > 2147483647.0) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: S = %lld samples are more than one launch prepares", who, (long long)S);
+    for (int64_t s = 0; s < S; s++)
+        if (party_of[s] < 0 || party_of[s] >= parties)
+            return c->set_err(TFHE_ERR_INVALID_ARG, "%s: party_of[%lld] = %d is outside the %d parties", who, (long long)s, party_of[s], parties);
+    return TFHE_OK;
+}
+
+// Replaces the selector set by S samples: allocates the store (compared with the free memory first), uploads party_of, and hands
+// `fill` the spectra buffer to write [S][per][M] into on the context's stream.  All or nothing: a failure leaves no selector set.
+template <typename F>
+static int32_t mk_tgsw_replace(tfhe_ctx *c, const char *who, const int32_t *party_of, int64_t S, size_t per, double scratch_bytes, F &&fill)
+{
+    const size_t npolys = (size_t)S * per, M = (size_t)(c->P.N / 2 > 0 ? c->P.N / 2 : 1);
+    quiesce(c);
+    mk_tgsw_drop(c);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+    if (scratch_bytes + (double)npolys * (double)M * sizeof(cplx) + (double)S * 4 > (double)free_b)
+        return c->set_err(TFHE_ERR_NOMEM, "%s: %lld samples do not fit the device's free memory", who, (long long)S);
+    auto body = [&]() -> int32_t {
+        HIP_TRY(c, hipMalloc((void **)&c->d_mk_tgsw, npolys * M * sizeof(cplx)));
+        HIP_TRY(c, hipMalloc((void **)&c->d_mk_tgsw_party, (size_t)S * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->d_mk_tgsw_party, party_of, (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
+        const int32_t rc = fill(c->d_mk_tgsw);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return TFHE_OK;
+    };
+    const int32_t rc = body();
+    if (rc) { mk_tgsw_drop(c); return rc; }
+    c->mk_tgsw_count = S;
+    return TFHE_OK;
+}
+
+// S caller-expanded RGSW samples as the selector set of tfhe_mk_extern_mul_batch / tfhe_mk_cmux_tree_batch
+int32_t tfhe_mk_tgsw_load(tfhe_ctx *c, const int32_t *tgsw, const int32_t *party_of, int64_t S, int32_t parties) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    if (!tgsw) return c->set_err(TFHE_ERR_INVALID_ARG, "mk_tgsw_load: NULL pointer");
+    size_t per = 0;
+    int32_t rc = mk_tgsw_check(c, "mk_tgsw_load", party_of, S, parties, &per);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = check_key_source(c, tgsw, "mk_tgsw_load");
+    if (rc) return rc;
+    const size_t npolys = (size_t)S * per, bytes_in = npolys * (size_t)c->P.N * 4;
+    void *d_in = nullptr;
+    auto guard = on_exit([&] { if (d_in) (void)hipFree(d_in); });
+    return mk_tgsw_replace(c, "mk_tgsw_load", party_of, S, per, (double)bytes_in, [&](cplx *d_out) -> int32_t {
+        HIP_TRY(c, hipMalloc(&d_in, bytes_in));
+        HIP_TRY(c, hipMemcpyAsync(d_in, tgsw, bytes_in, hipMemcpyDefault, c->stream));
+        return tgsw_prepare(c, (const int32_t *)d_in, d_out, npolys, c->stream);
+    });
+}
+ABI_CATCH(c, "tfhe_mk_tgsw_load")
+
+// The same store built from what the parties publish: the selectors are grouped by party and every party's group goes through
+// mk_expand_party (the expand path of the bootstrapping key, with the group's size in the place of n), on the any-N kernels'
+// transform since that is the order the CMUX level kernel reads.
+int32_t tfhe_mk_tgsw_expand_load(tfhe_ctx *c, int32_t parties, const int32_t *pub_b, const int32_t *party_of, const int32_t *c0, const int32_t *c1,
+                                 const int32_t *d0, const int32_t *d1, const int32_t *f0, const int32_t *f1, int64_t S, int32_t *expanded_out) try
+{
+    ENTER_CTX(c);
+    if (!c) return TFHE_ERR_INVALID_ARG;
+    if (!pub_b || !c0 || !c1 || !d0 || !d1 || !f0 || !f1) return c->set_err(TFHE_ERR_INVALID_ARG, "mk_tgsw_expand_load: NULL argument");
+    size_t per = 0;
+    int32_t rc = mk_tgsw_check(c, "mk_tgsw_expand_load", party_of, S, parties, &per);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int l = c->P.bs_l, P = parties;
+    const size_t N = (size_t)c->P.N, M = N / 2 > 0 ? N / 2 : 1, lN = (size_t)l * N;
+    alloc_checkpoint();
+    std::vector<std::vector<int64_t>> of((size_t)P);      // the selectors of each party, in the caller's order
+    for (int64_t s = 0; s < S; s++) of[(size_t)party_of[s]].push_back(s);
+    size_t cap = 0;
+    for (const auto &v : of) cap = std::max(cap, v.size());
+    const size_t ndec = (size_t)(P - 1) * l * l;
+    const double scratch = (6.0 * cap * lN + (double)ndec * N + (double)cap * per * N) * 4 + ((double)ndec + 2.0 * cap * l) * M * sizeof(cplx);
+    MkExpandWork w;
+    auto guard = on_exit([&] { w.release(); });
+    return mk_tgsw_replace(c, "mk_tgsw_expand_load", party_of, S, per, scratch, [&](cplx *d_out) -> int32_t {
+        int32_t rcp = mk_expand_alloc(c, w, P, cap);
+        if (rcp) return rcp;
+        hipStream_t s = c->stream;
+        std::vector<int32_t> h_in(6 * cap * lN), h_key(expanded_out ? cap * per * N : 0);
+        const int32_t *arr[6] = {c0, c1, d0, d1, f0, f1};
+        for (int i = 0; i < P; i++) {
+            const std::vector<int64_t> &mine = of[(size_t)i];
+            const size_t cnt = mine.size();
+            if (cnt == 0) continue;
+            const int32_t *src[6];
+            for (int a = 0; a < 6; a++) {
+                int32_t *dst = h_in.data() + (size_t)a * cnt * lN;
+                for (size_t j = 0; j < cnt; j++) memcpy(dst + j * lN, arr[a] + (size_t)mine[j] * lN, lN * 4);
+                src[a] = dst;
+            }
+            rcp = mk_expand_party(c, w, true, P, i, (int)cnt, pub_b, src, s);
+            if (rcp) return rcp;
+            for (size_t j = 0; j < cnt; j++) {      // sample j of the group is selector mine[j]
+                rcp = tgsw_prepare(c, w.d_key + j * per * N, d_out + (size_t)mine[j] * per * M, per, s);
+                if (rcp) return rcp;
+            }
+            if (expanded_out) HIP_TRY(c, hipMemcpyAsync(h_key.data(), w.d_key, cnt * per * N * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));      // h_in, h_dec and the scratch buffers are reused by the next party
+            if (expanded_out)
+                for (size_t j = 0; j < cnt; j++) memcpy(expanded_out + (size_t)mine[j] * per * N, h_key.data() + j * per * N, per * N * 4);
+        }
+        return TFHE_OK;
+    });
+}
+ABI_CATCH(c, "tfhe_mk_tgsw_expand_load")
 
 int32_t tfhe_mk_load_keyswitch_key(tfhe_ctx *c, const int32_t *ks, int32_t parties) try
 {

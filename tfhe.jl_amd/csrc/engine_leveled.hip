@@ -16,8 +16,7 @@ static int32_t leveled_state(tfhe_ctx *c, const char *who)
 // Grows the workspaces of one call, all or none: what they would have to grow by is compared with the device's free memory
 // BEFORE anything is allocated, so a request the device cannot hold is refused (TFHE_ERR_NOMEM) without a failed hipMalloc
 // behind it, and the buffers the context already holds stay as they are.
-struct LvlWant { DevBuf *buf; size_t bytes; };
-static int32_t leveled_reserve(tfhe_ctx *c, const char *who, const LvlWant *want, int count)
+int32_t leveled_reserve(tfhe_ctx *c, const char *who, const LvlWant *want, int count)
 {
     double grow = 0.0;      // (a double: the sum of an absurd request must not wrap)
     for (int i = 0; i < count; i++)

@@ -11,12 +11,20 @@ The host side mirrors the reference's constructors under the TLWE key that Cloud
 `secret_key.tlwe_key`: tlwe_encrypt (tlwe.jl:63-73 plus a message on the body), tgsw_encrypt_bits (tgsw.jl:84-88 at
 bs_noise_stddev).  The device side is Engine.tgsw_load / extern_mul / cmux_tree (tfhe_tgsw_load, tfhe_extern_mul_batch,
 tfhe_cmux_tree_batch); cmux_lookup strings them together.
+
+Under a multi-key cloud key (the mk_* functions below) the selectors are jointly encrypted: each party uni-encrypts the address bits
+it owns (mk_tgsw_uni_encrypt_bits: RGSW.UniEnc, mk_internals.jl:185-227) under the TLWE key that CloudKeyPart(..., keep_tlwe_key=True)
+keeps, the cloud expands them against all public keys (mk_tgsw_expand: RGSW.Expand, :304-345; or on the device) and folds a table of
+MK TLWE samples [P+1][N] with mk_tgsw_extern_mul (:348-391).  Keyswitched (out_form 2) the result is a multi-key LWE sample that
+mk_decrypt and every mk_gate accept.  Engine.mk_tgsw_load / mk_tgsw_expand_load / mk_extern_mul / mk_cmux_tree; mk_cmux_lookup strings
+them together.
 """
 import numpy as np
 
+from . import mk_keys
 from .keys import _tlwe_encrypt_zero_many, make_bootstrap_key
 from .lwe import LweKey, LweSampleArray
-from .numeric import negacyclic_mul_binary, wrap32
+from .numeric import dtot32, negacyclic_mul_binary, rand_uniform_torus32, wrap32
 
 
 def _tlwe_key(secret_key):
@@ -100,3 +108,85 @@ def cmux_lookup(ck, tables, address_tgsw, out_form=2, device=0, table_index=None
     sel = np.arange(B * depth, dtype=np.int32).reshape(B, depth)
     out = eng.cmux_tree(tables, sel, table_index=table_index, out_form=out_form)
     return LweSampleArray(out) if out_form == 2 else out
+
+
+# ---- under a multi-key cloud key -------------------------------------------------------------------------------------------------
+def mk_tlwe_trivial(polys, parties):
+    """mk_tlwe_noiseless_trivial (mk_internals.jl:69-76) of each message polynomial: int32 [..., N] -> int32 [count][P+1][N], zero masks."""
+    return tlwe_trivial(polys, parties)
+
+
+def _mk_tlwe_keys(tlwe_keys):
+    if any(k is None for k in tlwe_keys):
+        raise ValueError("a party's TLWE key is missing: CloudKeyPart(rng, secret_key, shared_key, keep_tlwe_key=True) keeps it as .tlwe_key")
+    return np.stack([k.key[0] for k in tlwe_keys])                       # [P][N] (mask_size = 1, mk_internals.jl:129)
+
+
+def mk_tlwe_encrypt(rng, tlwe_keys, alpha, polys):
+    """An MKTLweSample (mk_internals.jl:46-57) of each Torus32 message polynomial under the P parties' TLWE keys: uniform masks a_p,
+    b = sum_p a_p (*) s_p + e + mu with Gaussian e of standard deviation alpha; int32 [..., N] -> int32 [count][P+1][N]."""
+    s = _mk_tlwe_keys(tlwe_keys)
+    P, N = s.shape
+    mu = np.atleast_2d(np.asarray(polys, np.int32))
+    if mu.shape[1] != N:
+        raise ValueError(f"message polynomials must have {N} coefficients, got {mu.shape[1]}")
+    a = rand_uniform_torus32(rng, mu.shape[0], P, N)
+    b = mu.astype(np.int64) + dtot32(rng.standard_normal(size=mu.shape) * alpha).astype(np.int64)
+    for p in range(P):
+        b = b + negacyclic_mul_binary(s[p], a[:, p, :]).astype(np.int64)
+    return np.concatenate([a, wrap32(b)[:, None, :]], axis=1).astype(np.int32)
+
+
+def mk_tlwe_phase(tlwe_keys, samples):
+    """b - sum_p a_p (*) s_p (negacyclic) of MK TLWE samples int32 [count][P+1][N]: the noisy message polynomials [count][N]."""
+    s = _mk_tlwe_keys(tlwe_keys)
+    P = s.shape[0]
+    x = np.asarray(samples, np.int32)
+    if x.ndim == 2:
+        x = x[None]
+    ph = x[:, P, :].astype(np.int64)
+    for p in range(P):
+        ph = ph - negacyclic_mul_binary(s[p], x[:, p, :]).astype(np.int64)
+    return wrap32(ph)
+
+
+def mk_tgsw_uni_encrypt_bits(rng, tlwe_key, shared_key, public_b, bits):
+    """mk_tgsw_encrypt (RGSW.UniEnc, mk_internals.jl:185-227) of each bit at bs_noise_stddev under one party's TLWE key and public key
+    public_b [l][N]: the six arrays (c0, c1, d0, d1, f0, f1), int32 [S][l][N] each — what CloudKeyPart makes of its LWE key's bits."""
+    m = np.asarray(bits).astype(bool).reshape(-1).astype(np.int64)
+    return mk_keys._uni_encrypt(rng, shared_key.params, tlwe_key.key[0], shared_key.a, public_b, m)
+
+
+def mk_tgsw_expand(params, public_bs, party, c0, c1, d0, d1, f0, f1):
+    """mk_tgsw_expand (RGSW.Expand, mk_internals.jl:304-345) of one party's uni-encryptions [S][l][N] against all public keys
+    public_bs [P][l][N]: int32 [S][2lP + 2l][N], each sample x[l][P] | y[l][P] | c0[l] | c1[l] as an entry of the multi-key
+    bootstrapping key (MKCloudKey expands its parts through the same function)."""
+    return mk_keys._expand(params, list(public_bs), int(party), *(np.asarray(v, np.int32) for v in (c0, c1, d0, d1, f0, f1)))
+
+
+def mk_cmux_lookup(ck, tables, uni_bits, party_of, out_form=2, expand="device", device=0, table_index=None):
+    """table[address] for B jointly encrypted addresses under the MKCloudKey ck.  tables: int32 [2^d][P+1][N] or [T][2^d][P+1][N] with
+    table_index [B]; uni_bits: the six arrays of mk_tgsw_uni_encrypt_bits, each [B][d][l][N], bit v of address g uni-encrypted by party
+    party_of[g][v] (party_of: [B][d], or [d] for every row).  expand "device": RGSW.Expand on the GPU (tfhe_mk_tgsw_expand_load),
+    "host": numpy (mk_tgsw_expand) then mk_tgsw_load.  out_form 2 (default): multi-key LWE samples int32 [B][P*n+1] for mk_decrypt /
+    mk_gate_*; 1: extracted [B][P*N+1]; 0: MK TLWE samples [B][P+1][N]."""
+    assert expand in ("device", "host")
+    arrs = [np.asarray(a, np.int32) for a in uni_bits]
+    if len(arrs) != 6 or arrs[0].ndim != 4 or any(a.shape != arrs[0].shape for a in arrs):
+        raise ValueError("uni_bits must be six arrays [B][depth][l][N]")
+    B, depth = arrs[0].shape[:2]
+    who = np.broadcast_to(np.asarray(party_of, np.int32), (B, depth)).reshape(-1)
+    flat = [a.reshape((B * depth,) + a.shape[2:]) for a in arrs]
+    pub = np.stack([part.public_b for part in ck._parts])
+    eng = ck.engine(device)
+    if expand == "device":
+        eng.mk_tgsw_expand_load(pub, who, *flat)
+    else:
+        tg = np.zeros((B * depth, 2 * arrs[0].shape[2] * (ck.parties + 1), arrs[0].shape[3]), np.int32)
+        for i in range(ck.parties):
+            mine = np.nonzero(who == i)[0]
+            if mine.size:
+                tg[mine] = mk_tgsw_expand(ck.params, pub, i, *[a[mine] for a in flat])
+        eng.mk_tgsw_load(tg, who)
+    sel = np.arange(B * depth, dtype=np.int32).reshape(B, depth)
+    return eng.mk_cmux_tree(tables, sel, table_index=table_index, out_form=out_form)

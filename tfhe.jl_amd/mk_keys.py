@@ -28,34 +28,76 @@ def _gauss_poly(rng, alpha, *shape):
     return dtot32(rng.standard_normal(size=shape) * alpha).astype(np.int64)
 
 
+def _uni_encrypt(rng, params, s, a, public_b, m):
+    """RGSW.UniEnc (mk_tgsw_encrypt, mk_internals.jl:185-227) of the messages m (int64 [count]) under one party's TLWE key polynomial s,
+    the shared polynomials a [l][N] and that party's public key public_b [l][N]: (c0, c1, d0, d1, f0, f1), int32 [count][l][N] each."""
+    N, l, alpha = params.tlwe_polynomial_degree, params.bs_decomp_length, params.bs_noise_stddev
+    n = m.size
+    gadget = np.array([1 << (32 - (q + 1) * params.bs_log2_base) for q in range(l)], np.int64)
+    r = rand_uniform_bool(rng, n, N)                                # :197
+    c1 = rand_uniform_torus32(rng, n, l, N)                         # :200
+    c0 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(s, c1).astype(np.int64)   # :202-206
+    c0[:, :, 0] += m[:, None] * gadget[None, :]                     # + message * gadget (constant term)
+    d1 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(r[:, None, :], a[None]).astype(np.int64)   # :209-213
+    d1[:, :, 0] += m[:, None] * gadget[None, :]
+    d0 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(r[:, None, :], public_b[None]).astype(np.int64)  # :214-217
+    f1 = rand_uniform_torus32(rng, n, l, N)                         # :220
+    f0 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(s, f1).astype(np.int64)   # :222-226
+    f0 += r[:, None, :].astype(np.int64) * gadget[None, :, None]    # + r * gadget (every coefficient)
+    return tuple(wrap32(v) for v in (c0, c1, d0, d1, f0, f1))
+
+
+def _expand(params, pub, i, c0, c1, d0, d1, f0, f1):
+    """RGSW.Expand (mk_tgsw_expand, mk_internals.jl:304-345) of party i's uni-encryptions [count][l][N] against the public keys pub
+    [P][l][N]: int32 [count][2 l P + 2 l][N], per sample x[l][P] | y[l][P] | c0[l] | c1[l]."""
+    P = len(pub)
+    N, l, beta = params.tlwe_polynomial_degree, params.bs_decomp_length, params.bs_log2_base
+    n = np.asarray(c0).shape[0]
+    x = np.zeros((n, l, P, N), np.int64)
+    y = np.zeros((n, l, P, N), np.int64)
+    for q in range(P):
+        if q == i:
+            x[:, :, q] = d0                                         # :328-329 (zero added)
+            y[:, :, q] = d1                                         # :335-336
+            continue
+        # g^{-1}(b_q[jj] - b_i[jj]) for jj = 1..l                   :318-324
+        dec = decompose(wrap32(np.asarray(pub[q]).astype(np.int64) - np.asarray(pub[i]).astype(np.int64)), l, beta)  # [u][jj][N]
+        for jj in range(l):
+            xs = d0[:, jj].astype(np.int64)
+            ys = np.zeros((n, N), np.int64)
+            for u in range(l):
+                xs = xs + negacyclic_mul_small(dec[u, jj], f0[:, u])   # :331
+                ys = ys + negacyclic_mul_small(dec[u, jj], f1[:, u])   # :338
+            x[:, jj, q] = xs
+            y[:, jj, q] = ys
+    out = np.zeros((n, 2 * l * P + 2 * l, N), np.int32)
+    out[:, 0:l * P] = wrap32(x).reshape(n, l * P, N)
+    out[:, l * P:2 * l * P] = wrap32(y).reshape(n, l * P, N)
+    out[:, 2 * l * P:2 * l * P + l] = c0
+    out[:, 2 * l * P + l:] = c1
+    return out
+
+
 class CloudKeyPart:
     """mk_api.jl:60-80 — what one party generates: public key b (mk_internals.jl:116-139), the
-    uni-encryptions of its LWE key bits (mk_internals.jl:185-227, :419-439) and its keyswitch key."""
+    uni-encryptions of its LWE key bits (mk_internals.jl:185-227, :419-439) and its keyswitch key.
 
-    def __init__(self, rng, secret_key: SecretKey, shared_key: SharedKey):
+    keep_tlwe_key=True keeps the party's TLWE key as `.tlwe_key` (party-side secret material: what tfhe_jl_amd.leveled's
+    mk_tlwe_encrypt / mk_tlwe_phase / mk_tgsw_uni_encrypt_bits take; never passed to an engine).  It draws nothing more."""
+
+    def __init__(self, rng, secret_key: SecretKey, shared_key: SharedKey, keep_tlwe_key=False):
         p = secret_key.params
         self.params = p
-        N, l, n = p.tlwe_polynomial_degree, p.bs_decomp_length, p.lwe_size
-        alpha = p.bs_noise_stddev
+        N, l = p.tlwe_polynomial_degree, p.bs_decomp_length
         tlwe_key = TLweKey(rng, N, p.tlwe_mask_size)
+        self.tlwe_key = tlwe_key if keep_tlwe_key else None
         s = tlwe_key.key[0]                                             # mask_size = 1 (mk_internals.jl:129)
         a = shared_key.a
         # PublicKey: b_i = s * a_i + e_i                                 mk_internals.jl:131-136
-        self.public_b = wrap32(negacyclic_mul_small(s, a).astype(np.int64) + _gauss_poly(rng, alpha, l, N))
-        gadget = np.array([1 << (32 - (q + 1) * p.bs_log2_base) for q in range(l)], np.int64)
+        self.public_b = wrap32(negacyclic_mul_small(s, a).astype(np.int64) + _gauss_poly(rng, p.bs_noise_stddev, l, N))
         m = secret_key.key.key.astype(np.int64)                         # the n messages (LWE key bits)
         # RGSW.UniEnc for all n bits at once                            mk_internals.jl:185-227
-        r = rand_uniform_bool(rng, n, N)                                # :197
-        c1 = rand_uniform_torus32(rng, n, l, N)                         # :200
-        c0 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(s, c1).astype(np.int64)   # :202-206
-        c0[:, :, 0] += m[:, None] * gadget[None, :]                     # + message * gadget (constant term)
-        d1 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(r[:, None, :], a[None]).astype(np.int64)   # :209-213
-        d1[:, :, 0] += m[:, None] * gadget[None, :]
-        d0 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(r[:, None, :], self.public_b[None]).astype(np.int64)  # :214-217
-        f1 = rand_uniform_torus32(rng, n, l, N)                         # :220
-        f0 = _gauss_poly(rng, alpha, n, l, N) + negacyclic_mul_small(s, f1).astype(np.int64)   # :222-226
-        f0 += r[:, None, :].astype(np.int64) * gadget[None, :, None]    # + r * gadget (every coefficient)
-        self.c0, self.c1, self.d0, self.d1, self.f0, self.f1 = (wrap32(v) for v in (c0, c1, d0, d1, f0, f1))
+        self.c0, self.c1, self.d0, self.d1, self.f0, self.f1 = _uni_encrypt(rng, p, s, a, self.public_b, m)
         self.ks = make_keyswitch_key(rng, p.ks_noise_stddev, p.ks_decomp_length, p.ks_log2_base,
                                      secret_key.key, tlwe_key)          # mk_api.jl:74-76
 
@@ -81,35 +123,9 @@ class MKCloudKey:
         self._engines = {}
 
     def _expand_on_host(self):
-        ck_parts = self._parts
-        p, P = self.params, self.parties
-        N, l, n, beta = p.tlwe_polynomial_degree, p.bs_decomp_length, p.lwe_size, p.bs_log2_base
-        per = 2 * l * P + 2 * l
-        bk = np.zeros((P, n, per, N), np.int32)
-        pub = [part.public_b for part in ck_parts]
-        for i, part in enumerate(ck_parts):                             # party i, all n bits at once
-            x = np.zeros((n, l, P, N), np.int64)
-            y = np.zeros((n, l, P, N), np.int64)
-            for q in range(P):
-                if q == i:
-                    x[:, :, q] = part.d0                                # :328-329 (zero added)
-                    y[:, :, q] = part.d1                                # :335-336
-                    continue
-                # g^{-1}(b_q[jj] - b_i[jj]) for jj = 1..l               :318-324
-                dec = decompose(wrap32(pub[q].astype(np.int64) - pub[i].astype(np.int64)), l, beta)  # [u][jj][N]
-                for jj in range(l):
-                    xs = part.d0[:, jj].astype(np.int64)
-                    ys = np.zeros((n, N), np.int64)
-                    for u in range(l):
-                        xs = xs + negacyclic_mul_small(dec[u, jj], part.f0[:, u])   # :331
-                        ys = ys + negacyclic_mul_small(dec[u, jj], part.f1[:, u])   # :338
-                    x[:, jj, q] = xs
-                    y[:, jj, q] = ys
-            bk[i, :, 0:l * P] = wrap32(x).reshape(n, l * P, N)
-            bk[i, :, l * P:2 * l * P] = wrap32(y).reshape(n, l * P, N)
-            bk[i, :, 2 * l * P:2 * l * P + l] = part.c0
-            bk[i, :, 2 * l * P + l:] = part.c1
-        return bk
+        parts = self._parts
+        pub = [part.public_b for part in parts]
+        return np.stack([_expand(self.params, pub, i, part.c0, part.c1, part.d0, part.d1, part.f0, part.f1) for i, part in enumerate(parts)])
 
     def _part_arrays(self):
         parts = self._parts
