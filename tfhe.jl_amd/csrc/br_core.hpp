@@ -492,6 +492,94 @@ TFHE_HD void dft8_fwd_tw(cplx (&x)[8])
         x[1] = axpy(c0, kTwSL, c1); x[5] = axpy(c0, -kTwSL, c1); x[3] = axpy(d0, kTwSL, d1); x[7] = axpy(d0, -kTwSL, d1);
     }
 }
+// ---- pass-B twiddles in tan form, applied at the consumer ----------------------------------------------------------
+// The pass-B table tw2[q][s] = e^{-2 pi i q s/64} is symmetric.  After the second transposition (x2_store / x2_load) register v
+// of a lane came from register q = lane & 7 of lane s = v of its group, so its twiddle is tw2[v][lane & 7]: the set the inverse
+// transform conjugates in the same lane.  In both directions the twiddle can therefore sit right in front of a dft8 of the same
+// lane, with ONE per-lane constant set, and there it can take the tan form w_v = c_v (1 -+ i t_v) — two FMAs per point — with
+// the cosines c_v riding on the butterfly's additions (dft8_scaled: the general-ratio form of dft8_fwd_tw).  v = 4 stays an
+// ordinary complex multiply (c_4 = 1): W64^{4 s} is exactly -i at s = 4, where no tan form exists.  Every other cosine is
+// non-zero (v s = 16 mod 32 has no other solution with v, s <= 7); the largest |tan| is 10.15 at v s = +-15 mod 32.
+// The constants come from the host in long double (fill_tan2), 16 doubles per lane group s = lane & 7:
+//     t_1 t_2 t_3 t_5 t_6 t_7 | r0 r1 r2 r3 = c4/c0 (= 1) c5/c1 c6/c2 c7/c3 | g0 g1 = c2/c0 c3/c1 | L sL = c1/c0, L/sqrt(2) | w4
+// with c_v = cos(2 pi v s/64), t_v = tan(2 pi v s/64), c_0 = c_4 = 1.
+constexpr int kTan2Doubles = 16;                 // per lane group
+constexpr int kTan2Elems = 8 * kTan2Doubles / 2; // the whole table, in cplx
+struct LaneTan2 {
+    double t[6];         // v = 1, 2, 3, 5, 6, 7
+    double r1, r2, r3;   // (r0 = 1 is not kept)
+    double g0, g1, l, sl;
+    cplx w4;             // e^{-2 pi i 4 s/64}
+};
+template <typename LD, typename COS, typename SIN>
+inline void fill_tan2(double *h, COS cosfn, SIN sinfn)
+{
+    const LD pi = (LD)3.14159265358979323846264338327950288L;
+    for (int s = 0; s < 8; s++) {
+        LD c[8], t[8];
+        for (int v = 0; v < 8; v++) {
+            const LD a = (LD)2 * pi * (LD)(v * s) / (LD)64;
+            c[v] = cosfn(a); t[v] = sinfn(a) / cosfn(a);
+        }
+        double *o = h + s * kTan2Doubles;
+        const LD a4 = (LD)-2 * pi * (LD)(4 * s) / (LD)64;
+        o[14] = (double)cosfn(a4); o[15] = (double)sinfn(a4);
+        c[0] = 1; c[4] = 1;
+        o[0] = (double)t[1]; o[1] = (double)t[2]; o[2] = (double)t[3]; o[3] = (double)t[5]; o[4] = (double)t[6]; o[5] = (double)t[7];
+        for (int v = 0; v < 4; v++) o[6 + v] = (double)(c[v + 4] / c[v]);
+        o[10] = (double)(c[2] / c[0]); o[11] = (double)(c[3] / c[1]);
+        o[12] = (double)(c[1] / c[0]); o[13] = (double)(c[1] / c[0] * (LD)0.70710678118654752440084436210484904L);
+    }
+}
+TFHE_HD void load_lane_tan2(int lane, const double *tab, LaneTan2 &k)
+{
+    const double *o = tab + (lane & 7) * kTan2Doubles;
+#pragma unroll
+    for (int j = 0; j < 6; j++) k.t[j] = o[j];
+    k.r1 = o[7]; k.r2 = o[8]; k.r3 = o[9]; k.g0 = o[10]; k.g1 = o[11]; k.l = o[12]; k.sl = o[13];
+    k.w4 = mk(o[14], o[15]);
+}
+// x[v] <- x[v] w_v / c_v (INV: conj(w_v)): (a + i b)(1 - i t) = (a + t b) + i (b - t a), the conjugate form for the inverse
+template <bool INV>
+TFHE_HD cplx tan2_point(cplx x, double t)
+{
+    return INV ? mk(fma_(-t, x.y, x.x), fma_(t, x.x, x.y)) : mk(fma_(t, x.y, x.x), fma_(-t, x.x, x.y));
+}
+template <bool INV>
+TFHE_HD void tan2_apply(cplx (&x)[8], const LaneTan2 &k)
+{
+    x[1] = tan2_point<INV>(x[1], k.t[0]); x[2] = tan2_point<INV>(x[2], k.t[1]); x[3] = tan2_point<INV>(x[3], k.t[2]);
+    x[4] = INV ? cmulc(x[4], k.w4) : cmul(x[4], k.w4);
+    x[5] = tan2_point<INV>(x[5], k.t[3]); x[6] = tan2_point<INV>(x[6], k.t[4]); x[7] = tan2_point<INV>(x[7], k.t[5]);
+}
+// dft8<INV> of x[v] = c_v u[v], given u: every addition an FMA by the ratio of its operands' pending cosines; the outputs carry
+// c_0 = 1.  52 operations, as dft8.
+template <bool INV>
+TFHE_HD void dft8_scaled(cplx (&x)[8], const LaneTan2 &k)
+{
+    const cplx a0 = cadd(x[0], x[4]), a1 = axpy(x[1], k.r1, x[5]), a2 = axpy(x[2], k.r2, x[6]), a3 = axpy(x[3], k.r3, x[7]);
+    const cplx t0 = csub(x[0], x[4]), t1 = axpy(x[1], -k.r1, x[5]), t2 = axpy(x[2], -k.r2, x[6]), t3 = axpy(x[3], -k.r3, x[7]);
+    cplx b1, b2, b3;  // scales c1, c2, c3; b1, b3 lack their 1/sqrt(2)
+    if (!INV) {
+        b1 = mk(t1.x + t1.y, t1.y - t1.x);     // t1 * (1 - i)
+        b2 = mk(t2.y, -t2.x);                  // t2 * (-i)
+        b3 = mk(t3.y - t3.x, -(t3.x + t3.y));  // t3 * (-1 - i)
+    } else {
+        b1 = mk(t1.x - t1.y, t1.x + t1.y);     // t1 * (1 + i)
+        b2 = mk(-t2.y, t2.x);                  // t2 * (+i)
+        b3 = mk(-(t3.x + t3.y), t3.x - t3.y);  // t3 * (-1 + i)
+    }
+    {
+        const cplx c0 = axpy(a0, k.g0, a2), d0 = axpy(a0, -k.g0, a2), c1 = axpy(a1, k.g1, a3), e = axpy(a1, -k.g1, a3);
+        const cplx d1 = INV ? mk(-e.y, e.x) : mk(e.y, -e.x);
+        x[0] = axpy(c0, k.l, c1); x[4] = axpy(c0, -k.l, c1); x[2] = axpy(d0, k.l, d1); x[6] = axpy(d0, -k.l, d1);
+    }
+    {
+        const cplx c0 = axpy(t0, k.g0, b2), d0 = axpy(t0, -k.g0, b2), c1 = axpy(b1, k.g1, b3), e = axpy(b1, -k.g1, b3);
+        const cplx d1 = INV ? mk(-e.y, e.x) : mk(e.y, -e.x);
+        x[1] = axpy(c0, k.sl, c1); x[5] = axpy(c0, -k.sl, c1); x[3] = axpy(d0, k.sl, d1); x[7] = axpy(d0, -k.sl, d1);
+    }
+}
 TFHE_HD void fwd2_pass_a(cplx (&x)[8], const LaneTw &w)
 {
     dft8<false>(x);

@@ -162,7 +162,7 @@ struct tfhe_ctx {
                                  // measured (interleaved A/B): 1 gate 1.83 vs 1.91 ms (l = 2), 2.76 vs 3.07 ms (l = 3); 32 gates: 2 % slower
 
     // tables
-    cplx *d_tables = nullptr;   // tw1[512] | tw2[64] | twist[512]
+    cplx *d_tables = nullptr;   // tw1[512] | tw2[64] | twist[512] | tw1f[512] | the other kernels' tables (kH2TableOffset ...) | pass-B tan-form constants (kTan2TableOffset)
     Tables T{};
     Gadget g{};
     // any-N kernels (kernels_anyn.hpp): e^{-2 pi i t/M} [M] | e^{-i pi j/N} [M] for THIS context's N
@@ -360,6 +360,7 @@ int32_t ensure_dyn_lds(tfhe_ctx *c, const void *fn, size_t bytes, const char *wh
 
 constexpr size_t kH2TableOffset = kTableElems + 1024;      // tw1h | tw2q | tw3q of blind_rotate_kernel_h2
 constexpr size_t kN512TableOffset = kH2TableOffset + kH2TableElems;      // tw1 of blind_rotate_kernel_n512
+constexpr size_t kTan2TableOffset = kN512TableOffset + kN512TableElems;  // pass-B constants of blind_rotate_kernel_v3 (fill_tan2)
 
 inline int ilog2i(int x) { int r = 0; while ((1 << r) < x) r++; return r; }
 inline bool op_has_a(int op) { return !(op == TFHE_GATE_CONST0 || op == TFHE_GATE_CONST1); }

@@ -36,8 +36,9 @@ int32_t abi_caught(tfhe_ctx *c, const char *who) noexcept
 
 static void build_tables(std::vector<cplx> &h)
 {
-    h.resize(kN512TableOffset + kN512TableElems);
+    h.resize(kTan2TableOffset + kTan2Elems);
     fill_tables<long double>(h.data(), [](long double a) { return cosl(a); }, [](long double a) { return sinl(a); });
+    fill_tan2<long double>(reinterpret_cast<double *>(h.data() + kTan2TableOffset), [](long double a) { return cosl(a); }, [](long double a) { return sinl(a); });
     // N = 2048: tw1f2[w][q][t] = e^{-i pi t (1 + 4w + 8q) / 2048}
     const long double pi = 3.14159265358979323846264338327950288L;
     for (int w = 0; w < 2; w++)

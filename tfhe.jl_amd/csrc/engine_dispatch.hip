@@ -80,6 +80,7 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
     a.bk = c->d_bk;
     a.ext = (int32_t *)c->ext.p + first * ((size_t)c->P.k * c->P.N + 1);
     a.T = c->T;
+    a.tan2 = reinterpret_cast<const double *>(c->d_tables + kTan2TableOffset);
     a.g = c->g;
     a.n = c->P.n;
     a.mu = mu;

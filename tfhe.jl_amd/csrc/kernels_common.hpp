@@ -88,7 +88,10 @@ __device__ __forceinline__ void diag_begin(unsigned long long &t0, unsigned long
     }
 }
 template <bool DIAG>
-__device__ __forceinline__ void diag_end(const DiagArgs &d, size_t w, double worst, unsigned long long t0, unsigned long long r0, bool clock_writer = (threadIdx.x == 0))
+// (lane_in_wave: a kernel that keeps its lane number anyway passes it, and a clock_writer built from it, so that threadIdx.x need not stay
+//  alive to the end)
+__device__ __forceinline__ void diag_end(const DiagArgs &d, size_t w, double worst, unsigned long long t0, unsigned long long r0, bool clock_writer = (threadIdx.x == 0),
+                                         int lane_in_wave = (int)(threadIdx.x & 63))
 {
     if constexpr (DIAG) {
 #pragma unroll
@@ -96,7 +99,7 @@ __device__ __forceinline__ void diag_end(const DiagArgs &d, size_t w, double wor
             const double o = __shfl_xor(worst, off);
             worst = o > worst ? o : worst;
         }
-        if ((threadIdx.x & 63) == 0) {
+        if (lane_in_wave == 0) {
             atomicMax(&d.margin_bits[w], (unsigned long long)__double_as_longlong(worst));
             if (clock_writer) {
                 d.clk[2 * w] = __builtin_amdgcn_s_memtime() - t0;
@@ -227,6 +230,7 @@ struct BrArgs {
     const cplx *bk;       // [n][L][K1][K1][8][64] spectra, permuted order, scaled by 1/M
     int32_t *ext;         // [R][(K1-1)*N + 1]
     Tables T;
+    const double *tan2;   // [8][kTan2Doubles] pass-B constants in tan form (br_core.hpp: fill_tan2), read by blind_rotate_kernel_v3
     Gadget g;
     int32_t n;
     int32_t mu;

@@ -4,11 +4,12 @@
 #include "kernels_common.hpp"
 
 constexpr int kV3SyncEvery = 4;       // CMUX steps between the barriers of a lockstep group (1, 2, 4, 8, 16 measured: 11.62, 11.51, 11.49, 11.54, 11.53 ms)
-constexpr int kV3LdsBytes = 2 * kImg * 4 + (kXchElems + 64) * (int)sizeof(cplx);     // per rotation
+constexpr int kV3LdsBytes = 2 * kImg * 4 + (kXchElems + 64) * (int)sizeof(cplx);     // per rotation (the last 1 KB held the pass-B table while the kernel read it from LDS; the launch geometry keeps it)
 
 // v3: one wave per blind rotation at 2 waves/SIMD (<= 256 VGPRs, no AGPR/scratch spills).
-//   * pass-A twiddles (with the lane part of the twist folded in) resident in registers, pass-B twiddles
-//     in a 1 KB wave-private LDS table, the register part of the twist as compile-time constants:
+//   * pass-A twiddles (with the lane part of the twist folded in) resident in registers, pass-B twiddles in tan form
+//     (br_core.hpp: LaneTan2, 15 registers' worth of doubles per lane) applied by the receiving lane of the second
+//     transposition in both directions, the register part of the twist as compile-time constants:
 //     no global loads on the critical path except the key;
 //   * the accumulator lives only in LDS (read at rotate time and at the final add), each polynomial with its mirror
 //     block so that the rotation's signs and block offsets are scalar (rotate_sub3);
@@ -24,7 +25,7 @@ constexpr int kV3LdsBytes = 2 * kImg * 4 + (kXchElems + 64) * (int)sizeof(cplx);
 //     puts the pair on one SIMD pair in the same phase: 13.4 ms; RW = 8: 12.0 ms (profiles/r03/r03r_*, r03t_*);
 //   * no branch on bara[i] == 0 (the step then adds exactly zero);
 //   * the first transform of a step writes the spectrum accumulators (a product, not a multiply-add): no zeroing.
-template <int L, int KPF /* key values prefetched per transform: 16 = whole chunk, 8 = half */, bool TW2REG = false /* pass-B twiddles in registers instead of LDS */,
+template <int L, int KPF /* key values prefetched per transform: 16 = whole chunk, 8 = half */, bool TW2REG = true /* pass-B constants in registers: the only form left; the parameter stays in the kernel's name */,
           bool MARGIN = false /* diagnostics: rounding margin + in-kernel clock (DiagArgs) */, int RW = 1 /* rotations per workgroup */>
 __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(TV_ARGS(BrArgs) P)
 {
@@ -46,7 +47,6 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
     char *smem = smem_all + (size_t)wib * kV3LdsBytes;
     int32_t *acc_lds = reinterpret_cast<int32_t *>(smem);                    // [K1][kImg]
     cplx *xch = reinterpret_cast<cplx *>(smem + K1 * kImg * 4);              // [kXchElems]
-    cplx *tw2_lds = xch + kXchElems;                                         // [8][8]
     const int lane = (RW > 1) ? lane_id() : (int)threadIdx.x;
     size_t w = (size_t)blockIdx.x * RW + wib;
     const bool padding = (RW > 1) && w >= (size_t)P.R;                    // recomputes the last rotation, stores nothing
@@ -58,17 +58,16 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
     cplx tw1f[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) tw1f[q] = P.T.tw1f[q * 64 + lane];
-    tw2_lds[lane] = P.T.tw2[lane];
-    cplx tw2r[8];
-    if (TW2REG) {
-#pragma unroll
-        for (int q = 1; q < 8; q++) tw2r[q] = P.T.tw2[q * 8 + (lane & 7)];
-    }
+    LaneTan2 tk;
+    load_lane_tan2(lane, P.tan2, tk);
+    // DIAG: the running rounding margin lives in the wave's spare LDS behind the exchange buffer between the steps' roundings, not in two
+    // registers across the transforms, which have none to spare; the arithmetic is the timed kernel's, instruction for instruction
+    double *worst_lds = reinterpret_cast<double *>(xch + kXchElems);        // [64]
+    if (MARGIN) worst_lds[lane] = 0.0;
     init_zero_poly(lane, acc_lds);
     init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds + kImg);
     WAVE_LDS_FENCE();
 
-    double worst = 0.0;
     cplx kbuf[16];
     // chunk f of step: key spectra for transform f = (c, p): 16 values per lane (co-major, k2 minor)
     auto key_ptr = [&](int step, int f) {
@@ -103,15 +102,8 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
             x1_store_a(lane, x, xch);
             WAVE_LDS_FENCE();
             x1_load_b(lane, x, xch);
-            // pass B (twiddles from the LDS table)
-            {
-                cplx t2[8];
-#pragma unroll
-                for (int q = 1; q < 8; q++) t2[q] = TW2REG ? tw2r[q] : tw2_lds[q * 8 + (lane & 7)];
-                dft8<false>(x);
-#pragma unroll
-                for (int q = 1; q < 8; q++) x[q] = cmul(x[q], t2[q]);
-            }
+            // pass B: its twiddles wait for the receiving lane, in front of the last butterfly
+            dft8<false>(x);
             WAVE_LDS_FENCE();
             x2_store(lane, x, xch);
             WAVE_LDS_FENCE();
@@ -124,7 +116,11 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
             }
             x2_load(lane, x, xch);
             WAVE_LDS_FENCE();
-            dft8<false>(x);
+            // (all eight reads in flight before the first tangent is applied: left to itself the scheduler pairs each two reads with their
+            //  FMAs and drains the LDS queue once more per transform)
+            __builtin_amdgcn_sched_barrier(0);
+            tan2_apply<false>(x, tk);
+            dft8_scaled<false>(x, tk);
             // MAC: out[co] (+)= D[p, c] .* BK_i[p, c].a[co]        (tgsw.jl:128); f is wave-uniform: a scalar branch
             if (KPF == 16) {
                 if (f == 0) {
@@ -170,14 +166,8 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
             x2_store(lane, out[co], xch);
             WAVE_LDS_FENCE();
             x2_load(lane, out[co], xch);
-            {
-                cplx t2[8];
-#pragma unroll
-                for (int q = 1; q < 8; q++) t2[q] = TW2REG ? tw2r[q] : tw2_lds[q * 8 + (lane & 7)];
-#pragma unroll
-                for (int q = 1; q < 8; q++) out[co][q] = cmulc(out[co][q], t2[q]);
-            }
-            dft8<true>(out[co]);
+            tan2_apply<true>(out[co], tk);
+            dft8_scaled<true>(out[co], tk);
             WAVE_LDS_FENCE();
             x1_store_b(lane, out[co], xch);
             WAVE_LDS_FENCE();
@@ -186,7 +176,9 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
 #pragma unroll
             for (int q = 0; q < 8; q++) out[co][q] = cmulc(out[co][q], tw1f[q]);
             dft8<true>(out[co]);
+            double worst = MARGIN ? worst_lds[lane] : 0.0;
             accumulate_poly<MARGIN>(lane, out[co], acc_lds + co * kImg, &worst);
+            if (MARGIN) worst_lds[lane] = worst;
         }
         WAVE_LDS_FENCE();
     }
@@ -196,5 +188,8 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
     extract_mask_poly(lane, acc_lds, ext);
     if (lane == 0) ext[kN] = acc_lds[kImg + kMir];
     store_bodies(P, w, lane, acc_lds + kImg + kMir, kN);
-    diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0);
+    // (RW = 4: the lane number is not threadIdx.x, which would have to stay alive to the end for diag_end's defaults — one register more than
+    //  the tuned DIAG forms have.  The run-time-l DIAG form keeps the defaults and its few spilled bytes: tests/test_resource_usage.py lists it.)
+    if constexpr (RW > 1 && L != 0) diag_end<MARGIN>(P.diag, w, MARGIN ? worst_lds[lane] : 0.0, dg_t0, dg_r0, wib == 0 && lane == 0, lane);
+    else diag_end<MARGIN>(P.diag, w, MARGIN ? worst_lds[lane] : 0.0, dg_t0, dg_r0);
 }
