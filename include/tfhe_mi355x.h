@@ -435,6 +435,28 @@ int32_t tfhe_extern_mul_batch(tfhe_ctx *ctx, const int32_t *tlwe_in, const int32
 int32_t tfhe_cmux_tree_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, const int32_t *table_index, int32_t depth,
                              const int32_t *sel, int32_t *out, int64_t B, int32_t out_form);
 
+/* CMUX network (addition within ABI v7): the same CMUX wired by a public netlist instead of by halving — the backward evaluation of a
+ * deterministic automaton or an ordered decision diagram on TGSW-encrypted variables.  The network is shared by all rows: `levels`
+ * levels (1 ... 1024), level v with widths[v] nodes (1 ... 4096); nodes: host int32 [sum widths][3] = (src0, src1, var) in level order.
+ * Node i of level v of row g is  in[src0] + selector[sel[g][var]] (.) (in[src1] - in[src0])  — a selector that encrypts 1 picks src1 —
+ * where `in` is, for v = 0, the E TLWE samples of the row's table data[table_index[g]] (E >= 1, any count) and, for v > 0, the outputs
+ * of level v - 1.  var indexes the row's V selectors, sel: host int32 [B][V] in [0, S), and is per node.  A node with src0 == src1 is
+ * a copy: no product, no noise, the same words.  All F = widths[levels-1] nodes of the last level are outputs.
+ * data: host int32 [T][E][k+1][N]; table_index: host int32 [B] in [0, T) or NULL = table 0.  out_form 0: out int32 [B][F][k+1][N];
+ * 1: extracted at coefficient 0, [B][F][k*N+1]; 2: that keyswitched, [B][F][n+1].  One launch per level
+ * (csrc/kernels_cmux_net.hpp; tfhe_last_kernel_name reports "cmux_net_level_kernel(N=..,k=..,l=..[,spec=global])", the option
+ * "anyn_spec" = 1 puts the spectrum accumulators in global memory as for the any-N rotation).  A tree-shaped network equals
+ * tfhe_cmux_tree_batch word for word.
+ * Workspace: two device buffers of B max(widths of the even levels) and B max(widths of the odd levels) TLWE samples plus the T
+ * tables; as above the sizes are compared with the device's free memory BEFORE anything is allocated (TFHE_ERR_NOMEM, the context
+ * stays usable).  Everything is validated on the host in O(B V + nodes) before anything is uploaded, the message naming the
+ * offender — TFHE_ERR_INVALID_ARG: NULL buffer, levels / a width / E / V / T out of range, a source negative or not below the width
+ * of the level below (E at level 0), var outside [0, V), a selector or table index out of range, out_form outside 0 ... 2, B * width
+ * above one launch; TFHE_ERR_NO_KEY: no selector set, or out_form 2 without the keyswitch key; TFHE_ERR_STATE as the calls above.
+ * B = 0 returns TFHE_OK. */
+int32_t tfhe_cmux_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths,
+                            int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form);
+
 /* ---- leveled mode under a multi-key cloud key (additions within ABI v7) ---------------------------------
  * The same two operations on multi-key samples, with no blind rotation: the selectors are the parties' uni-encryptions of address
  * bits (mk_tgsw_encrypt, RGSW.UniEnc, mk_internals.jl:185-227) expanded against all public keys (mk_tgsw_expand, :304-345), the

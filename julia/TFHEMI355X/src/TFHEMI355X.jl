@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -512,6 +512,44 @@ function cmux_tree(gck::GpuCloudKey, data::Array{Int32,4}, sel::AbstractMatrix, 
     GC.@preserve data s idx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_cmux_tree_batch, LIB), Int32,
         (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Int32),
         gck.ctx, data, Int64(size(data, 4)), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), Int32(depth), s, out, Int64(B), Int32(out_form)))
+    out_form == 0 ? out : unflatten(out, LweParams(width))
+end
+
+"""
+    cmux_net(gck, data::Array{Int32,4}, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_index=nothing; out_form=2)
+
+CMUX network (tfhe_cmux_net_batch): the CMUX of `cmux_tree` wired by a public netlist, the backward evaluation of an automaton or a
+decision diagram.  `data` holds `T` tables of `E` TLWE samples (Int32 `N x (k+1) x E x T`); `widths[v]` is the node count of level `v`;
+`nodes` is `3 x sum(widths)`, column `(src0, src1, var)` in level order, all 1-based: the node is `in[src0] + C_var ⊡ (in[src1] - in[src0])`
+with `in` the table (first level) or the outputs of the level below, and `src0 == src1` a copy.  `sel` is `V x B` (1-based indices into
+the loaded selectors), `table_index` 1-based or `nothing` (first table).  With `F = widths[end]` outputs per row, `out_form` 2 returns
+the `F * B` `LweSample`s under the gate key (output `i` of row `g` at `(g - 1) F + i`), 1 the extracted samples of size `k N`, 0 the TLWE
+samples as Int32 `N x (k+1) x F x B`.
+"""
+function cmux_net(gck::GpuCloudKey, data::Array{Int32,4}, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_index=nothing; out_form::Integer=2)
+    p = gck.params
+    N, k = p.tlwe_polynomial_degree, p.tlwe_mask_size
+    w = Int32.(collect(widths))
+    levels = length(w)
+    1 <= levels <= 1024 || error("tfhe_mi355x: levels = ", levels, " (1 ... 1024)")
+    all(x -> 1 <= x <= 4096, w) || error("tfhe_mi355x: every width must be 1 ... 4096")
+    size(nodes) == (3, sum(w)) || error("tfhe_mi355x: nodes must be 3 x sum(widths)")
+    E = size(data, 3)
+    size(data)[1:2] == (N, k + 1) && E >= 1 && size(data, 4) >= 1 || error("tfhe_mi355x: tables must be N x (k+1) x E x T")
+    V, B = size(sel)
+    V >= 1 || error("tfhe_mi355x: sel must be V x B with V >= 1")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    nd = Matrix{Int32}(nodes .- 1)
+    s = Matrix{Int32}(sel .- 1)
+    idx = table_index === nothing ? nothing : Int32.(collect(table_index) .- 1)
+    F = Int(w[end])
+    width = out_form == 2 ? p.lwe_size : k * N
+    out = out_form == 0 ? Array{Int32}(undef, N, k + 1, F, B) : Array{Int32}(undef, width + 1, F * B)
+    B == 0 && return out_form == 0 ? out : LweSample[]
+    GC.@preserve data w nd s idx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_cmux_net_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Int64, Int32),
+        gck.ctx, data, Int64(size(data, 4)), Int32(E), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), w, Int32(levels), nd, s, Int32(V), out,
+        Int64(B), Int32(out_form)))
     out_form == 0 ? out : unflatten(out, LweParams(width))
 end
 

@@ -14,6 +14,7 @@
 //   mk_g2_inst.hip        one instantiation of the many-party two-wave kernel per translation unit (-DG2_TV=1: its TV form)
 //   engine_leveled.hip    leveled mode: batched external products and CMUX trees on a caller's TGSW / TLWE samples  ("leveled")
 //   engine_mk_leveled.hip the same under a multi-key cloud key: expanded RGSW selectors, MK TLWE samples          ("mk leveled")
+//   engine_cmux_net.hip   leveled mode: CMUX networks (automata, decision diagrams) wired by a public netlist          ("cmux net")
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
 // only under the TFHE_EMIT_* macro of the unit that launches them (templates are instantiated where they are launched).

@@ -12,6 +12,11 @@ The host side mirrors the reference's constructors under the TLWE key that Cloud
 bs_noise_stddev).  The device side is Engine.tgsw_load / extern_mul / cmux_tree (tfhe_tgsw_load, tfhe_extern_mul_batch,
 tfhe_cmux_tree_batch); cmux_lookup strings them together.
 
+A CMUX network (CmuxNet; Engine.cmux_net, tfhe_cmux_net_batch; cmux_net_lookup) is the same CMUX wired by a public netlist instead of
+by halving: the TFHE paper's evaluation of a deterministic automaton or an ordered decision diagram on TGSW-encrypted letters.  A
+function of d encrypted bits with a small automaton then costs a few CMUXes per bit instead of 2^d - 1 per lookup: dfa_net builds the
+network of an automaton, less_than_net the five-state comparator of two d-bit integers, tree_net the network of cmux_lookup.
+
 Under a multi-key cloud key (the mk_* functions below) the selectors are jointly encrypted: each party uni-encrypts the address bits
 it owns (mk_tgsw_uni_encrypt_bits: RGSW.UniEnc, mk_internals.jl:185-227) under the TLWE key that CloudKeyPart(..., keep_tlwe_key=True)
 keeps, the cloud expands them against all public keys (mk_tgsw_expand: RGSW.Expand, :304-345; or on the device) and folds a table of
@@ -108,6 +113,137 @@ def cmux_lookup(ck, tables, address_tgsw, out_form=2, device=0, table_index=None
     sel = np.arange(B * depth, dtype=np.int32).reshape(B, depth)
     out = eng.cmux_tree(tables, sel, table_index=table_index, out_form=out_form)
     return LweSampleArray(out) if out_form == 2 else out
+
+
+# ---- CMUX networks: automata and decision diagrams ------------------------------------------------------------------------------
+NET_MAX_LEVELS, NET_MAX_WIDTH = 1024, 4096
+
+
+class CmuxNet:
+    """The public wiring of a CMUX network, validated as tfhe_cmux_net_batch validates it.  widths: the node count of each level (1 ...
+    1024 levels of 1 ... 4096 nodes); nodes: int32 [sum widths][3] = (src0, src1, var) in level order.  Node i of level v is
+    in[src0] + C_var (.) (in[src1] - in[src0]) — a variable that is 1 picks src1 — with `in` the table entries for v = 0 and the outputs
+    of level v - 1 above; src0 == src1 is a copy.  The outputs are the nodes of the last level.  `entries` (the table length E) and
+    `variables` (V) default to the smallest counts the nodes need; given, the nodes are checked against them."""
+
+    def __init__(self, widths, nodes, entries=None, variables=None):
+        w = np.asarray(widths)
+        if w.ndim != 1 or not np.issubdtype(w.dtype, np.integer) or not 1 <= w.size <= NET_MAX_LEVELS:
+            raise ValueError(f"widths must be 1 ... {NET_MAX_LEVELS} integers, got shape {w.shape}")
+        for v, x in enumerate(w):
+            if not 1 <= x <= NET_MAX_WIDTH:
+                raise ValueError(f"widths[{v}] = {x} (1 ... {NET_MAX_WIDTH})")
+        nd = np.asarray(nodes)
+        if not np.issubdtype(nd.dtype, np.integer) or nd.shape != (int(w.sum()), 3):
+            raise ValueError(f"nodes must be integers [{int(w.sum())}][3] = (src0, src1, var), got {nd.shape}")
+        nd = nd.astype(np.int64)
+        need_e = int(nd[:w[0], :2].max()) + 1
+        need_v = int(nd[:, 2].max()) + 1
+        E = need_e if entries is None else int(entries)
+        V = need_v if variables is None else int(variables)
+        if E < 1 or V < 1:
+            raise ValueError(f"entries = {E}, variables = {V} (at least one each)")
+        first = 0
+        for v, x in enumerate(w):
+            below = E if v == 0 else int(w[v - 1])
+            lv = nd[first:first + int(x)]
+            bad = np.argwhere((lv[:, :2] < 0) | (lv[:, :2] >= below))
+            if bad.size:
+                i, e = (int(t) for t in bad[0])
+                what = "table entries" if v == 0 else "nodes"
+                raise ValueError(f"node {i} of level {v}: src{e} = {lv[i, e]} is outside the {below} {what} below")
+            bad = np.flatnonzero((lv[:, 2] < 0) | (lv[:, 2] >= V))
+            if bad.size:
+                raise ValueError(f"node {bad[0]} of level {v}: var = {lv[bad[0], 2]} is outside [0, {V})")
+            first += int(x)
+        self.widths = np.ascontiguousarray(w, np.int32)
+        self.nodes = np.ascontiguousarray(nd, np.int32)
+        self.levels = int(w.size)
+        self.entries, self.variables = E, V
+
+    def level(self, v):
+        """The records of level v, int32 [widths[v]][3]."""
+        first = int(self.widths[:v].sum())
+        return self.nodes[first:first + int(self.widths[v])]
+
+    @property
+    def products(self):
+        """External products per row: the nodes that are not copies."""
+        return int(np.count_nonzero(self.nodes[:, 0] != self.nodes[:, 1]))
+
+    def evaluate_clear(self, entries, bits):
+        """The same wiring on plain values: the outputs of the last level for table `entries` and variable values `bits`."""
+        cur = list(entries)
+        if len(cur) < self.entries or len(bits) < self.variables:
+            raise ValueError(f"the network reads {self.entries} entries and {self.variables} variables, got {len(cur)} and {len(bits)}")
+        for v in range(self.levels):
+            cur = [cur[s1] if bits[var] else cur[s0] for s0, s1, var in self.level(v).tolist()]
+        return cur
+
+
+def tree_net(depth):
+    """The network of cmux_lookup / Engine.cmux_tree: 2^depth entries, level v folds the pairs (2i, 2i + 1) by variable v."""
+    if not 1 <= depth <= 12:
+        raise ValueError(f"depth = {depth} (1 ... 12)")
+    widths = [1 << (depth - 1 - v) for v in range(depth)]
+    nodes = [(2 * i, 2 * i + 1, v) for v in range(depth) for i in range(widths[v])]
+    return CmuxNet(widths, nodes, entries=1 << depth, variables=depth)
+
+
+def dfa_net(delta0, delta1, start, steps, letter_var=None):
+    """The backward evaluation of a deterministic automaton (the TFHE paper's leveled automaton evaluation).  State q moves to delta0[q]
+    on letter 0 and to delta1[q] on letter 1; the automaton reads `steps` letters from `start`, letter j being variable letter_var[j]
+    (default: j).  Level v handles letter steps - 1 - v and has one node per state reachable after that many letters, in increasing
+    state order; a state whose two transitions agree (an absorbing state) becomes a copy node.  Level 0 reads table entry q = the weight
+    of ending in state q (E = number of states); the one output is the weight of the state the letters lead to."""
+    d0, d1 = [int(q) for q in delta0], [int(q) for q in delta1]
+    Q = len(d0)
+    if Q < 1 or len(d1) != Q or any(not 0 <= q < Q for q in d0 + d1) or not 0 <= start < Q:
+        raise ValueError("delta0 and delta1 must map every state to a state, and start must be a state")
+    if not 1 <= steps <= NET_MAX_LEVELS:
+        raise ValueError(f"steps = {steps} (1 ... {NET_MAX_LEVELS})")
+    var = list(range(steps)) if letter_var is None else [int(x) for x in letter_var]
+    if len(var) != steps:
+        raise ValueError(f"letter_var must name a variable for each of the {steps} letters")
+    reach = [[int(start)]]                                           # reach[j]: the states after j letters, sorted
+    for j in range(steps - 1):
+        reach.append(sorted({d[q] for q in reach[-1] for d in (d0, d1)}))
+    widths, nodes = [], []
+    for v in range(steps):
+        j = steps - 1 - v
+        place = {q: q for q in range(Q)} if v == 0 else {q: i for i, q in enumerate(reach[j + 1])}
+        widths.append(len(reach[j]))
+        nodes += [(place[d0[q]], place[d1[q]], var[j]) for q in reach[j]]
+    return CmuxNet(widths, nodes, entries=Q, variables=max(var) + 1)
+
+
+def less_than_net(bits):
+    """x < y for two `bits`-bit unsigned integers as a five-state automaton over the letters x_{d-1}, y_{d-1}, ..., x_0, y_0 (highest
+    bit first): equal so far (0), equal and x's bit was 0 (1) or 1 (2), x < y decided (3), x > y decided (4).  Returns (net, table):
+    the network over variables x_0 ... x_{d-1}, y_0 ... y_{d-1} (variable b = bit b of x, d + b = bit b of y; 2 d levels of at most 4
+    nodes) and its end-state table, the truth of x < y in each of the five states — table_to_tlwe(table, N, k) is the data."""
+    d = int(bits)
+    if not 1 <= d <= NET_MAX_LEVELS // 2:
+        raise ValueError(f"bits = {bits} (1 ... {NET_MAX_LEVELS // 2})")
+    letter_var = [(d - 1 - j // 2) + (d if j & 1 else 0) for j in range(2 * d)]
+    net = dfa_net([1, 0, 4, 3, 4], [2, 3, 0, 3, 4], 0, 2 * d, letter_var)
+    return net, [False, False, False, True, False]
+
+
+def cmux_net_lookup(ck, data, net, bits_tgsw, out_form=2, device=0, table_index=None):
+    """The network `net` on B rows of encrypted variables.  data: int32 [E][k+1][N] (table_to_tlwe) or [T][E][k+1][N] with table_index
+    [B]; bits_tgsw: int32 [B][V][l][k+1][k+1][N], variable v of row g encrypted by tgsw_encrypt_bits.  out_form 2 (default): an
+    LweSampleArray under the gate key, ready for gate_* / Circuit, of B F samples (row g's output i at g F + i; F = 1 for an
+    automaton); 1: the extracted samples int32 [B][F][k N + 1]; 0: the TLWE samples int32 [B][F][k+1][N]."""
+    a = np.asarray(bits_tgsw, np.int32)
+    if a.ndim != 6:
+        raise ValueError(f"bits_tgsw must be [B][V][l][k+1][k+1][N], got {a.shape}")
+    B, V = a.shape[:2]
+    eng = ck.engine(device)
+    eng.tgsw_load(a.reshape((B * V,) + a.shape[2:]))
+    sel = np.arange(B * V, dtype=np.int32).reshape(B, V)
+    out = eng.cmux_net(data, net, sel, table_index=table_index, out_form=out_form)
+    return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
 
 
 # ---- under a multi-key cloud key -------------------------------------------------------------------------------------------------
