@@ -498,6 +498,23 @@ int32_t tfhe_mk_extern_mul_batch(tfhe_ctx *ctx, const int32_t *tlwe_in, const in
 int32_t tfhe_mk_cmux_tree_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, const int32_t *table_index, int32_t depth,
                                 const int32_t *sel, int32_t *out, int64_t B, int32_t out_form);
 
+/* CMUX network on multi-key samples (addition within ABI v7): tfhe_cmux_net_batch's contract — the same netlist, limits, validation and
+ * messages — with data host int32 [T][E][P+1][N] and sel: host int32 [B][V] into the multi-key selector set.  Node i of level v of row
+ * g is  in[src0] + selector[sel[g][var]] (.) (in[src1] - in[src0])  with mk_tgsw_extern_mul for the party of THAT selector: the party
+ * is per node, so one level may mix the parties' variables.  A node with src0 == src1 is a copy.  out_form 0: out int32 [B][F][P+1][N];
+ * 1: mk_tlwe_extract_sample at coefficient 0, [B][F][P*N+1]; 2: that through mk_keyswitch, [B][F][P*n+1], multi-key LWE samples every
+ * tfhe_mk_gate* call accepts.  One launch per level (csrc/kernels_mk_cmux_net.hpp; tfhe_last_kernel_name reports
+ * "mk_cmux_net_level_kernel(N=..,P=..,l=..[,spec=global])"; the option "anyn_spec" = 1 puts the three spectrum accumulators in global
+ * memory, where they are anyway from N = 4096 up).  A tree-shaped network equals tfhe_mk_cmux_tree_batch word for word.  The jointly
+ * encrypted comparison of two 16-bit integers held by two parties is 32 levels and 48 products per row.
+ * Workspace and TFHE_ERR_NOMEM as tfhe_cmux_net_batch, on samples of P + 1 polynomials.  Refused in this order: TFHE_ERR_STATE on a
+ * single-key context, a multi-device context, with "measure_margin" on; TFHE_ERR_NO_KEY without the multi-key bootstrapping key or a
+ * selector set; TFHE_ERR_INVALID_ARG as tfhe_cmux_net_batch; TFHE_ERR_NO_KEY for out_form 2 without the multi-key keyswitch key.
+ * B = 0 returns TFHE_OK. */
+int32_t tfhe_mk_cmux_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index,
+                               const int32_t *widths, int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V,
+                               int32_t *out, int64_t B, int32_t out_form);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Timing of the most recent batch call on ctx, from HIP events recorded on the stream the kernels

@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -844,6 +844,45 @@ function mk_cmux_tree(mck::GpuMKCloudKey, data::Array{Int32,4}, sel::AbstractMat
     out_form == 2 || return out
     params = LweParams(n)
     [MKLweSample(params, reshape(out[1:n*P, g], n, P), out[n * P + 1, g], 0.) for g in 1:B]
+end
+
+"""
+    mk_cmux_net(mck, data::Array{Int32,4}, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_index=nothing; out_form=2)
+
+CMUX network on multi-key samples (tfhe_mk_cmux_net_batch): `cmux_net` with tables Int32 `N x (P+1) x E x T` and `sel` (`V x B`, 1-based)
+into the selectors of `mk_tgsw_load!`; every node multiplies for the party of its own selector, so the comparison of two integers that
+two parties hold is the comparator network on their uni-encrypted bits.  `widths`, `nodes` (`3 x sum(widths)`, 1-based) and
+`table_index` as `cmux_net`.  With `F = widths[end]` outputs per row, `out_form` 2 returns the `F * B` `MKLweSample`s that `mk_gate_nand`
+accepts (output `i` of row `g` at `(g - 1) F + i`), 1 the extracted samples as Int32 `(P N + 1) x (F B)`, 0 the MK TLWE samples as Int32
+`N x (P+1) x F x B`.
+"""
+function mk_cmux_net(mck::GpuMKCloudKey, data::Array{Int32,4}, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_index=nothing; out_form::Integer=2)
+    p, P = mck.params, mck.parties
+    N, n = p.tlwe_polynomial_degree, p.lwe_size
+    w = Int32.(collect(widths))
+    levels = length(w)
+    1 <= levels <= 1024 || error("tfhe_mi355x: levels = ", levels, " (1 ... 1024)")
+    all(x -> 1 <= x <= 4096, w) || error("tfhe_mi355x: every width must be 1 ... 4096")
+    size(nodes) == (3, sum(w)) || error("tfhe_mi355x: nodes must be 3 x sum(widths)")
+    E = size(data, 3)
+    size(data)[1:2] == (N, P + 1) && E >= 1 && size(data, 4) >= 1 || error("tfhe_mi355x: tables must be N x (P+1) x E x T")
+    V, B = size(sel)
+    V >= 1 || error("tfhe_mi355x: sel must be V x B with V >= 1")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    nd = Matrix{Int32}(nodes .- 1)
+    s = Matrix{Int32}(sel .- 1)
+    idx = table_index === nothing ? nothing : Int32.(collect(table_index) .- 1)
+    F = Int(w[end])
+    width = out_form == 2 ? P * n : P * N
+    out = out_form == 0 ? Array{Int32}(undef, N, P + 1, F, B) : Array{Int32}(undef, width + 1, F * B)
+    B == 0 && return out_form == 2 ? MKLweSample[] : out
+    GC.@preserve data w nd s idx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_cmux_net_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Int64, Int32),
+        mck.ctx, data, Int64(size(data, 4)), Int32(E), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), w, Int32(levels), nd, s, Int32(V), out,
+        Int64(B), Int32(out_form)))
+    out_form == 2 || return out
+    params = LweParams(n)
+    [MKLweSample(params, reshape(out[1:n*P, r], n, P), out[n * P + 1, r], 0.) for r in 1:F*B]
 end
 
 """

@@ -19,7 +19,7 @@ from .lut import (lut_encode, lut_decode, lut_encrypt, lut_decrypt, make_test_ve
 from .serialize import save_cloud_key, load_cloud_key
 from .leveled import tlwe_encrypt, tlwe_trivial, tlwe_phase, tgsw_encrypt_bits, table_to_tlwe, cmux_lookup
 from .leveled import CmuxNet, tree_net, dfa_net, less_than_net, cmux_net_lookup
-from .leveled import mk_tlwe_trivial, mk_tlwe_encrypt, mk_tlwe_phase, mk_tgsw_uni_encrypt_bits, mk_tgsw_expand, mk_cmux_lookup
+from .leveled import mk_tlwe_trivial, mk_tlwe_encrypt, mk_tlwe_phase, mk_tgsw_uni_encrypt_bits, mk_tgsw_expand, mk_cmux_lookup, mk_cmux_net_lookup
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
 
 __all__ = [

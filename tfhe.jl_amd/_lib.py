@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "tfhe_mk_bootstrap_tv_batch", "tfhe_mk_bootstrap_tv_multi_batch", "tfhe_mk_lut_level", "tfhe_mk_linear_level",
     "tfhe_tgsw_load", "tfhe_extern_mul_batch", "tfhe_cmux_tree_batch", "tfhe_cmux_net_batch",
     "tfhe_mk_tgsw_load", "tfhe_mk_tgsw_expand_load", "tfhe_mk_extern_mul_batch", "tfhe_mk_cmux_tree_batch",
+    "tfhe_mk_cmux_net_batch",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -158,6 +159,8 @@ def load():
         lib.tfhe_mk_tgsw_expand_load.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
         lib.tfhe_mk_extern_mul_batch.argtypes = [vp, vp, vp, vp, i64]
         lib.tfhe_mk_cmux_tree_batch.argtypes = [vp, vp, i64, vp, i32, vp, vp, i64, i32]
+    if hasattr(lib, "tfhe_mk_cmux_net_batch"):
+        lib.tfhe_mk_cmux_net_batch.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, i32]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -471,16 +474,13 @@ class Engine:
         self._check(self._lib.tfhe_cmux_tree_batch(self._h, _ptr(d), d.shape[0], _ptr(idx), depth, _ptr(sel), _ptr(out), B, int(out_form)))
         return out
 
-    def cmux_net(self, data, net, sel, table_index=None, out_form=2):
-        """CMUX network (tfhe_cmux_net_batch).  data: int32 [T][E][k+1][N] tables of TLWE samples (or [E][k+1][N]: one table); net: a
-        leveled.CmuxNet, the public wiring shared by all rows; sel: int32 [B][V] indices into the loaded selector set, one per variable
-        of the network; table_index: [B] or None (table 0).  Row g's result is the F outputs of the last level: TLWE samples
-        [B][F][k+1][N] (out_form 0), extracted at coefficient 0 [B][F][k*N+1] (1) or keyswitched under the gate key [B][F][n+1] (2)."""
+    def _net_args(self, data, net, sel, table_index, polys):
+        """The shape checks cmux_net and mk_cmux_net share: tables [T][E][polys][N] (or one table [E][polys][N]), sel [B][V]."""
         d = _i32c(data)
         if d.ndim == 3:
             d = d[None]
-        if d.ndim != 4 or d.shape[0] < 1 or d.shape[1] < 1 or d.shape[2:] != (self.k + 1, self.N):
-            raise ValueError(f"tables must be [T][E][{self.k + 1}][{self.N}], got {d.shape}")
+        if d.ndim != 4 or d.shape[0] < 1 or d.shape[1] < 1 or d.shape[2:] != (polys, self.N):
+            raise ValueError(f"tables must be [T][E][{polys}][{self.N}], got {d.shape}")
         if d.shape[1] < net.entries:
             raise ValueError(f"the network reads table entry {net.entries - 1}, the tables have {d.shape[1]}")
         sel = _i32c(np.atleast_2d(sel))
@@ -492,6 +492,15 @@ class Engine:
             idx = _i32c(table_index).reshape(-1)
             if idx.size != B:
                 raise ValueError(f"table_index must have one entry per row ({B}), got {idx.size}")
+        return d, sel, idx
+
+    def cmux_net(self, data, net, sel, table_index=None, out_form=2):
+        """CMUX network (tfhe_cmux_net_batch).  data: int32 [T][E][k+1][N] tables of TLWE samples (or [E][k+1][N]: one table); net: a
+        leveled.CmuxNet, the public wiring shared by all rows; sel: int32 [B][V] indices into the loaded selector set, one per variable
+        of the network; table_index: [B] or None (table 0).  Row g's result is the F outputs of the last level: TLWE samples
+        [B][F][k+1][N] (out_form 0), extracted at coefficient 0 [B][F][k*N+1] (1) or keyswitched under the gate key [B][F][n+1] (2)."""
+        d, sel, idx = self._net_args(data, net, sel, table_index, self.k + 1)
+        B, V = sel.shape
         F = int(net.widths[-1])
         shape = {0: (B, F, self.k + 1, self.N), 1: (B, F, self.k * self.N + 1), 2: (B, F, self.n + 1)}.get(int(out_form), (0,))
         out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
@@ -562,6 +571,21 @@ class Engine:
         shape = {0: (B, P + 1, self.N), 1: (B, P * self.N + 1), 2: (B, P * self.n + 1)}.get(int(out_form), (0,))
         out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
         self._check(self._lib.tfhe_mk_cmux_tree_batch(self._h, _ptr(d), d.shape[0], _ptr(idx), depth, _ptr(sel), _ptr(out), B, int(out_form)))
+        return out
+
+    def mk_cmux_net(self, data, net, sel, table_index=None, out_form=2):
+        """CMUX network on multi-key samples (tfhe_mk_cmux_net_batch): cmux_net with tables int32 [T][E][P+1][N] and sel [B][V] into the
+        multi-key selector set; every node multiplies for the party of its own selector.  Row g's F outputs are MK TLWE samples
+        [B][F][P+1][N] (out_form 0), extracted at coefficient 0 [B][F][P*N+1] (1) or keyswitched to multi-key LWE samples [B][F][P*n+1]
+        (2), operands of every mk_gate."""
+        P = self._mk_width("mk_cmux_net")
+        d, sel, idx = self._net_args(data, net, sel, table_index, P + 1)
+        B, V = sel.shape
+        F = int(net.widths[-1])
+        shape = {0: (B, F, P + 1, self.N), 1: (B, F, P * self.N + 1), 2: (B, F, P * self.n + 1)}.get(int(out_form), (0,))
+        out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
+        self._check(self._lib.tfhe_mk_cmux_net_batch(self._h, _ptr(d), d.shape[0], d.shape[1], _ptr(idx), _ptr(net.widths), net.levels, _ptr(net.nodes),
+                                                     _ptr(sel), V, _ptr(out), B, int(out_form)))
         return out
 
     # ---- levelised circuits on the device-resident wire table ----

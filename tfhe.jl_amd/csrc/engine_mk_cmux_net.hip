@@ -1,33 +1,24 @@
-// engine_cmux_net.hip — leveled mode: tfhe_cmux_net_batch, CMUX networks (automata, decision diagrams) wired by a public netlist on a
-// caller's TGSW selectors (tfhe_tgsw_load, engine_keys.hip) and TLWE samples; the network level kernel (kernels_cmux_net.hpp) is
-// compiled here and nowhere else
-#define TFHE_EMIT_CMUX_NET_KERNELS
+// engine_mk_cmux_net.hip — leveled mode under a multi-key cloud key: tfhe_mk_cmux_net_batch, CMUX networks (automata, decision diagrams)
+// wired by a public netlist on a caller's expanded RGSW selectors (tfhe_mk_tgsw_load / tfhe_mk_tgsw_expand_load, engine_keys.hip) and
+// MK TLWE samples; the multi-key network level kernel (kernels_mk_cmux_net.hpp) is compiled here and nowhere else
+#define TFHE_EMIT_MK_CMUX_NET_KERNELS
 #include "engine.hpp"
-#include "kernels_leveled.hpp"
-#include "kernels_cmux_net.hpp"
+#include "kernels_mk_cmux_net.hpp"
 #include "leveled_checks.hpp"
 
-static const char *const WHO = "cmux_net_batch";
+static const char *const WHO = "mk_cmux_net_batch";
 
-// what the entry point refuses before it looks at its arguments (the conditions of engine_leveled.hip's entry points)
-static int32_t cmux_net_state(tfhe_ctx *c)
-{
-    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key (leveled operations are single-key)", WHO);
-    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "%s: multi-device context (leveled operations run on a one-device context)", WHO);
-    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the network level kernel has no DIAG instantiation)", WHO);
-    return TFHE_OK;
-}
-
-// One validated call on a device context: `levels` launches over B rows.  Level 0 reads row g's E samples at data[table_index[g]],
-// level v > 0 the widths[v-1] outputs of the level below; the F = widths[levels-1] outputs of the last level are the result.
-// Workspaces: buffer 0 holds the outputs of the even levels, buffer 1 those of the odd ones, each sized by its own widest level.
-static int32_t run_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths, int32_t levels,
-                       const int32_t *nodes, size_t total_nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form)
+// One validated call on a device context: engine_cmux_net.hip's run_net on MK samples of (P + 1) polynomials.  Level 0 reads row g's E
+// samples at data[table_index[g]], level v > 0 the widths[v-1] outputs of the level below; the F = widths[levels-1] outputs of the last
+// level are the result.  Workspaces: buffer 0 holds the outputs of the even levels, buffer 1 those of the odd ones, each sized by its
+// own widest level.  Timing events as the gate entry points: levels in slot 0, keyswitch in slot 1.
+static int32_t run_mk_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths, int32_t levels,
+                          const int32_t *nodes, size_t total_nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int N = c->P.N, K1 = c->P.k + 1, M = N / 2 > 0 ? N / 2 : 1, n = c->P.n, kNn = c->P.k * N;
-    const size_t sample = (size_t)K1 * N;
+    const int N = c->P.N, NP = c->mk_parties, K1 = NP + 1, M = N / 2 > 0 ? N / 2 : 1, n = c->P.n;
+    const size_t sample = (size_t)K1 * N, ext_w = (size_t)NP * N + 1, out_w = (size_t)NP * n + 1;
     size_t wmax[2] = {0, 0}, wall = 0;                              // the widest even level, the widest odd level, the widest level
     for (int lv = 0; lv < levels; lv++) {
         const size_t w = (size_t)widths[lv];
@@ -35,7 +26,7 @@ static int32_t run_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, c
         if (w > wall) wall = w;
     }
     const size_t B_ = (size_t)B, F = (size_t)widths[levels - 1], G = B_ * F;
-    const bool fits = leveled::lds_bytes(N, K1) <= 160 * 1024;
+    const bool fits = leveled::mk_lds_bytes(N, true) <= 160 * 1024;
     const bool spec_lds = c->anyn_spec < 0 ? fits : (c->anyn_spec == 0 && fits);
     auto up = [](size_t words) { return (words + 63) / 64 * 64; };
     // e0 [B F] (the keyswitch's identity map) | table_index [B] | sel [B][V] | nodes [total][3]
@@ -45,9 +36,9 @@ static int32_t run_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, c
         {&c->lvl_data, data_bytes},
         {&c->lvl_ws[0], B_ * wmax[0] * sample * 4},
         {&c->lvl_ws[1], B_ * wmax[1] * sample * 4},
-        {&c->lvl_spec, spec_lds ? 0 : B_ * wall * K1 * M * sizeof(cplx)},
-        {&c->ext, out_form >= 1 ? G * (kNn + 1) * 4 : 0},
-        {&c->io[3], out_form == 2 ? G * (n + 1) * 4 : 0},
+        {&c->lvl_spec, spec_lds ? 0 : B_ * wall * 3 * M * sizeof(cplx)},
+        {&c->ext, out_form >= 1 ? G * ext_w * 4 : 0},
+        {&c->io[3], out_form == 2 ? G * out_w * 4 : 0},
         {&c->map, map_bytes},
     };
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }       // (the workspaces may still be in use by a call on another stream)
@@ -66,16 +57,17 @@ static int32_t run_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, c
     HIP_TRY(c, hipMemcpyAsync(c->lvl_data.p, data, data_bytes, hipMemcpyHostToDevice, s));
     const int32_t *d_map = (const int32_t *)c->map.p;
 
-    leveled::NetArgs a;
+    leveled::MkNetArgs a;
     a.sel = d_map + o_sel;
-    a.tgsw = c->d_tgsw;
+    a.party_of = c->d_mk_tgsw_party;
+    a.tgsw = c->d_mk_tgsw;
     a.spec_g = spec_lds ? nullptr : (cplx *)c->lvl_spec.p;
     a.wtab = c->d_anyn_tab; a.twist = c->d_anyn_tab + N / 2;
     a.g = c->g;
-    a.K1 = K1; a.L = c->P.bs_l; a.log2N = ilog2i(N);
+    a.parties = NP; a.L = c->P.bs_l; a.log2N = ilog2i(N);
     a.V = V;
-    const size_t lds = leveled::lds_bytes(N, spec_lds ? K1 : 0);
-    if (lds > 64 * 1024) LDS_TRY(c, lds, leveled::cmux_net_level_kernel);
+    const size_t lds = leveled::mk_lds_bytes(N, spec_lds);
+    if (lds > 64 * 1024) LDS_TRY(c, lds, leveled::mk_cmux_net_level_kernel);
     const unsigned nt = (unsigned)anyn::threads_for(N);
 
     next_timing_slot(c);
@@ -94,7 +86,7 @@ static int32_t run_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, c
         a.out = last && out_form != 0 ? nullptr : (int32_t *)c->lvl_ws[lv & 1].p;
         a.ext = last && out_form != 0 ? (int32_t *)c->ext.p : nullptr;
         if (last) final_tlwe = a.out;
-        hipLaunchKernelGGL(leveled::cmux_net_level_kernel, dim3((unsigned)(B_ * w)), dim3(nt), lds, s, a);
+        hipLaunchKernelGGL(leveled::mk_cmux_net_level_kernel, dim3((unsigned)(B_ * w)), dim3(nt), lds, s, a);
         HIP_TRY(c, hipGetLastError());
         first_node += w;
     }
@@ -105,36 +97,39 @@ static int32_t run_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, c
     }
     HIP_TRY(c, hipEventRecord(c->ev[3], s));
     if (out_form == 0) HIP_TRY(c, hipMemcpyAsync(out, final_tlwe, G * sample * 4, hipMemcpyDeviceToHost, s));
-    else if (out_form == 1) HIP_TRY(c, hipMemcpyAsync(out, c->ext.p, G * (kNn + 1) * 4, hipMemcpyDeviceToHost, s));
-    else HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, G * (n + 1) * 4, hipMemcpyDeviceToHost, s));
+    else if (out_form == 1) HIP_TRY(c, hipMemcpyAsync(out, c->ext.p, G * ext_w * 4, hipMemcpyDeviceToHost, s));
+    else HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, G * out_w * 4, hipMemcpyDeviceToHost, s));
     rc = leave_stream(c, s);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     commit_timing_slot(c);
     c->last_rotations = 0;
     c->diag_rows = 0;
-    name_kernel(c, spec_lds ? "cmux_net_level_kernel(N=%d,k=%d,l=%d)" : "cmux_net_level_kernel(N=%d,k=%d,l=%d,spec=global)", N, c->P.k, c->P.bs_l);
+    name_kernel(c, spec_lds ? "mk_cmux_net_level_kernel(N=%d,P=%d,l=%d)" : "mk_cmux_net_level_kernel(N=%d,P=%d,l=%d,spec=global)", N, NP, c->P.bs_l);
     return TFHE_OK;
 }
 
-int32_t tfhe_cmux_net_batch(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths, int32_t levels,
-                            const int32_t *nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form) try
+int32_t tfhe_mk_cmux_net_batch(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths, int32_t levels,
+                               const int32_t *nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form) try
 {
     ENTER_CTX(c);
     if (!c) return TFHE_ERR_INVALID_ARG;
     if (B < 0) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: B = %lld is negative", WHO, (long long)B);
     if (!widths || !nodes) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL network (widths, nodes)", WHO);
     if (B > 0 && (!data || !sel || !out)) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL argument (data, sel, out)", WHO);
-    int32_t rc = cmux_net_state(c);
+    int32_t rc = mk_leveled_state(c, WHO);
     if (rc) return rc;
     size_t total_nodes = 0;
     rc = net_check_netlist(c, WHO, T, E, widths, levels, nodes, V, B, out_form, &total_nodes);
     if (rc) return rc;
-    if (!c->d_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (tfhe_tgsw_load)", WHO);
-    if (out_form == 2 && !c->have_ks()) return c->set_err(TFHE_ERR_NO_KEY, "%s: out_form 2 needs the keyswitch key", WHO);
-    rc = net_check_rows(c, WHO, sel, V, B, c->tgsw_count, table_index, T);
+    if (out_form == 2 && !c->have_mk_ks()) return c->set_err(TFHE_ERR_NO_KEY, "%s: out_form 2 needs the multi-key keyswitch key", WHO);
+    // (the keyswitch addresses rows by ITS key's parties, the levels write them by the bootstrapping key's: they must agree)
+    if (out_form == 2 && c->ks.parties != c->mk_parties)
+        return c->set_err(TFHE_ERR_STATE, "%s: the bootstrapping key was loaded for %d parties, the keyswitch key for %d: load both for the same parties", WHO,
+                          c->mk_parties, c->ks.parties);
+    rc = net_check_rows(c, WHO, sel, V, B, c->mk_tgsw_count, table_index, T);
     if (rc) return rc;
     if (B == 0) return TFHE_OK;
-    return run_net(c, data, T, E, table_index, widths, levels, nodes, total_nodes, sel, V, out, B, out_form);
+    return run_mk_net(c, data, T, E, table_index, widths, levels, nodes, total_nodes, sel, V, out, B, out_form);
 }
-ABI_CATCH(c, "tfhe_cmux_net_batch")
+ABI_CATCH(c, "tfhe_mk_cmux_net_batch")

@@ -4,17 +4,7 @@
 #define TFHE_EMIT_MK_LEVELED_KERNELS
 #include "engine.hpp"
 #include "kernels_mk_leveled.hpp"
-
-// what both entry points refuse before they look at their arguments
-static int32_t mk_leveled_state(tfhe_ctx *c, const char *who)
-{
-    if (c->P.parties < 2) return c->set_err(TFHE_ERR_STATE, "%s: context is single-key (tfhe_extern_mul_batch / tfhe_cmux_tree_batch are its leveled calls)", who);
-    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "%s: multi-device context (leveled operations run on a one-device context)", who);
-    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the CMUX level kernel has no DIAG instantiation)", who);
-    if (!c->have_mk_bk) return c->set_err(TFHE_ERR_NO_KEY, "%s: no multi-key bootstrapping key loaded", who);
-    if (!c->d_mk_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (tfhe_mk_tgsw_load)", who);
-    return TFHE_OK;
-}
+#include "leveled_checks.hpp"      // mk_leveled_state
 
 // One validated call on a device context: run_levels of engine_leveled.hip on MK samples of (P + 1) polynomials.  Host arrays: in
 // [in_rows][2^depth or 1][P+1][N], row_index [B] or NULL = row 0 (d0_zero: row g), sel [B][depth].  out_form 0: the MK TLWE sample

@@ -1,0 +1,71 @@
+// leveled_checks.hpp — host-only checks that more than one leveled unit makes before anything is uploaded: the state a multi-key
+// leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip) and the netlist of a CMUX network (engine_cmux_net.hip,
+// engine_mk_cmux_net.hip).  Every function sets the context's error message, naming the caller `who`, and returns its code.
+#pragma once
+#include "engine.hpp"
+
+enum { NET_MAX_LEVELS = 1024, NET_MAX_WIDTH = 4096 };
+
+// what the multi-key leveled entry points refuse before they look at their arguments
+inline int32_t mk_leveled_state(tfhe_ctx *c, const char *who)
+{
+    if (c->P.parties < 2) return c->set_err(TFHE_ERR_STATE, "%s: context is single-key (tfhe_extern_mul_batch / tfhe_cmux_tree_batch are its leveled calls)", who);
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "%s: multi-device context (leveled operations run on a one-device context)", who);
+    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the CMUX level kernel has no DIAG instantiation)", who);
+    if (!c->have_mk_bk) return c->set_err(TFHE_ERR_NO_KEY, "%s: no multi-key bootstrapping key loaded", who);
+    if (!c->d_mk_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (tfhe_mk_tgsw_load)", who);
+    return TFHE_OK;
+}
+
+// The public part of a CMUX-network call, O(nodes): the scalar arguments, every width (and B * width within one launch), every
+// record's sources against the level below (E at level 0) and its var against V.  *total_nodes = sum of the widths.
+inline int32_t net_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_t E, const int32_t *widths, int32_t levels, const int32_t *nodes,
+                                 int32_t V, int64_t B, int32_t out_form, size_t *total_nodes)
+{
+    if (levels < 1 || levels > NET_MAX_LEVELS) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: levels = %d (1 ... %d)", who, levels, (int)NET_MAX_LEVELS);
+    if (E < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: E = %d (at least one table entry)", who, E);
+    if (V < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: V = %d (at least one variable)", who, V);
+    if (T < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: T = %lld (at least one table)", who, (long long)T);
+    if ((double)T * (double)E > 2147483647.0)
+        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: T * E = %.0f table entries (at most 2^31 - 1)", who, (double)T * (double)E);
+    if (out_form < 0 || out_form > 2) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: out_form = %d (0 TLWE, 1 extracted, 2 key-switched)", who, out_form);
+    size_t total = 0;
+    for (int lv = 0; lv < levels; lv++) {
+        if (widths[lv] < 1 || widths[lv] > NET_MAX_WIDTH)
+            return c->set_err(TFHE_ERR_INVALID_ARG, "%s: widths[%d] = %d (1 ... %d)", who, lv, widths[lv], (int)NET_MAX_WIDTH);
+        if ((double)B * (double)widths[lv] > 2147483647.0)
+            return c->set_err(TFHE_ERR_INVALID_ARG, "%s: B * widths[%d] = %.0f workgroups exceed one launch", who, lv, (double)B * (double)widths[lv]);
+        total += (size_t)widths[lv];
+    }
+    const int32_t *rec = nodes;
+    for (int lv = 0; lv < levels; lv++) {
+        const int32_t below = lv == 0 ? E : widths[lv - 1];
+        for (int i = 0; i < widths[lv]; i++, rec += 3) {
+            for (int e = 0; e < 2; e++)
+                if (rec[e] < 0 || rec[e] >= below)
+                    return c->set_err(TFHE_ERR_INVALID_ARG, "%s: node %d of level %d: src%d = %d is outside the %d %s below", who, i, lv, e, rec[e], below,
+                                      lv == 0 ? "table entries" : "nodes");
+            if (rec[2] < 0 || rec[2] >= V)
+                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: node %d of level %d: var = %d is outside [0, %d)", who, i, lv, rec[2], V);
+        }
+    }
+    *total_nodes = total;
+    return TFHE_OK;
+}
+
+// The per-row part, O(B V): every selector against the `selectors` loaded ones, every table index against T.
+inline int32_t net_check_rows(tfhe_ctx *c, const char *who, const int32_t *sel, int32_t V, int64_t B, int64_t selectors, const int32_t *table_index, int64_t T)
+{
+    for (int64_t g = 0; g < B; g++)
+        for (int32_t v = 0; v < V; v++) {
+            const int32_t e = sel[g * V + v];
+            if (e < 0 || e >= selectors)
+                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: sel[%lld][%d] = %d is outside the %lld loaded selectors", who, (long long)g, (int)v, e,
+                                  (long long)selectors);
+        }
+    if (table_index)
+        for (int64_t g = 0; g < B; g++)
+            if (table_index[g] < 0 || table_index[g] >= T)
+                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: table_index[%lld] = %d is outside [0, %lld)", who, (long long)g, table_index[g], (long long)T);
+    return TFHE_OK;
+}

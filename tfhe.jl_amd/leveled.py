@@ -22,7 +22,8 @@ it owns (mk_tgsw_uni_encrypt_bits: RGSW.UniEnc, mk_internals.jl:185-227) under t
 keeps, the cloud expands them against all public keys (mk_tgsw_expand: RGSW.Expand, :304-345; or on the device) and folds a table of
 MK TLWE samples [P+1][N] with mk_tgsw_extern_mul (:348-391).  Keyswitched (out_form 2) the result is a multi-key LWE sample that
 mk_decrypt and every mk_gate accept.  Engine.mk_tgsw_load / mk_tgsw_expand_load / mk_extern_mul / mk_cmux_tree; mk_cmux_lookup strings
-them together.
+them together.  The CMUX networks above run on the same selectors (Engine.mk_cmux_net, tfhe_mk_cmux_net_batch; mk_cmux_net_lookup):
+the comparison of two integers that two parties hold is less_than_net on their uni-encrypted bits.
 """
 import numpy as np
 
@@ -306,23 +307,42 @@ def mk_cmux_lookup(ck, tables, uni_bits, party_of, out_form=2, expand="device", 
     party_of[g][v] (party_of: [B][d], or [d] for every row).  expand "device": RGSW.Expand on the GPU (tfhe_mk_tgsw_expand_load),
     "host": numpy (mk_tgsw_expand) then mk_tgsw_load.  out_form 2 (default): multi-key LWE samples int32 [B][P*n+1] for mk_decrypt /
     mk_gate_*; 1: extracted [B][P*N+1]; 0: MK TLWE samples [B][P+1][N]."""
+    eng, sel = _mk_load_selectors(ck, uni_bits, party_of, expand, device, "depth")
+    return eng.mk_cmux_tree(tables, sel, table_index=table_index, out_form=out_form)
+
+
+def _mk_load_selectors(ck, uni_bits, party_of, expand, device, what):
+    """Expand B rows of C uni-encrypted bits (six arrays [B][C][l][N], bit c of row g by party party_of[g][c]) into the selector set of
+    ck's engine on `device`, on the GPU or in numpy.  Returns the engine and sel [B][C], row g's selectors in order."""
     assert expand in ("device", "host")
     arrs = [np.asarray(a, np.int32) for a in uni_bits]
     if len(arrs) != 6 or arrs[0].ndim != 4 or any(a.shape != arrs[0].shape for a in arrs):
-        raise ValueError("uni_bits must be six arrays [B][depth][l][N]")
-    B, depth = arrs[0].shape[:2]
-    who = np.broadcast_to(np.asarray(party_of, np.int32), (B, depth)).reshape(-1)
-    flat = [a.reshape((B * depth,) + a.shape[2:]) for a in arrs]
+        raise ValueError(f"uni_bits must be six arrays [B][{what}][l][N]")
+    B, C = arrs[0].shape[:2]
+    who = np.broadcast_to(np.asarray(party_of, np.int32), (B, C)).reshape(-1)
+    flat = [a.reshape((B * C,) + a.shape[2:]) for a in arrs]
     pub = np.stack([part.public_b for part in ck._parts])
     eng = ck.engine(device)
     if expand == "device":
         eng.mk_tgsw_expand_load(pub, who, *flat)
     else:
-        tg = np.zeros((B * depth, 2 * arrs[0].shape[2] * (ck.parties + 1), arrs[0].shape[3]), np.int32)
+        tg = np.zeros((B * C, 2 * arrs[0].shape[2] * (ck.parties + 1), arrs[0].shape[3]), np.int32)
         for i in range(ck.parties):
             mine = np.nonzero(who == i)[0]
             if mine.size:
                 tg[mine] = mk_tgsw_expand(ck.params, pub, i, *[a[mine] for a in flat])
         eng.mk_tgsw_load(tg, who)
-    sel = np.arange(B * depth, dtype=np.int32).reshape(B, depth)
-    return eng.mk_cmux_tree(tables, sel, table_index=table_index, out_form=out_form)
+    return eng, np.arange(B * C, dtype=np.int32).reshape(B, C)
+
+
+def mk_cmux_net_lookup(ck, data, net, uni_bits, party_of, out_form=2, expand="device", device=0, table_index=None):
+    """The network `net` on B rows of jointly encrypted variables under the MKCloudKey ck (Engine.mk_cmux_net, tfhe_mk_cmux_net_batch).
+    data: int32 [E][P+1][N] or [T][E][P+1][N] with table_index [B]; the table of an automaton under P parties is
+    table_to_tlwe(values, N, k=P): trivial samples with P zero masks.  uni_bits: the six arrays of mk_tgsw_uni_encrypt_bits, each
+    [B][V][l][N], variable v of row g uni-encrypted by party party_of[g][v] (party_of: [B][V], or [V] for every row); expand as
+    mk_cmux_lookup.  With less_than_net(d), party 0 owning x (variables 0 ... d-1) and party 1 owning y (d ... 2d-1), the one output
+    is x < y and neither party shows its integer.  out_form 2 (default): multi-key LWE samples int32 [B F][P*n+1] for mk_decrypt /
+    mk_gate_* (row g's output i at g F + i; F = 1 for an automaton); 1: extracted [B][F][P*N+1]; 0: MK TLWE samples [B][F][P+1][N]."""
+    eng, sel = _mk_load_selectors(ck, uni_bits, party_of, expand, device, "V")
+    out = eng.mk_cmux_net(data, net, sel, table_index=table_index, out_form=out_form)
+    return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
