@@ -457,6 +457,26 @@ int32_t tfhe_cmux_tree_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, cons
 int32_t tfhe_cmux_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths,
                             int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form);
 
+/* CMUX network with a public monomial on every edge (addition within ABI v7): tfhe_cmux_net_batch's contract with one difference, a node
+ * record of five words, nodes: host int32 [sum widths][5] = (src0, src1, var, rot0, rot1).  Node i of level v of row g is
+ *     X^rot0 in[src0] + selector[sel[g][var]] (.) (X^rot1 in[src1] - X^rot0 in[src0])
+ * where X^r p is mul_by_monomial(p, r) (bootstrap.jl:21, :54) on every polynomial of the sample, mask and body: coefficient j moves to
+ * j + r mod 2N and changes sign past N.  rot0, rot1 are public, in [0, 2N).  A node with src0 == src1 and rot0 == rot1 is a rotated
+ * copy: no product, no noise, the exact words of X^rot0 in[src0].  A node with src0 == src1 and rot0 != rot1 is a true product:
+ * CMUX(C_b; acc, X^(2N - 2^b) acc) for b = 0 ... r-1 rotates acc by minus an encrypted r-bit index (the blind rotation by TGSW bits),
+ * which brings entry `index` of a table packed N entries to a sample to coefficient 0, where out_form 1 and 2 extract: a 2^d-entry
+ * table costs 2^(d - log2 N) - 1 + log2 N external products per lookup instead of 2^d - 1.  X^w on the transitions of an automaton
+ * gives weighted automata (output X^(sum of weights) table[end state]).  With every rotation 0 the call equals tfhe_cmux_net_batch
+ * word for word.
+ * Everything else is tfhe_cmux_net_batch's: the limits (1024 levels, width 4096, B * width within one launch), data, table_index, sel,
+ * the three out_forms (extraction at coefficient 0), the two workspaces sized per level parity and TFHE_ERR_NOMEM before any
+ * allocation, the order of the refusals, B = 0, the tfhe_last_timing_ms slots.  TFHE_ERR_INVALID_ARG also for a rotation outside
+ * [0, 2N), the message naming node, level and field (rot0 / rot1), before anything is uploaded.  One launch per level
+ * (csrc/kernels_rot_net.hpp; tfhe_last_kernel_name reports "rot_net_level_kernel(N=..,k=..,l=..[,spec=global])"; the option
+ * "anyn_spec" is honoured). */
+int32_t tfhe_rot_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths,
+                           int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form);
+
 /* ---- leveled mode under a multi-key cloud key (additions within ABI v7) ---------------------------------
  * The same two operations on multi-key samples, with no blind rotation: the selectors are the parties' uni-encryptions of address
  * bits (mk_tgsw_encrypt, RGSW.UniEnc, mk_internals.jl:185-227) expanded against all public keys (mk_tgsw_expand, :304-345), the

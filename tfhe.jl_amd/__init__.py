@@ -19,6 +19,7 @@ from .lut import (lut_encode, lut_decode, lut_encrypt, lut_decrypt, make_test_ve
 from .serialize import save_cloud_key, load_cloud_key
 from .leveled import tlwe_encrypt, tlwe_trivial, tlwe_phase, tgsw_encrypt_bits, table_to_tlwe, cmux_lookup
 from .leveled import CmuxNet, tree_net, dfa_net, less_than_net, cmux_net_lookup
+from .leveled import RotNet, pack_table_to_tlwe, packed_lookup_net, wfa_net, rot_net_lookup, packed_lookup
 from .leveled import mk_tlwe_trivial, mk_tlwe_encrypt, mk_tlwe_phase, mk_tgsw_uni_encrypt_bits, mk_tgsw_expand, mk_cmux_lookup, mk_cmux_net_lookup
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
 
@@ -35,5 +36,6 @@ __all__ = [
     "make_multi_test_vector", "programmable_bootstrap_multi", "make_gate_test_vector", "GATE_BIT_TO_Z2",
     "tlwe_encrypt", "tlwe_trivial", "tlwe_phase", "tgsw_encrypt_bits", "table_to_tlwe", "cmux_lookup",
     "CmuxNet", "tree_net", "dfa_net", "less_than_net", "cmux_net_lookup",
+    "RotNet", "pack_table_to_tlwe", "packed_lookup_net", "wfa_net", "rot_net_lookup", "packed_lookup",
     "save_cloud_key", "load_cloud_key", "Engine", "EngineError", "OPCODES", "LIB_PATH", "pinned_empty",
 ]

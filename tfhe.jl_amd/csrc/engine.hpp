@@ -16,6 +16,7 @@
 //   engine_mk_leveled.hip the same under a multi-key cloud key: expanded RGSW selectors, MK TLWE samples          ("mk leveled")
 //   engine_cmux_net.hip   leveled mode: CMUX networks (automata, decision diagrams) wired by a public netlist          ("cmux net")
 //   engine_mk_cmux_net.hip  the same networks under a multi-key cloud key                                              ("mk cmux net")
+//   engine_rot_net.hip    leveled mode: CMUX networks with a monomial X^rot on every edge (packed tables, weighted automata)  ("rot net")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions

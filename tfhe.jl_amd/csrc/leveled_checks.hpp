@@ -1,6 +1,6 @@
 // leveled_checks.hpp — host-only checks that more than one leveled unit makes before anything is uploaded: the state a multi-key
 // leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip) and the netlist of a CMUX network (engine_cmux_net.hip,
-// engine_mk_cmux_net.hip).  Every function sets the context's error message, naming the caller `who`, and returns its code.
+// engine_mk_cmux_net.hip; with monomial edges: engine_rot_net.hip).  Every function sets the context's error message, naming the caller `who`, and returns its code.
 #pragma once
 #include "engine.hpp"
 
@@ -18,9 +18,10 @@ inline int32_t mk_leveled_state(tfhe_ctx *c, const char *who)
 }
 
 // The public part of a CMUX-network call, O(nodes): the scalar arguments, every width (and B * width within one launch), every
-// record's sources against the level below (E at level 0) and its var against V.  *total_nodes = sum of the widths.
-inline int32_t net_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_t E, const int32_t *widths, int32_t levels, const int32_t *nodes,
-                                 int32_t V, int64_t B, int32_t out_form, size_t *total_nodes)
+// record's sources against the level below (E at level 0) and its var against V.  *total_nodes = sum of the widths.  A record has
+// `words` words: (src0, src1, var), and with words = 5 the rotations (rot0, rot1) of a network with monomial edges, each in [0, two_n).
+inline int32_t net_check_records(tfhe_ctx *c, const char *who, int64_t T, int32_t E, const int32_t *widths, int32_t levels, const int32_t *nodes,
+                                 int32_t V, int64_t B, int32_t out_form, size_t *total_nodes, int words, int32_t two_n)
 {
     if (levels < 1 || levels > NET_MAX_LEVELS) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: levels = %d (1 ... %d)", who, levels, (int)NET_MAX_LEVELS);
     if (E < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: E = %d (at least one table entry)", who, E);
@@ -40,17 +41,34 @@ inline int32_t net_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_
     const int32_t *rec = nodes;
     for (int lv = 0; lv < levels; lv++) {
         const int32_t below = lv == 0 ? E : widths[lv - 1];
-        for (int i = 0; i < widths[lv]; i++, rec += 3) {
+        for (int i = 0; i < widths[lv]; i++, rec += words) {
             for (int e = 0; e < 2; e++)
                 if (rec[e] < 0 || rec[e] >= below)
                     return c->set_err(TFHE_ERR_INVALID_ARG, "%s: node %d of level %d: src%d = %d is outside the %d %s below", who, i, lv, e, rec[e], below,
                                       lv == 0 ? "table entries" : "nodes");
             if (rec[2] < 0 || rec[2] >= V)
                 return c->set_err(TFHE_ERR_INVALID_ARG, "%s: node %d of level %d: var = %d is outside [0, %d)", who, i, lv, rec[2], V);
+            for (int e = 3; e < words; e++)
+                if (rec[e] < 0 || rec[e] >= two_n)
+                    return c->set_err(TFHE_ERR_INVALID_ARG, "%s: node %d of level %d: rot%d = %d is outside [0, %d)", who, i, lv, e - 3, rec[e], two_n);
         }
     }
     *total_nodes = total;
     return TFHE_OK;
+}
+
+// the netlist of tfhe_cmux_net_batch / tfhe_mk_cmux_net_batch: records (src0, src1, var)
+inline int32_t net_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_t E, const int32_t *widths, int32_t levels, const int32_t *nodes,
+                                 int32_t V, int64_t B, int32_t out_form, size_t *total_nodes)
+{
+    return net_check_records(c, who, T, E, widths, levels, nodes, V, B, out_form, total_nodes, 3, 0);
+}
+
+// the netlist of tfhe_rot_net_batch: records (src0, src1, var, rot0, rot1), the rotations public exponents of X in [0, 2N)
+inline int32_t rot_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_t E, const int32_t *widths, int32_t levels, const int32_t *nodes,
+                                 int32_t V, int32_t N, int64_t B, int32_t out_form, size_t *total_nodes)
+{
+    return net_check_records(c, who, T, E, widths, levels, nodes, V, B, out_form, total_nodes, 5, 2 * N);
 }
 
 // The per-row part, O(B V): every selector against the `selectors` loaded ones, every table index against T.

@@ -24,6 +24,12 @@ MK TLWE samples [P+1][N] with mk_tgsw_extern_mul (:348-391).  Keyswitched (out_f
 mk_decrypt and every mk_gate accept.  Engine.mk_tgsw_load / mk_tgsw_expand_load / mk_extern_mul / mk_cmux_tree; mk_cmux_lookup strings
 them together.  The CMUX networks above run on the same selectors (Engine.mk_cmux_net, tfhe_mk_cmux_net_batch; mk_cmux_net_lookup):
 the comparison of two integers that two parties hold is less_than_net on their uni-encrypted bits.
+
+A network with monomial edges (RotNet; Engine.rot_net, tfhe_rot_net_batch; rot_net_lookup) multiplies each source of a CMUX by a public
+X^rot (mul_by_monomial, bootstrap.jl:21, :54).  CMUX(C_b; acc, X^(-2^b) acc) for the low address bits b is the blind rotation by TGSW
+bits: a table packed N entries to a sample (pack_table_to_tlwe, "vertical packing") is read at 2^(d - log2 N) - 1 + log2 N external
+products instead of 2^d - 1 (packed_lookup_net, packed_lookup), and an automaton with X^weight on its transitions (wfa_net) returns
+X^(sum of weights) table[end state]: f(popcount(x)) of up to N - 1 encrypted bits is one state and one product per bit.
 """
 import numpy as np
 
@@ -120,6 +126,46 @@ def cmux_lookup(ck, tables, address_tgsw, out_form=2, device=0, table_index=None
 NET_MAX_LEVELS, NET_MAX_WIDTH = 1024, 4096
 
 
+def _check_netlist(widths, nodes, fields, entries, variables, two_n):
+    """The validation of net_check_netlist / rot_check_netlist (csrc/leveled_checks.hpp) with their messages: widths, then every record's
+    sources against the level below, its var against V and, in a five-word record, its rotations against [0, two_n).  Returns widths
+    and nodes as int32 arrays, E and V."""
+    w = np.asarray(widths)
+    if w.ndim != 1 or not np.issubdtype(w.dtype, np.integer) or not 1 <= w.size <= NET_MAX_LEVELS:
+        raise ValueError(f"widths must be 1 ... {NET_MAX_LEVELS} integers, got shape {w.shape}")
+    for v, x in enumerate(w):
+        if not 1 <= x <= NET_MAX_WIDTH:
+            raise ValueError(f"widths[{v}] = {x} (1 ... {NET_MAX_WIDTH})")
+    nd = np.asarray(nodes)
+    if not np.issubdtype(nd.dtype, np.integer) or nd.shape != (int(w.sum()), len(fields)):
+        raise ValueError(f"nodes must be integers [{int(w.sum())}][{len(fields)}] = ({', '.join(fields)}), got {nd.shape}")
+    nd = nd.astype(np.int64)
+    need_e = int(nd[:w[0], :2].max()) + 1
+    need_v = int(nd[:, 2].max()) + 1
+    E = need_e if entries is None else int(entries)
+    V = need_v if variables is None else int(variables)
+    if E < 1 or V < 1:
+        raise ValueError(f"entries = {E}, variables = {V} (at least one each)")
+    first = 0
+    for v, x in enumerate(w):
+        below = E if v == 0 else int(w[v - 1])
+        lv = nd[first:first + int(x)]
+        bad = np.argwhere((lv[:, :2] < 0) | (lv[:, :2] >= below))
+        if bad.size:
+            i, e = (int(t) for t in bad[0])
+            what = "table entries" if v == 0 else "nodes"
+            raise ValueError(f"node {i} of level {v}: src{e} = {lv[i, e]} is outside the {below} {what} below")
+        bad = np.flatnonzero((lv[:, 2] < 0) | (lv[:, 2] >= V))
+        if bad.size:
+            raise ValueError(f"node {bad[0]} of level {v}: var = {lv[bad[0], 2]} is outside [0, {V})")
+        bad = np.argwhere((lv[:, 3:] < 0) | (lv[:, 3:] >= two_n))
+        if bad.size:
+            i, e = (int(t) for t in bad[0])
+            raise ValueError(f"node {i} of level {v}: {fields[3 + e]} = {lv[i, 3 + e]} is outside [0, {two_n})")
+        first += int(x)
+    return np.ascontiguousarray(w, np.int32), np.ascontiguousarray(nd, np.int32), E, V
+
+
 class CmuxNet:
     """The public wiring of a CMUX network, validated as tfhe_cmux_net_batch validates it.  widths: the node count of each level (1 ...
     1024 levels of 1 ... 4096 nodes); nodes: int32 [sum widths][3] = (src0, src1, var) in level order.  Node i of level v is
@@ -128,39 +174,8 @@ class CmuxNet:
     `variables` (V) default to the smallest counts the nodes need; given, the nodes are checked against them."""
 
     def __init__(self, widths, nodes, entries=None, variables=None):
-        w = np.asarray(widths)
-        if w.ndim != 1 or not np.issubdtype(w.dtype, np.integer) or not 1 <= w.size <= NET_MAX_LEVELS:
-            raise ValueError(f"widths must be 1 ... {NET_MAX_LEVELS} integers, got shape {w.shape}")
-        for v, x in enumerate(w):
-            if not 1 <= x <= NET_MAX_WIDTH:
-                raise ValueError(f"widths[{v}] = {x} (1 ... {NET_MAX_WIDTH})")
-        nd = np.asarray(nodes)
-        if not np.issubdtype(nd.dtype, np.integer) or nd.shape != (int(w.sum()), 3):
-            raise ValueError(f"nodes must be integers [{int(w.sum())}][3] = (src0, src1, var), got {nd.shape}")
-        nd = nd.astype(np.int64)
-        need_e = int(nd[:w[0], :2].max()) + 1
-        need_v = int(nd[:, 2].max()) + 1
-        E = need_e if entries is None else int(entries)
-        V = need_v if variables is None else int(variables)
-        if E < 1 or V < 1:
-            raise ValueError(f"entries = {E}, variables = {V} (at least one each)")
-        first = 0
-        for v, x in enumerate(w):
-            below = E if v == 0 else int(w[v - 1])
-            lv = nd[first:first + int(x)]
-            bad = np.argwhere((lv[:, :2] < 0) | (lv[:, :2] >= below))
-            if bad.size:
-                i, e = (int(t) for t in bad[0])
-                what = "table entries" if v == 0 else "nodes"
-                raise ValueError(f"node {i} of level {v}: src{e} = {lv[i, e]} is outside the {below} {what} below")
-            bad = np.flatnonzero((lv[:, 2] < 0) | (lv[:, 2] >= V))
-            if bad.size:
-                raise ValueError(f"node {bad[0]} of level {v}: var = {lv[bad[0], 2]} is outside [0, {V})")
-            first += int(x)
-        self.widths = np.ascontiguousarray(w, np.int32)
-        self.nodes = np.ascontiguousarray(nd, np.int32)
-        self.levels = int(w.size)
-        self.entries, self.variables = E, V
+        self.widths, self.nodes, self.entries, self.variables = _check_netlist(widths, nodes, ("src0", "src1", "var"), entries, variables, 0)
+        self.levels = int(self.widths.size)
 
     def level(self, v):
         """The records of level v, int32 [widths[v]][3]."""
@@ -245,6 +260,142 @@ def cmux_net_lookup(ck, data, net, bits_tgsw, out_form=2, device=0, table_index=
     sel = np.arange(B * V, dtype=np.int32).reshape(B, V)
     out = eng.cmux_net(data, net, sel, table_index=table_index, out_form=out_form)
     return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
+
+
+# ---- CMUX networks with monomial edges: packed tables and weighted automata ------------------------------------------------------
+def _monomial_clear(p, r, N):
+    """X^r p mod (X^N + 1) on a plain integer polynomial [N], 0 <= r < 2N: coefficient j moves to j + r mod 2N, the sign flips past N."""
+    p = np.asarray(p)
+    if r >= N:
+        p, r = -p, r - N
+    return np.concatenate([-p[N - r:], p[:N - r]])
+
+
+class RotNet:
+    """The public wiring of a CMUX network with monomial edges over polynomials of `degree` N coefficients, validated as
+    tfhe_rot_net_batch validates it.  widths as CmuxNet's; nodes: int32 [sum widths][5] = (src0, src1, var, rot0, rot1) in level order,
+    the rotations in [0, 2N).  Node i of level v is X^rot0 in[src0] + C_var (.) (X^rot1 in[src1] - X^rot0 in[src0]) — a variable that is
+    1 picks X^rot1 in[src1].  src0 == src1 with rot0 == rot1 is a rotated copy; src0 == src1 with rot0 != rot1 is a true product, the
+    step of a blind rotation.  `entries` and `variables` as CmuxNet's."""
+
+    def __init__(self, widths, nodes, degree, entries=None, variables=None):
+        N = int(degree)
+        if N < 2 or N & (N - 1):
+            raise ValueError(f"degree = {degree} (a power of two, at least 2)")
+        self.degree = N
+        self.widths, self.nodes, self.entries, self.variables = _check_netlist(widths, nodes, ("src0", "src1", "var", "rot0", "rot1"), entries,
+                                                                               variables, 2 * N)
+        self.levels = int(self.widths.size)
+
+    def level(self, v):
+        """The records of level v, int32 [widths[v]][5]."""
+        first = int(self.widths[:v].sum())
+        return self.nodes[first:first + int(self.widths[v])]
+
+    @property
+    def products(self):
+        """External products per row: the nodes that are not rotated copies."""
+        nd = self.nodes
+        return int(np.count_nonzero((nd[:, 0] != nd[:, 1]) | (nd[:, 3] != nd[:, 4])))
+
+    def evaluate_clear(self, entries, bits):
+        """The same wiring on plain integer polynomials [N] with the same negacyclic rotation: the outputs of the last level for table
+        `entries` and variable values `bits`."""
+        cur = [np.asarray(e) for e in entries]
+        if len(cur) < self.entries or len(bits) < self.variables or any(e.shape != (self.degree,) for e in cur):
+            raise ValueError(f"the network reads {self.entries} polynomials of {self.degree} coefficients and {self.variables} variables")
+        for v in range(self.levels):
+            cur = [_monomial_clear(cur[s1], r1, self.degree) if bits[var] else _monomial_clear(cur[s0], r0, self.degree)
+                   for s0, s1, var, r0, r1 in self.level(v).tolist()]
+        return cur
+
+
+def _packing(count, N):
+    """depth and r = min(depth, log2 N) of a packed table of `count` = 2^depth entries."""
+    depth = int(count).bit_length() - 1
+    if count < 2 or count != 1 << depth:
+        raise ValueError(f"a packed table has 2^depth entries (depth >= 1), got {count}")
+    return depth, min(depth, int(N).bit_length() - 1)
+
+
+def pack_table_to_tlwe(values, N, k=1, encode=encode_gate_bit, rng=None, secret_key=None):
+    """A table of 2^depth values packed 2^r = min(2^depth, N) to a sample, int32 [2^(depth-r)][k+1][N]: entry i carries encode(values[i])
+    on coefficient i & (2^r - 1) of sample i >> r; coefficients past 2^r are zero.  Trivial or encrypted samples as table_to_tlwe."""
+    depth, r = _packing(len(values), N)
+    mu = np.zeros((1 << (depth - r), N), np.int32)
+    mu[:, :1 << r] = wrap32(np.array([int(encode(v)) for v in values], np.int64)).reshape(-1, 1 << r)
+    if secret_key is None:
+        return tlwe_trivial(mu, k)
+    if rng is None:
+        raise ValueError("an encrypted table needs rng as well as secret_key")
+    return tlwe_encrypt(rng, secret_key, mu)
+
+
+def packed_lookup_net(depth, N):
+    """The network that reads a pack_table_to_tlwe table of 2^depth entries at an address of `depth` variables (variable b = address bit
+    b, bit 0 the lowest): with r = min(depth, log2 N), tree levels on the address bits r ... depth-1 fold the E = 2^(depth-r) samples to
+    the one that holds the entry, then for b = 0 ... r-1 the node (0, 0, b, 0, 2N - 2^b) multiplies by X^(-2^b) where bit b is set: the
+    entry arrives at coefficient 0.  E - 1 + r external products; depth 1 ... 24 while E <= 4096."""
+    logN = int(N).bit_length() - 1
+    if N < 2 or N != 1 << logN:
+        raise ValueError(f"N = {N} (a power of two, at least 2)")
+    if not 1 <= depth <= 24 or depth - min(depth, logN) > 12:
+        raise ValueError(f"depth = {depth} (1 ... 24, and at most 4096 table samples: depth <= {logN + 12} at N = {N})")
+    r = min(depth, logN)
+    widths = [1 << (depth - r - 1 - t) for t in range(depth - r)] + [1] * r
+    nodes = [(2 * i, 2 * i + 1, r + t, 0, 0) for t in range(depth - r) for i in range(widths[t])]
+    nodes += [(0, 0, b, 0, 2 * N - (1 << b)) for b in range(r)]
+    return RotNet(widths, nodes, N, entries=1 << (depth - r), variables=depth)
+
+
+def wfa_net(delta0, delta1, weight0, weight1, start, steps, N, letter_var=None):
+    """dfa_net with X^weight on every transition: state q moves to delta0[q] and multiplies by X^weight0[q] on letter 0, to delta1[q]
+    and X^weight1[q] on letter 1 (weights taken mod 2N).  The one output is X^(sum of the weights along the path) table[end state].  A
+    state whose two transitions and weights agree becomes a rotated copy.  One state looping on itself with weights 0 and 2N - 1
+    rotates by minus the popcount of the letters: f(popcount) for the table polynomial sum_c f(c) X^c."""
+    base = dfa_net(delta0, delta1, start, steps, letter_var)
+    w0, w1 = [int(w) % (2 * N) for w in weight0], [int(w) % (2 * N) for w in weight1]
+    Q = len(w0)
+    if Q != base.entries or len(w1) != Q:
+        raise ValueError("weight0 and weight1 must give a weight for every state")
+    reach = [[int(start)]]                                           # as dfa_net: the states after j letters, sorted
+    for j in range(steps - 1):
+        reach.append(sorted({d[q] for q in reach[-1] for d in (delta0, delta1)}))
+    rot = [(w0[q], w1[q]) for v in range(steps) for q in reach[steps - 1 - v]]
+    nodes = np.concatenate([base.nodes, np.array(rot, np.int32)], axis=1)
+    return RotNet(base.widths, nodes, N, entries=Q, variables=base.variables)
+
+
+def rot_net_lookup(ck, data, net, bits_tgsw, out_form=2, device=0, table_index=None):
+    """cmux_net_lookup for a RotNet: the network `net` on B rows of encrypted variables.  data: int32 [E][k+1][N] or [T][E][k+1][N]
+    with table_index [B]; bits_tgsw: int32 [B][V][l][k+1][k+1][N].  out_form as cmux_net_lookup (extraction at coefficient 0)."""
+    a = np.asarray(bits_tgsw, np.int32)
+    if a.ndim != 6:
+        raise ValueError(f"bits_tgsw must be [B][V][l][k+1][k+1][N], got {a.shape}")
+    B, V = a.shape[:2]
+    eng = ck.engine(device)
+    eng.tgsw_load(a.reshape((B * V,) + a.shape[2:]))
+    sel = np.arange(B * V, dtype=np.int32).reshape(B, V)
+    out = eng.rot_net(data, net, sel, table_index=table_index, out_form=out_form)
+    return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
+
+
+def packed_lookup(ck, table, address_tgsw, out_form=2, device=0, encode=encode_gate_bit):
+    """table[address] for B encrypted addresses through a packed table: cmux_lookup at 2^(d - log2 N) - 1 + log2 N external products per
+    address.  table: 2^d plain values (packed here by pack_table_to_tlwe as trivial samples) or the packed samples themselves, int32
+    [2^(d-r)][k+1][N]; address_tgsw: int32 [B][d][l][k+1][k+1][N] as cmux_lookup's.  out_form 2 (default): an LweSampleArray of B
+    samples under the gate key; 1: extracted [B][k N + 1]; 0: the TLWE samples [B][k+1][N], the entry on coefficient 0."""
+    a = np.asarray(address_tgsw, np.int32)
+    if a.ndim != 6:
+        raise ValueError(f"address_tgsw must be [B][depth][l][k+1][k+1][N], got {a.shape}")
+    depth, N, k = a.shape[1], a.shape[-1], a.shape[3] - 1
+    t = np.asarray(table)
+    data = pack_table_to_tlwe(list(t), N, k, encode) if t.ndim == 1 else t
+    net = packed_lookup_net(depth, N)
+    if data.shape[0] != net.entries:
+        raise ValueError(f"a packed table of 2^{depth} entries has {net.entries} samples, got {data.shape[0]}")
+    out = rot_net_lookup(ck, data, net, a, out_form=out_form, device=device)
+    return out if out_form == 2 else out[:, 0]
 
 
 # ---- under a multi-key cloud key -------------------------------------------------------------------------------------------------
