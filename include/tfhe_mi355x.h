@@ -404,7 +404,8 @@ int32_t tfhe_mk_linear_level(tfhe_ctx *ctx, const int32_t *term_start, const int
  * and no blind rotation; the result can leave as an LWE sample under the gate key and go into tfhe_gates_batch.
  * Formats: TLWE sample int32 [k+1][N] = a[0..k-1], b (tlwe.jl:34-41); TGSW sample int32 [l][k+1][k+1][N] = samples[p, j].a[c]
  * (tgsw.jl:25-32), exactly one entry of the bootstrapping key's canonical form.  One kernel (csrc/kernels_leveled.hpp) serves every
- * parameter set a context accepts; tfhe_last_kernel_name reports "cmux_level_kernel(N=..,k=..,l=..)".
+ * parameter set a context accepts; tfhe_last_kernel_name reports "cmux_level_kernel(N=..,k=..,l=..[,spec=global])" (the option "anyn_spec"
+ * = 1 puts the spectrum accumulators in global memory, as for the network kernels; the multi-key tree kernel reads it the same way).
  * Exactness: as the rotation, (k+1) l digit-by-selector products are summed in Float64 before the one rounding per coefficient:
  * "exact_domain" (tfhe_get_option) applies unchanged, with the selector words in the place of the key words.
  * All three follow the one-caller-at-a-time rule and return TFHE_ERR_STATE on a multi-key context and on a multi-device context

@@ -152,6 +152,8 @@ def test_gpu_random_network_equals_schoolbook(tfhe, N, k, l, beta):
     got2 = eng.cmux_net(data, net, sel, table_index=index, out_form=2)
     assert eng.last_timing_ms(1) > 0 and got2.shape == (B, 2, LWE + 1)
     assert np.array_equal(got2.reshape(B * 2, -1), eng.keyswitch(want_ext.reshape(B * 2, -1))), "out_form 2"
+    from leveled_ref import ks_ref, ks_schoolbook                      # (imported here: leveled_ref imports, through test_rot_net, this module)
+    assert np.array_equal(got2, ks_ref(ks_schoolbook(ck.params, ck.keyswitch_key), want_ext)), "out_form 2 against the integer keyswitch"
     # NULL table index = table 0 for every row
     want0, _ = ref_rows(Tree(N, k, l, beta, tgsw), net, data, [0] * B, sel[:1])
     assert np.array_equal(eng.cmux_net(data, net, sel[:1], out_form=0), want0)

@@ -178,6 +178,8 @@ def test_gpu_cmux_tree_equals_schoolbook(tfhe, N, k, l, beta, depth):
         got2 = eng.cmux_tree(data, sel, table_index=index, out_form=2)
         assert eng.last_timing_ms(1) > 0
         assert np.array_equal(got2, eng.keyswitch(got1)), ("out_form 2", index)
+        from leveled_ref import ks_ref, ks_schoolbook                  # (imported here: leveled_ref imports Tree from this module)
+        assert np.array_equal(got2, ks_ref(ks_schoolbook(ck.params, ck.keyswitch_key), want_ext)), ("out_form 2 against the integer keyswitch", index)
     if depth == 1:                                                  # d0 = 0: the CMUX is the plain external product of d1
         zero = data.copy()
         zero[:, 0] = 0

@@ -45,7 +45,7 @@ class MKTree:
     def __init__(self, orc, N, l, beta, P, tgsw, party_of, ks=None, n=None, t=8, gamma=2):
         self.N, self.l, self.beta, self.P = N, l, beta, P
         gadget, self.offset = orc.tgsw_constants(l, beta)                        # tgsw.jl:8-21
-        assert [int(g) for g in gadget] == [1 << (32 - p * beta) for p in range(1, l + 1)]
+        assert [int(g) & MASK32 for g in gadget] == [(1 << (32 - p * beta)) & MASK32 for p in range(1, l + 1)]      # (as 32-bit words: 2^31 at beta = 1)
         # |digit| <= 2^(beta-1), |key word| <= 2^31, N terms, up to l P + l products summed before the reduction: no int64 overflow
         assert (beta - 1) + 31 + (N.bit_length() - 1) + (l * P + l - 1).bit_length() < 63
         self.tg = np.asarray(tgsw, np.int64).reshape(-1, 2 * l * P + 2 * l, N)

@@ -50,7 +50,8 @@ static int32_t run_levels(tfhe_ctx *c, const char *who, const int32_t *in, int64
     const size_t per_row_in = d0_zero ? 1 : (size_t)1 << depth;
     const size_t nodes0 = (size_t)1 << (depth - 1);                 // output nodes of level 0 per row: the widest level
     const size_t ws_bytes = (size_t)B * nodes0 * sample * 4;        // B 2^(depth-1) TLWE samples per buffer
-    const bool fits = leveled::lds_bytes(N, K1) <= 160 * 1024;
+    const bool in_lds = leveled::lds_bytes(N, K1) <= 160 * 1024;
+    const bool fits = c->anyn_spec < 0 ? in_lds : (c->anyn_spec == 0 && in_lds);      // option anyn_spec, as the network kernels read it: 1 = accumulators in global memory
     const size_t B_ = (size_t)B, Sd = B_ * (size_t)depth;
     auto up = [](size_t words) { return (words + 63) / 64 * 64; };
     const size_t o_idx = up(B_), o_sel = o_idx + up(B_), map_bytes = (o_sel + Sd) * 4;      // e0 [B] | row_index [B] | sel [B][depth]
