@@ -141,18 +141,29 @@ def edge_level(rng, rows, N):
 
 
 # ---- expected words --------------------------------------------------------------------------------------------------------------------
+def coefficient_of(j, N, n_out):
+    """c_j: the accumulator coefficient at which sample j of n_out is extracted (a function of its own so that
+    tests/test_pbs_fuzz.py can replace it by a wrong one and see the expected words move)."""
+    return j * (N // n_out)
+
+
+def table_of(tables, index, g):
+    """Row g's test polynomial: tables[index[g]], table 0 without an index (its own function for the same reason)."""
+    return tables[0 if index is None else index[g]]
+
+
 def expected(sb, tables, index, x, n_outs, mk=False):
     """{(n_out, with_keyswitch): int32 [B][n_out][width]} from one schoolbook rotation per row: bootstrap_tv / mk_bootstrap_tv for every
     n_out at once (the accumulator and the samples at shared coefficients are computed once)."""
     rotate, extract, keyswitch = (sb.mk_rotate, sb.mk_extract_at, sb.mk_keyswitch) if mk else (sb.rotate, sb.extract_at, sb.keyswitch)
     N = sb.N
-    cs = sorted({j * (N // K) for K in n_outs for j in range(K)})
+    cs = sorted({coefficient_of(j, N, K) for K in n_outs for j in range(K)})
     per_row = []
     for g, row in enumerate(x):
-        acc = rotate(tables[0 if index is None else index[g]], row)
+        acc = rotate(table_of(tables, index, g), row)
         ext = {c: extract(acc, c) for c in cs}
         per_row.append((ext, {c: keyswitch(ext[c]) for c in cs}))
-    return {(K, ks): _i32(np.array([[r[ks][j * (N // K)] for j in range(K)] for r in per_row])) for K in n_outs for ks in (False, True)}
+    return {(K, ks): _i32(np.array([[r[ks][coefficient_of(j, N, K)] for j in range(K)] for r in per_row])) for K in n_outs for ks in (False, True)}
 
 
 class _Case:
@@ -569,15 +580,23 @@ def test_gpu_mk_gates_equal_schoolbook(parties):
 DELTA, DELTA_AT = -2**31 + 3, 1                          # v = DELTA X^1
 
 
-@functools.lru_cache(maxsize=None)
-def closed_form(N, n_out):
-    """All 2N body values b 2^s, b in [-N, N), and the un-keyswitched bodies they must give: the mask is zero, so nothing rotates
-    after testvectbis = X^{-barb} v (bootstrap.jl:54) and sample j's body is coefficient j N / n_out of that monomial product."""
-    s = 32 - (2 * N).bit_length() + 1
+@functools.lru_cache(maxsize=4)
+def _delta_rotations(N, exponents):
+    """X^{-e} v for the delta table v and every exponent e of the tuple: int64 [len(exponents)][N], shared by the n_out of one set."""
     v = np.zeros(N, np.int64)
     v[DELTA_AT] = DELTA
-    b = np.arange(-N, N)
-    bodies = np.stack([wrap32(monomial(v, -int(e), N))[[j * (N // n_out) for j in range(n_out)]] for e in b])
+    return v, np.stack([wrap32(monomial(v, -int(e), N)) for e in exponents])
+
+
+@functools.lru_cache(maxsize=None)
+def closed_form(N, n_out, exponents=None):
+    """All 2N body values b 2^s, b in [-N, N) (or the exponents of the tuple `exponents`, for degrees at which 2N rows are too many),
+    and the un-keyswitched bodies they must give: the mask is zero, so nothing rotates after testvectbis = X^{-barb} v
+    (bootstrap.jl:54) and sample j's body is coefficient j N / n_out of that monomial product."""
+    s = 32 - (2 * N).bit_length() + 1
+    b = np.arange(-N, N) if exponents is None else np.array(exponents, np.int64)
+    v, rotated = _delta_rotations(N, tuple(int(e) for e in b))
+    bodies = rotated[:, [j * (N // n_out) for j in range(n_out)]]
     return _i32(v), _i32(b << s), _i32(bodies)
 
 
