@@ -4,110 +4,10 @@
 #define TFHE_EMIT_MK_CMUX_NET_KERNELS
 #include "engine.hpp"
 #include "kernels_mk_cmux_net.hpp"
+#include "leveled_run.hpp"
 #include "leveled_checks.hpp"
 
 static const char *const WHO = "mk_cmux_net_batch";
-
-// One validated call on a device context: engine_cmux_net.hip's run_net on MK samples of (P + 1) polynomials.  Level 0 reads row g's E
-// samples at data[table_index[g]], level v > 0 the widths[v-1] outputs of the level below; the F = widths[levels-1] outputs of the last
-// level are the result.  Workspaces: buffer 0 holds the outputs of the even levels, buffer 1 those of the odd ones, each sized by its
-// own widest level.  Timing events as the gate entry points: levels in slot 0, keyswitch in slot 1.
-static int32_t run_mk_net(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths, int32_t levels,
-                          const int32_t *nodes, size_t total_nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const int N = c->P.N, NP = c->mk_parties, K1 = NP + 1, M = N / 2 > 0 ? N / 2 : 1, n = c->P.n;
-    const size_t sample = (size_t)K1 * N, ext_w = (size_t)NP * N + 1, out_w = (size_t)NP * n + 1;
-    size_t wmax[2] = {0, 0}, wall = 0;                              // the widest even level, the widest odd level, the widest level
-    for (int lv = 0; lv < levels; lv++) {
-        const size_t w = (size_t)widths[lv];
-        if (w > wmax[lv & 1]) wmax[lv & 1] = w;
-        if (w > wall) wall = w;
-    }
-    const size_t B_ = (size_t)B, F = (size_t)widths[levels - 1], G = B_ * F;
-    const bool fits = leveled::mk_lds_bytes(N, true) <= 160 * 1024;
-    const bool spec_lds = c->anyn_spec < 0 ? fits : (c->anyn_spec == 0 && fits);
-    auto up = [](size_t words) { return (words + 63) / 64 * 64; };
-    // e0 [B F] (the keyswitch's identity map) | table_index [B] | sel [B][V] | nodes [total][3]
-    const size_t o_idx = up(G), o_sel = o_idx + up(B_), o_nodes = o_sel + up(B_ * (size_t)V), map_bytes = (o_nodes + 3 * total_nodes) * 4;
-    const size_t data_bytes = (size_t)T * (size_t)E * sample * 4;
-    const LvlWant want[] = {
-        {&c->lvl_data, data_bytes},
-        {&c->lvl_ws[0], B_ * wmax[0] * sample * 4},
-        {&c->lvl_ws[1], B_ * wmax[1] * sample * 4},
-        {&c->lvl_spec, spec_lds ? 0 : B_ * wall * 3 * M * sizeof(cplx)},
-        {&c->ext, out_form >= 1 ? G * ext_w * 4 : 0},
-        {&c->io[3], out_form == 2 ? G * out_w * 4 : 0},
-        {&c->map, map_bytes},
-    };
-    { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }       // (the workspaces may still be in use by a call on another stream)
-    int32_t rc = leveled_reserve(c, WHO, want, (int)(sizeof want / sizeof want[0]));
-    if (rc) return rc;
-
-    rc = ensure_host_map(c, map_bytes);
-    if (rc) return rc;
-    int32_t *h = (int32_t *)c->h_map;
-    for (size_t r = 0; r < G; r++) h[r] = (int32_t)r;
-    if (table_index) memcpy(h + o_idx, table_index, B_ * 4);
-    else memset(h + o_idx, 0, B_ * 4);
-    memcpy(h + o_sel, sel, B_ * (size_t)V * 4);
-    memcpy(h + o_nodes, nodes, 3 * total_nodes * 4);
-    HIP_TRY(c, hipMemcpyAsync(c->map.p, c->h_map, map_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->lvl_data.p, data, data_bytes, hipMemcpyHostToDevice, s));
-    const int32_t *d_map = (const int32_t *)c->map.p;
-
-    leveled::MkNetArgs a;
-    a.sel = d_map + o_sel;
-    a.party_of = c->d_mk_tgsw_party;
-    a.tgsw = c->d_mk_tgsw;
-    a.spec_g = spec_lds ? nullptr : (cplx *)c->lvl_spec.p;
-    a.wtab = c->d_anyn_tab; a.twist = c->d_anyn_tab + N / 2;
-    a.g = c->g;
-    a.parties = NP; a.L = c->P.bs_l; a.log2N = ilog2i(N);
-    a.V = V;
-    const size_t lds = leveled::mk_lds_bytes(N, spec_lds);
-    if (lds > 64 * 1024) LDS_TRY(c, lds, leveled::mk_cmux_net_level_kernel);
-    const unsigned nt = (unsigned)anyn::threads_for(N);
-
-    next_timing_slot(c);
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    const int32_t *final_tlwe = nullptr;
-    size_t first_node = 0;
-    for (int lv = 0; lv < levels; lv++) {
-        const size_t w = (size_t)widths[lv];
-        const bool last = lv == levels - 1;
-        a.in = lv == 0 ? (const int32_t *)c->lvl_data.p : (const int32_t *)c->lvl_ws[(lv - 1) & 1].p;
-        a.row_index = lv == 0 ? d_map + o_idx : nullptr;
-        a.row_words = (int64_t)((lv == 0 ? (size_t)E : (size_t)widths[lv - 1]) * sample);
-        a.nodes = d_map + o_nodes + 3 * first_node;
-        a.nodes_out = (int32_t)w;
-        a.out = last && out_form != 0 ? nullptr : (int32_t *)c->lvl_ws[lv & 1].p;
-        a.ext = last && out_form != 0 ? (int32_t *)c->ext.p : nullptr;
-        if (last) final_tlwe = a.out;
-        hipLaunchKernelGGL(leveled::mk_cmux_net_level_kernel, dim3((unsigned)(B_ * w)), dim3(nt), lds, s, a);
-        HIP_TRY(c, hipGetLastError());
-        first_node += w;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    if (out_form == 2) {
-        rc = launch_keyswitch(c, G, d_map, nullptr, nullptr, (const int32_t *)c->ext.p, (int32_t *)c->io[3].p, s);
-        if (rc) return rc;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[3], s));
-    if (out_form == 0) HIP_TRY(c, hipMemcpyAsync(out, final_tlwe, G * sample * 4, hipMemcpyDeviceToHost, s));
-    else if (out_form == 1) HIP_TRY(c, hipMemcpyAsync(out, c->ext.p, G * ext_w * 4, hipMemcpyDeviceToHost, s));
-    else HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, G * out_w * 4, hipMemcpyDeviceToHost, s));
-    rc = leave_stream(c, s);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    commit_timing_slot(c);
-    c->last_rotations = 0;
-    c->diag_rows = 0;
-    name_kernel(c, spec_lds ? "mk_cmux_net_level_kernel(N=%d,P=%d,l=%d)" : "mk_cmux_net_level_kernel(N=%d,P=%d,l=%d,spec=global)", N, NP, c->P.bs_l);
-    return TFHE_OK;
-}
 
 int32_t tfhe_mk_cmux_net_batch(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths, int32_t levels,
                                const int32_t *nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form) try
@@ -130,6 +30,15 @@ int32_t tfhe_mk_cmux_net_batch(tfhe_ctx *c, const int32_t *data, int64_t T, int3
     rc = net_check_rows(c, WHO, sel, V, B, c->mk_tgsw_count, table_index, T);
     if (rc) return rc;
     if (B == 0) return TFHE_OK;
-    return run_mk_net(c, data, T, E, table_index, widths, levels, nodes, total_nodes, sel, V, out, B, out_form);
+    LevelPlan p = {data, T, E, table_index, false, sel, V, widths, levels, "the widest level", nodes, 3};
+    plan_multi_key(p, c, "mk_cmux_net_level_kernel");
+    p.B = B, p.out = out, p.out_form = out_form;
+    return run_leveled<leveled::MkNetArgs, leveled::mk_cmux_net_level_kernel>(c, WHO, p, [&](leveled::MkNetArgs &a, int, const int32_t *d_nodes) {
+        a.tgsw = c->d_mk_tgsw;
+        a.nodes = d_nodes;
+        a.party_of = c->d_mk_tgsw_party;
+        a.parties = c->mk_parties;
+        a.V = V;
+    });
 }
 ABI_CATCH(c, "tfhe_mk_cmux_net_batch")

@@ -5,131 +5,32 @@
 // one external product per node that has two different sources.  A node with src0 == src1 is a copy: no product, no noise, and
 // word for word what the formula gives (the product of the zero difference is exactly zero).
 //
-// The arithmetic is cmux_level_kernel's, statement for statement: the same any-N blocks, the same accumulation order (c outer, p
-// inner, the first product initialises), the same rounding — a tree-shaped network equals tfhe_cmux_tree_batch in every word.
-// Workgroup barriers only; every loop is bounded by a parameter; inputs are read-only and the outputs go to the other buffer.
+// The arithmetic is cmux_level_kernel's because it is the same function, leveled::cmux (kernels_leveled_core.hpp): a tree-shaped
+// network equals tfhe_cmux_tree_batch in every word.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include "br_core.hpp"
-#include "kernels_anyn.hpp"
-
-using namespace tfhe;
+#include "kernels_leveled_core.hpp"
 
 namespace leveled {
 
-struct NetArgs {
-    const int32_t *in;        // the level's input samples: row r's nodes at in + r * row_words, node m at + m * K1 * N
-    const int32_t *row_index; // [B] row g reads input row row_index[g] (level 0: its table), or NULL: row g
-    const int32_t *nodes;     // [nodes_out][3] this level's records (src0, src1, var), checked by the host
-    const int32_t *sel;       // [B][V] the selector behind each of row g's variables, checked by the host
-    const cplx *tgsw;         // [S][L][K1][K1][M] selector spectra, fft_fwd's order, scaled 1/M
-    int32_t *out;             // [B][nodes_out][K1][N] the level's output samples, or NULL when only `ext` is wanted
-    int32_t *ext;             // [B][nodes_out][(K1-1) N + 1] every output extracted at coefficient 0 (tlwe.jl:55-59), or NULL
-    cplx *spec_g;             // [workgroups][K1][M] spectrum accumulators when they are not in LDS, else NULL
-    const cplx *wtab;         // [M]  e^{-2 pi i t / M}
-    const cplx *twist;        // [M]  e^{-i pi j / N}
-    Gadget g;
-    int64_t row_words;        // words between two input rows
-    int32_t K1, L, log2N;
+struct NetArgs : LevelArgs {
+    const int32_t *nodes;     // [nodes_out][3] this level's records (src0, src1, var), checked by the host; with monomial edges
+                              // (RotNetArgs) [nodes_out][5]: (src0, src1, var, rot0, rot1)
+    int32_t K1;
     int32_t V;                // sel's row length
-    int32_t nodes_out;        // output nodes per row
 };
 
 #ifdef TFHE_EMIT_CMUX_NET_KERNELS      // (defined by engine_cmux_net.hip, the one translation unit that launches it)
-// one pair of output words (coefficients j and j + M of polynomial co) to the sample and / or its extraction at coefficient 0:
-// tlwe_extract_sample (tlwe.jl:55-59): a'[0] = p[0], a'[m] = -p[N - m], mask polynomials in order; b = body[0]
-__device__ __forceinline__ void net_store(int32_t *out, int32_t *ext, int co, int j, int32_t lo, int32_t hi, int K1, int N, int M)
-{
-    const size_t e = (size_t)co * N + j;
-    if (out) { out[e] = lo; out[e + M] = hi; }
-    if (ext) {
-        if (co + 1 < K1) {
-            int32_t *a = ext + (size_t)co * N;
-            if (j == 0) a[0] = lo; else a[N - j] = (int32_t)(0u - (uint32_t)lo);
-            a[N - (j + M)] = (int32_t)(0u - (uint32_t)hi);
-        } else if (j == 0) {
-            ext[(size_t)(K1 - 1) * N] = lo;
-        }
-    }
-}
-
-// blockIdx.x = g * nodes_out + i: the workgroups of a row sit together and share its selector spectra in L2
 __global__ __launch_bounds__(512) void cmux_net_level_kernel(NetArgs P)
 {
-    using namespace anyn;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int N = 1 << P.log2N, M = N >> 1, log2M = P.log2N - 1, Mp = padded_len(M);
-    const int K1 = P.K1, L = P.L;
-    const bool spec_lds = P.spec_g == nullptr;
-    cplx *buf = reinterpret_cast<cplx *>(smem);
-    cplx *spec = spec_lds ? buf + Mp : P.spec_g + (size_t)blockIdx.x * K1 * M;
-    const int spec_stride = spec_lds ? Mp : M;
-    int32_t *tmp = reinterpret_cast<int32_t *>(buf + (size_t)(spec_lds ? 1 + K1 : 1) * Mp);
-    const size_t g = blockIdx.x / (unsigned)P.nodes_out, i = blockIdx.x % (unsigned)P.nodes_out;
-    const size_t sample = (size_t)K1 * N;
-    const int32_t *rec = P.nodes + 3 * i;
+    const Frame f = frame(P, smem, P.K1);
+    const size_t sample = (size_t)P.K1 * f.N;
+    const int32_t *rec = P.nodes + 3 * f.i;
     const int32_t src0 = rec[0], src1 = rec[1], var = rec[2];
-    const int32_t *row = P.in + (size_t)(P.row_index ? P.row_index[g] : (int64_t)g) * (size_t)P.row_words;
-    const int32_t *d0 = row + (size_t)src0 * sample;
-    const int32_t *d1 = row + (size_t)src1 * sample;
-    int32_t *out = P.out ? P.out + (size_t)blockIdx.x * sample : nullptr;
-    int32_t *ext = P.ext ? P.ext + (size_t)blockIdx.x * ((size_t)(K1 - 1) * N + 1) : nullptr;
-
-    if (src0 == src1) {       // a copy node (uniform over the workgroup: the record depends on blockIdx alone)
-#pragma unroll 1
-        for (int co = 0; co < K1; co++)
-            for (int j = tid; j < M; j += nt) net_store(out, ext, co, j, d0[(size_t)co * N + j], d0[(size_t)co * N + j + M], K1, N, M);
-        return;
-    }
-
-    const cplx *key = P.tgsw + (size_t)P.sel[g * (size_t)P.V + var] * ((size_t)L * K1 * K1 * M);
-    const int beta = P.g.log2_base;
-    const int32_t xormask = gadget_xor_mask(L, beta);
-
-#pragma unroll 1
-    for (int c = 0; c < K1; c++) {
-        // tmp = ((d1 - d0)[c] + offset) ^ xormask: digit2 then reads the signed digits of tgsw.jl:99-117
-        for (int j = tid; j < N; j += nt) {
-            const uint32_t v = (uint32_t)d1[(size_t)c * N + j] - (uint32_t)d0[(size_t)c * N + j];
-            tmp[j] = (int32_t)((v + (uint32_t)P.g.offset) ^ (uint32_t)xormask);
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int p = 0; p < L; p++) {
-            digits_to_buf(tmp, p + 1, beta, M, P.twist, buf, tid, nt);
-            __syncthreads();
-            fft_fwd(buf, P.wtab, log2M, tid, nt);
-            // out[co] += D[p, c] .* C[p, c].a[co]        tgsw.jl:128
-#pragma unroll 1
-            for (int co = 0; co < K1; co++)
-                mac(buf, key + (size_t)((p * K1 + c) * K1 + co) * M, spec + (size_t)co * spec_stride, spec_lds, c == 0 && p == 0, M, tid, nt);
-            __syncthreads();
-        }
-    }
-
-#pragma unroll 1
-    for (int co = 0; co < K1; co++) {
-        cplx *y = spec + (size_t)co * spec_stride;
-        if (!spec_lds) {
-            for (int f = tid; f < M; f += nt) buf[phys(f)] = y[f];
-            __syncthreads();
-            y = buf;
-        }
-        fft_inv(y, P.wtab, log2M, tid, nt);
-        // conj(y_j) e^{-i pi j/N}: real -> coefficient j, imaginary -> j + M (polynomials.jl:127-129), rounded
-        // (polynomials.jl:115-116), plus d0 (bootstrap.jl:22)
-        for (int j = tid; j < M; j += nt) {
-            const cplx v = y[phys(j)], w = P.twist[j];
-            const double re = v.x * w.x + v.y * w.y, im = v.x * w.y - v.y * w.x;
-            const size_t e = (size_t)co * N + j;
-            const int32_t lo = (int32_t)((uint32_t)d0[e] + (uint32_t)round_to_torus32(re));
-            const int32_t hi = (int32_t)((uint32_t)d0[e + M] + (uint32_t)round_to_torus32(im));
-            net_store(out, ext, co, j, lo, hi, K1, N, M);
-        }
-        __syncthreads();
-    }
+    const Src<SRC_PLAIN> d0{f.row + (size_t)src0 * sample, 0}, d1{f.row + (size_t)src1 * sample, 0};
+    int32_t *out = node_out(P.out, sample), *ext = node_out(P.ext, (size_t)(P.K1 - 1) * f.N + 1);
+    if (src0 == src1) return copy_node(f, d0, P.K1 - 1, out, ext);
+    cmux(f, P.g, P.tgsw, P.sel[f.g * (size_t)P.V + var], d1, d0, P.K1, out, ext);
 }
 #endif  // TFHE_EMIT_CMUX_NET_KERNELS
 

@@ -6,6 +6,15 @@
 
 enum { NET_MAX_LEVELS = 1024, NET_MAX_WIDTH = 4096 };
 
+// what the single-key leveled entry points refuse before they look at their arguments
+inline int32_t leveled_state(tfhe_ctx *c, const char *who)
+{
+    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "%s: context is multi-key (leveled operations are single-key)", who);
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "%s: multi-device context (leveled operations run on a one-device context)", who);
+    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the CMUX level kernel has no DIAG instantiation)", who);
+    return TFHE_OK;
+}
+
 // what the multi-key leveled entry points refuse before they look at their arguments
 inline int32_t mk_leveled_state(tfhe_ctx *c, const char *who)
 {
@@ -71,7 +80,7 @@ inline int32_t rot_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_
     return net_check_records(c, who, T, E, widths, levels, nodes, V, B, out_form, total_nodes, 5, 2 * N);
 }
 
-// The per-row part, O(B V): every selector against the `selectors` loaded ones, every table index against T.
+// The per-row part, O(B V): every selector against the `selectors` loaded ones, every table index against T (a CMUX tree: V = depth).
 inline int32_t net_check_rows(tfhe_ctx *c, const char *who, const int32_t *sel, int32_t V, int64_t B, int64_t selectors, const int32_t *table_index, int64_t T)
 {
     for (int64_t g = 0; g < B; g++)
