@@ -536,6 +536,27 @@ int32_t tfhe_mk_cmux_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, in
                                const int32_t *widths, int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V,
                                int32_t *out, int64_t B, int32_t out_form);
 
+/* CMUX network with a public monomial on every edge, on multi-key samples (addition within ABI v7): tfhe_mk_cmux_net_batch's contract
+ * with tfhe_rot_net_batch's one difference, a node record of five words, nodes: host int32 [sum widths][5] = (src0, src1, var, rot0,
+ * rot1).  Node i of level v of row g is
+ *     X^rot0 in[src0] + selector[sel[g][var]] (.) (X^rot1 in[src1] - X^rot0 in[src0])
+ * with mk_tgsw_extern_mul for the party of that selector and X^r p = mul_by_monomial(p, r) on all P + 1 polynomials of the MK TLWE
+ * sample; rot0, rot1 are public, in [0, 2N).  src0 == src1 with rot0 == rot1 is a rotated copy (no product, no noise, the exact words
+ * of X^rot0 in[src0]); src0 == src1 with rot0 != rot1 is a true product.  A table packed N entries to an MK TLWE sample is read at an
+ * address whose bits several parties own at 2^(d - log2 N) - 1 + log2 N multi-key external products instead of 2^d - 1, and a
+ * 2^16-entry table, beyond tfhe_mk_cmux_tree_batch's depth 12, at 63 + 10 products under N = 1024; a one-state automaton with weights
+ * 0 and 2N - 1 returns f(popcount) of bits from several parties.  With every rotation 0 the call equals tfhe_mk_cmux_net_batch word
+ * for word.
+ * Everything else is tfhe_mk_cmux_net_batch's: data, table_index, sel, the limits, the three out_forms (extraction at coefficient 0),
+ * the workspaces and TFHE_ERR_NOMEM before any allocation, B = 0, the timing slots, and the order of the refusals, with
+ * TFHE_ERR_INVALID_ARG also for a rotation outside [0, 2N), the message naming node, level and field (rot0 / rot1), before anything
+ * is uploaded.  One launch per level (csrc/kernels_mk_rot_net.hpp; tfhe_last_kernel_name reports
+ * "mk_rot_net_level_kernel(N=..,P=..,l=..[,spec=global])"; the option "anyn_spec" is honoured).  A single-key context is refused with
+ * TFHE_ERR_STATE, as a multi-key context is by tfhe_rot_net_batch. */
+int32_t tfhe_mk_rot_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index,
+                              const int32_t *widths, int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V,
+                              int32_t *out, int64_t B, int32_t out_form);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Timing of the most recent batch call on ctx, from HIP events recorded on the stream the kernels

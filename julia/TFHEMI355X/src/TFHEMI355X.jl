@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -915,6 +915,46 @@ function mk_cmux_net(mck::GpuMKCloudKey, data::Array{Int32,4}, widths, nodes::Ab
     out = out_form == 0 ? Array{Int32}(undef, N, P + 1, F, B) : Array{Int32}(undef, width + 1, F * B)
     B == 0 && return out_form == 2 ? MKLweSample[] : out
     GC.@preserve data w nd s idx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_cmux_net_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Int64, Int32),
+        mck.ctx, data, Int64(size(data, 4)), Int32(E), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), w, Int32(levels), nd, s, Int32(V), out,
+        Int64(B), Int32(out_form)))
+    out_form == 2 || return out
+    params = LweParams(n)
+    [MKLweSample(params, reshape(out[1:n*P, r], n, P), out[n * P + 1, r], 0.) for r in 1:F*B]
+end
+
+"""
+    mk_rot_net(mck, data::Array{Int32,4}, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_index=nothing; out_form=2)
+
+CMUX network with a public monomial on every edge, on multi-key samples (tfhe_mk_rot_net_batch): `mk_cmux_net` with `nodes`
+`5 x sum(widths)`, column `(src0, src1, var, rot0, rot1)`; the node is `X^rot0 in[src0] + C_var ⊡ (X^rot1 in[src1] - X^rot0 in[src0])` with
+`X^r` the reference's `mul_by_monomial` on all `P + 1` polynomials and the product for the party of selector `var`.  Sources and `var` are
+1-based as in `mk_cmux_net`; the rotations are exponents in `0:2N-1` and pass unchanged.  The nodes `(1, 1, b + 1, 0, 2N - 2^b)` for
+`b = 0 ... log2(N) - 1` read a table packed `N` entries to an MK TLWE sample at an address whose bits several parties own.  `data`,
+`sel`, `table_index` and the results are `mk_cmux_net`'s.
+"""
+function mk_rot_net(mck::GpuMKCloudKey, data::Array{Int32,4}, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_index=nothing; out_form::Integer=2)
+    p, P = mck.params, mck.parties
+    N, n = p.tlwe_polynomial_degree, p.lwe_size
+    w = Int32.(collect(widths))
+    levels = length(w)
+    1 <= levels <= 1024 || error("tfhe_mi355x: levels = ", levels, " (1 ... 1024)")
+    all(x -> 1 <= x <= 4096, w) || error("tfhe_mi355x: every width must be 1 ... 4096")
+    size(nodes) == (5, sum(w)) || error("tfhe_mi355x: nodes must be 5 x sum(widths)")
+    all(r -> 0 <= r < 2N, view(nodes, 4:5, :)) || error("tfhe_mi355x: every rotation must be 0 ... 2N - 1")
+    E = size(data, 3)
+    size(data)[1:2] == (N, P + 1) && E >= 1 && size(data, 4) >= 1 || error("tfhe_mi355x: tables must be N x (P+1) x E x T")
+    V, B = size(sel)
+    V >= 1 || error("tfhe_mi355x: sel must be V x B with V >= 1")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    nd = Matrix{Int32}(vcat(nodes[1:3, :] .- 1, nodes[4:5, :]))
+    s = Matrix{Int32}(sel .- 1)
+    idx = table_index === nothing ? nothing : Int32.(collect(table_index) .- 1)
+    F = Int(w[end])
+    width = out_form == 2 ? P * n : P * N
+    out = out_form == 0 ? Array{Int32}(undef, N, P + 1, F, B) : Array{Int32}(undef, width + 1, F * B)
+    B == 0 && return out_form == 2 ? MKLweSample[] : out
+    GC.@preserve data w nd s idx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_rot_net_batch, LIB), Int32,
         (Ptr{Cvoid}, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Int64, Int32),
         mck.ctx, data, Int64(size(data, 4)), Int32(E), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), w, Int32(levels), nd, s, Int32(V), out,
         Int64(B), Int32(out_form)))

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "tfhe_mk_bootstrap_tv_batch", "tfhe_mk_bootstrap_tv_multi_batch", "tfhe_mk_lut_level", "tfhe_mk_linear_level",
     "tfhe_tgsw_load", "tfhe_extern_mul_batch", "tfhe_cmux_tree_batch", "tfhe_cmux_net_batch",
     "tfhe_mk_tgsw_load", "tfhe_mk_tgsw_expand_load", "tfhe_mk_extern_mul_batch", "tfhe_mk_cmux_tree_batch",
-    "tfhe_mk_cmux_net_batch", "tfhe_rot_net_batch",
+    "tfhe_mk_cmux_net_batch", "tfhe_rot_net_batch", "tfhe_mk_rot_net_batch",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -163,6 +163,8 @@ def load():
         lib.tfhe_mk_cmux_net_batch.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, i32]
     if hasattr(lib, "tfhe_rot_net_batch"):
         lib.tfhe_rot_net_batch.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, i32]
+    if hasattr(lib, "tfhe_mk_rot_net_batch"):
+        lib.tfhe_mk_rot_net_batch.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, i32]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -603,6 +605,22 @@ class Engine:
         out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
         self._check(self._lib.tfhe_mk_cmux_net_batch(self._h, _ptr(d), d.shape[0], d.shape[1], _ptr(idx), _ptr(net.widths), net.levels, _ptr(net.nodes),
                                                      _ptr(sel), V, _ptr(out), B, int(out_form)))
+        return out
+
+    def mk_rot_net(self, data, net, sel, table_index=None, out_form=2):
+        """CMUX network with monomial edges on multi-key samples (tfhe_mk_rot_net_batch): mk_cmux_net with net a leveled.RotNet, whose
+        records carry a public rotation X^rot for each source, applied to all P + 1 polynomials; shapes and out_forms as mk_cmux_net
+        (extraction at coefficient 0: a packed lookup rotates the wanted coefficient there)."""
+        P = self._mk_width("mk_rot_net")
+        if getattr(net, "degree", None) != self.N:
+            raise ValueError(f"the network's rotations are taken mod 2 * {getattr(net, 'degree', None)}, the engine's polynomials have {self.N} coefficients")
+        d, sel, idx = self._net_args(data, net, sel, table_index, P + 1)
+        B, V = sel.shape
+        F = int(net.widths[-1])
+        shape = {0: (B, F, P + 1, self.N), 1: (B, F, P * self.N + 1), 2: (B, F, P * self.n + 1)}.get(int(out_form), (0,))
+        out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
+        self._check(self._lib.tfhe_mk_rot_net_batch(self._h, _ptr(d), d.shape[0], d.shape[1], _ptr(idx), _ptr(net.widths), net.levels, _ptr(net.nodes),
+                                                    _ptr(sel), V, _ptr(out), B, int(out_form)))
         return out
 
     # ---- levelised circuits on the device-resident wire table ----

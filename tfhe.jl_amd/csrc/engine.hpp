@@ -17,9 +17,10 @@
 //   engine_cmux_net.hip   leveled mode: CMUX networks (automata, decision diagrams) wired by a public netlist          ("cmux net")
 //   engine_mk_cmux_net.hip  the same networks under a multi-key cloud key                                              ("mk cmux net")
 //   engine_rot_net.hip    leveled mode: CMUX networks with a monomial X^rot on every edge (packed tables, weighted automata)  ("rot net")
+//   engine_mk_rot_net.hip   the same networks with monomial edges under a multi-key cloud key                          ("mk rot net")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
-//   leveled_run.hpp       host-only: the one runner behind the ten leveled entry points (workspaces, uploads, level loop, download)
-//   kernels_leveled_core.hpp  device-only: the CMUX level body the five level kernels share
+//   leveled_run.hpp       host-only: the one runner behind the eleven leveled entry points (workspaces, uploads, level loop, download)
+//   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
 // only under the TFHE_EMIT_* macro of the unit that launches them (templates are instantiated where they are launched).

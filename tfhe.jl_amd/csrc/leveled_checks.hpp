@@ -1,6 +1,7 @@
 // leveled_checks.hpp — host-only checks that more than one leveled unit makes before anything is uploaded: the state a multi-key
-// leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip) and the netlist of a CMUX network (engine_cmux_net.hip,
-// engine_mk_cmux_net.hip; with monomial edges: engine_rot_net.hip).  Every function sets the context's error message, naming the caller `who`, and returns its code.
+// leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip) and the netlist of a CMUX network
+// (engine_cmux_net.hip, engine_mk_cmux_net.hip; with monomial edges: engine_rot_net.hip, engine_mk_rot_net.hip).  Every function sets
+// the context's error message, naming the caller `who`, and returns its code.
 #pragma once
 #include "engine.hpp"
 
@@ -73,7 +74,7 @@ inline int32_t net_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_
     return net_check_records(c, who, T, E, widths, levels, nodes, V, B, out_form, total_nodes, 3, 0);
 }
 
-// the netlist of tfhe_rot_net_batch: records (src0, src1, var, rot0, rot1), the rotations public exponents of X in [0, 2N)
+// the netlist of tfhe_rot_net_batch / tfhe_mk_rot_net_batch: records (src0, src1, var, rot0, rot1), the rotations public exponents of X in [0, 2N)
 inline int32_t rot_check_netlist(tfhe_ctx *c, const char *who, int64_t T, int32_t E, const int32_t *widths, int32_t levels, const int32_t *nodes,
                                  int32_t V, int32_t N, int64_t B, int32_t out_form, size_t *total_nodes)
 {

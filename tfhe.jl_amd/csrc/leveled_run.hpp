@@ -1,5 +1,5 @@
 // leveled_run.hpp — host-only: the one runner behind the leveled entry points (engine_leveled.hip, engine_mk_leveled.hip,
-// engine_cmux_net.hip, engine_rot_net.hip, engine_mk_cmux_net.hip).  An entry point validates its arguments, describes the call in a
+// engine_cmux_net.hip, engine_rot_net.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip).  An entry point validates its arguments, describes the call in a
 // LevelPlan and names its kernel; the workspace protocol, the uploads, the level loop, the keyswitch, the download and the timing are
 // here and nowhere else.
 #pragma once

@@ -29,7 +29,10 @@ A network with monomial edges (RotNet; Engine.rot_net, tfhe_rot_net_batch; rot_n
 X^rot (mul_by_monomial, bootstrap.jl:21, :54).  CMUX(C_b; acc, X^(-2^b) acc) for the low address bits b is the blind rotation by TGSW
 bits: a table packed N entries to a sample (pack_table_to_tlwe, "vertical packing") is read at 2^(d - log2 N) - 1 + log2 N external
 products instead of 2^d - 1 (packed_lookup_net, packed_lookup), and an automaton with X^weight on its transitions (wfa_net) returns
-X^(sum of weights) table[end state]: f(popcount(x)) of up to N - 1 encrypted bits is one state and one product per bit.
+X^(sum of weights) table[end state]: f(popcount(x)) of up to N - 1 encrypted bits is one state and one product per bit.  Entries of
+w bits are packed N / w to a sample and leave as w outputs of one address walk (pack_words_to_tlwe, packed_words_net).  The same
+networks run on jointly encrypted variables under a multi-key cloud key (Engine.mk_rot_net, tfhe_mk_rot_net_batch; mk_rot_net_lookup,
+mk_packed_lookup): a table packed N entries to an MK TLWE sample is read at an address whose bits several parties own.
 """
 import numpy as np
 
@@ -348,6 +351,49 @@ def packed_lookup_net(depth, N):
     return RotNet(widths, nodes, N, entries=1 << (depth - r), variables=depth)
 
 
+def _word_packing(count, word_bits, N):
+    """depth, log2 w and r = min(depth, log2 N - log2 w) of a table of `count` = 2^depth entries of w = word_bits bits each."""
+    w, logN = int(word_bits), int(N).bit_length() - 1
+    if N < 2 or N != 1 << logN:
+        raise ValueError(f"N = {N} (a power of two, at least 2)")
+    if w < 1 or w & (w - 1) or w > N:
+        raise ValueError(f"word_bits = {word_bits} (a power of two, at most N = {N})")
+    depth = int(count).bit_length() - 1
+    if count < 2 or count != 1 << depth:
+        raise ValueError(f"a packed table has 2^depth entries (depth >= 1), got {count}")
+    return depth, w, min(depth, logN - (w.bit_length() - 1))
+
+
+def pack_words_to_tlwe(values, word_bits, N, k=1, encode=encode_gate_bit):
+    """A table of 2^depth words of w = word_bits bits packed 2^r = min(2^depth, N / w) words to a trivial sample, int32
+    [2^(depth-r)][k+1][N]: bit t of entry i is encode(values[i] >> t & 1) on coefficient w (i mod 2^r) + t of sample i >> r;
+    coefficients past w 2^r are zero.  packed_words_net reads it; with w = 1 it is pack_table_to_tlwe of the entries' lowest bits."""
+    depth, w, r = _word_packing(len(values), word_bits, N)
+    bits = np.array([[int(encode((int(v) >> t) & 1)) for t in range(w)] for v in values], np.int64)
+    mu = np.zeros((1 << (depth - r), N), np.int32)
+    mu[:, :w << r] = wrap32(bits).reshape(-1, w << r)
+    return tlwe_trivial(mu, k)
+
+
+def packed_words_net(depth, word_bits, N):
+    """The network that reads a pack_words_to_tlwe table of 2^depth words of w = word_bits bits at an address of `depth` variables: with
+    r = min(depth, log2 N - log2 w), tree levels on the address bits r ... depth-1, then for b = 0 ... r-1 the node
+    (0, 0, b, 0, 2N - w 2^b): the word arrives on coefficients 0 ... w-1.  For w > 1 one last level of w rotated copies of node 0 by
+    X^(-t) puts bit t on coefficient 0 of output t: F = w outputs for one address walk, and the copies add no product and no noise.
+    With w = 1 it is packed_lookup_net(depth, N), record for record."""
+    depth = int(depth)
+    _, w, r = _word_packing(1 << max(depth, 1), word_bits, N)
+    if not 1 <= depth <= 24 or depth - r > 12:
+        raise ValueError(f"depth = {depth} (1 ... 24, and at most 4096 table samples: depth <= {r + 12} at N = {N}, word_bits = {w})")
+    widths = [1 << (depth - r - 1 - t) for t in range(depth - r)] + [1] * r
+    nodes = [(2 * i, 2 * i + 1, r + t, 0, 0) for t in range(depth - r) for i in range(widths[t])]
+    nodes += [(0, 0, b, 0, 2 * N - (w << b)) for b in range(r)]
+    if w > 1:
+        widths.append(w)
+        nodes += [(0, 0, 0, (2 * N - t) % (2 * N), (2 * N - t) % (2 * N)) for t in range(w)]
+    return RotNet(widths, nodes, N, entries=1 << (depth - r), variables=depth)
+
+
 def wfa_net(delta0, delta1, weight0, weight1, start, steps, N, letter_var=None):
     """dfa_net with X^weight on every transition: state q moves to delta0[q] and multiplies by X^weight0[q] on letter 0, to delta1[q]
     and X^weight1[q] on letter 1 (weights taken mod 2N).  The one output is X^(sum of the weights along the path) table[end state].  A
@@ -497,3 +543,31 @@ def mk_cmux_net_lookup(ck, data, net, uni_bits, party_of, out_form=2, expand="de
     eng, sel = _mk_load_selectors(ck, uni_bits, party_of, expand, device, "V")
     out = eng.mk_cmux_net(data, net, sel, table_index=table_index, out_form=out_form)
     return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
+
+
+def mk_rot_net_lookup(ck, data, net, uni_bits, party_of, out_form=2, expand="device", device=0, table_index=None):
+    """mk_cmux_net_lookup for a RotNet (Engine.mk_rot_net, tfhe_mk_rot_net_batch): the network `net` on B rows of jointly encrypted
+    variables.  data: int32 [E][P+1][N] or [T][E][P+1][N] with table_index [B]; uni_bits, party_of, expand and out_form as
+    mk_cmux_net_lookup (extraction at coefficient 0)."""
+    eng, sel = _mk_load_selectors(ck, uni_bits, party_of, expand, device, "V")
+    out = eng.mk_rot_net(data, net, sel, table_index=table_index, out_form=out_form)
+    return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
+
+
+def mk_packed_lookup(ck, table, uni_bits, party_of, out_form=2, expand="device", device=0, encode=encode_gate_bit):
+    """table[address] for B jointly encrypted addresses through a packed table: mk_cmux_lookup at 2^(d - log2 N) - 1 + log2 N external
+    products per address.  table: 2^d plain values (packed here by pack_table_to_tlwe(values, N, k=P) as trivial samples) or the packed
+    MK TLWE samples themselves, int32 [2^(d-r)][P+1][N]; uni_bits: the six arrays of mk_tgsw_uni_encrypt_bits, each [B][d][l][N], bit v
+    of address g uni-encrypted by party party_of[g][v].  out_form 2 (default): multi-key LWE samples int32 [B][P*n+1] for mk_decrypt /
+    mk_gate_*; 1: extracted [B][P*N+1]; 0: the MK TLWE samples [B][P+1][N], the entry on coefficient 0."""
+    shape = np.shape(uni_bits[0]) if len(uni_bits) == 6 else ()
+    if len(shape) != 4:
+        raise ValueError("uni_bits must be six arrays [B][depth][l][N]")
+    depth, N = shape[1], shape[3]
+    t = np.asarray(table)
+    data = pack_table_to_tlwe(list(t), N, ck.parties, encode) if t.ndim == 1 else t
+    net = packed_lookup_net(depth, N)
+    if data.shape[0] != net.entries:
+        raise ValueError(f"a packed table of 2^{depth} entries has {net.entries} samples, got {data.shape[0]}")
+    out = mk_rot_net_lookup(ck, data, net, uni_bits, party_of, out_form=out_form, expand=expand, device=device)
+    return out if out_form == 2 else out[:, 0]
