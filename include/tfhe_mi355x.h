@@ -478,6 +478,39 @@ int32_t tfhe_cmux_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32
 int32_t tfhe_rot_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index, const int32_t *widths,
                            int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V, int32_t *out, int64_t B, int32_t out_form);
 
+/* Blind rotation of the caller's TLWE accumulators (addition within ABI v7): blind_rotate (bootstrap.jl:26-41) on an accumulator the
+ * caller supplies, returning the accumulator the caller asks for — the way from the bootstrapped half (gates, lookups: LWE samples) to
+ * the leveled one.  For row g
+ *     A_0 = X^(-barb_g) acc[acc_index[g]]                            on all k + 1 polynomials, the mask included
+ *     A_(i+1) = A_i + selector[sel[i]] (.) (X^(e_g,i) A_i - A_i)     i = 0 ... steps - 1        (bootstrap.jl:19-23, :32-39)
+ * with the selectors of tfhe_tgsw_load: an entry of the bootstrapping key in canonical form is a TGSW selector, so loading the key's n
+ * entries (and address-bit selectors in the same set, if wanted) makes this the bootstrap's rotation, whichever kernel family serves
+ * the gates.  With an encrypted test polynomial as acc the server evaluates a lookup table it cannot read; with the output of a CMUX
+ * tree (out_form 0 there) as acc, a table of p 2^d entries is addressed in part by an LWE digit computed by gates; with out_form 0
+ * here, a bootstrap's result leaves as a TLWE sample that tfhe_cmux_tree_batch / tfhe_cmux_net_batch accept as `data`.
+ * acc: host int32 [T][k+1][N], TLWE samples, trivial or encrypted; acc_index: host int32 [B] in [0, T), or NULL = accumulator 0 for
+ * every row.  rows: host int32 [B][steps+1], mask words then body; in_form 0: LWE samples under the key whose bits the selectors
+ * encrypt, switched to Z_2N in the kernel (bootstrap.jl:74-75); in_form 1: the exponents themselves, every word in [0, 2N).  A zero
+ * exponent adds exactly zero.  sel: host int32 [steps] in [0, S), shared by all rows, or NULL = selector i for step i.  steps: 1 ...
+ * 65536.  out_form 0: the final accumulator, out int32 [B][k+1][N] (n_out must be 1); 1: for j < n_out its extraction at coefficient
+ * j N / n_out (tfhe_bootstrap_tv_multi_batch's rule), [B][n_out][k*N+1]; 2: those keyswitched, [B][n_out][n+1].  n_out: a power of
+ * two <= 32, and 1 or <= N / 4.  With acc = (0, tv), in_form 0, sel NULL and the bootstrapping key as selectors the call equals
+ * tfhe_bootstrap_tv_multi_batch word for word; with B = 1 and out_form 0 it equals the tfhe_rot_net_batch chain "rotated copy by
+ * 2N - barb, then `steps` levels of width 1 with records (0, 0, i, 0, e_i)" word for word, in one launch instead of steps + 1.
+ * Noise: the accumulator's own noise passes through unrefreshed, and the rotation adds what a bootstrap's rotation adds.
+ * One kernel, one workgroup per row (csrc/kernels_blind_rotate_tlwe.hpp; tfhe_last_kernel_name reports
+ * "tlwe_rotate_kernel(N=..,k=..,l=..,steps=..[,spec=global])"; the option "anyn_spec" is honoured); tfhe_last_rotation_count = B;
+ * tfhe_last_timing_ms: 0 = the rotation, 1 = the keyswitch, 2 = both.  Everything is validated on the host before anything is uploaded
+ * — TFHE_ERR_INVALID_ARG: NULL buffer, B < 0, steps / in_form / out_form / T / n_out out of range, n_out != 1 with out_form 0, a
+ * selector or accumulator index out of range, sel NULL with fewer than `steps` selectors loaded, with in_form 1 a word outside
+ * [0, 2N) (the message names row and column); TFHE_ERR_NO_KEY: no selector set, or out_form 2 without the keyswitch key;
+ * TFHE_ERR_STATE: a multi-key context, a multi-device context, measure_margin on.  The workspaces (the T accumulators, two samples
+ * per row, the rows, the extractions) are compared with the device's free memory BEFORE anything is allocated: TFHE_ERR_NOMEM, the
+ * context stays usable.  B = 0 returns TFHE_OK.  Out of scope: the multi-key form, and forms on the tuned rotation families' key
+ * layouts (the call reads the selector set alone). */
+int32_t tfhe_blind_rotate_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t steps,
+                                int32_t in_form, const int32_t *sel, int32_t n_out, int32_t *out, int64_t B, int32_t out_form);
+
 /* ---- leveled mode under a multi-key cloud key (additions within ABI v7) ---------------------------------
  * The same two operations on multi-key samples, with no blind rotation: the selectors are the parties' uni-encryptions of address
  * bits (mk_tgsw_encrypt, RGSW.UniEnc, mk_internals.jl:185-227) expanded against all public keys (mk_tgsw_expand, :304-345), the

@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -588,6 +588,46 @@ function rot_net(gck::GpuCloudKey, data::Array{Int32,4}, widths, nodes::Abstract
         (Ptr{Cvoid}, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Int64, Int32),
         gck.ctx, data, Int64(size(data, 4)), Int32(E), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), w, Int32(levels), nd, s, Int32(V), out,
         Int64(B), Int32(out_form)))
+    out_form == 0 ? out : unflatten(out, LweParams(width))
+end
+
+"""
+    blind_rotate(gck, acc::Array{Int32,3}, rows::AbstractMatrix, sel=nothing, acc_index=nothing; in_form=0, n_out=1, out_form=2)
+
+Blind rotation of the caller's TLWE accumulators (tfhe_blind_rotate_batch).  `acc` is `N x (k+1) x T`, TLWE samples, trivial or encrypted;
+`rows` is `(steps+1) x B`, column `g` the mask words then the body of row `g`: an LWE sample (`in_form` 0) or exponents in `0:2N-1`
+(`in_form` 1), which pass unchanged.  Row `g` is `A = X^(-barb) acc[acc_index[g]]` on all `k + 1` polynomials, then
+`A += C_sel[i] ⊡ (X^e_i A - A)` for every step, with the selectors of `tgsw_load!` (the bootstrapping key's entries are such selectors).
+`sel` (`steps` entries) and `acc_index` (`B` entries) are 1-based; `nothing` means selector `i` for step `i` and accumulator 1 for every
+row.  `out_form` 0: the accumulators `N x (k+1) x B`; 1: for `j < n_out` the extraction at coefficient `j N / n_out`; 2 (default):
+those keyswitched under the gate key — `n_out * B` samples, row `g`'s output `j` at `g n_out + j`.
+"""
+function blind_rotate(gck::GpuCloudKey, acc::Array{Int32,3}, rows::AbstractMatrix, sel=nothing, acc_index=nothing; in_form::Integer=0, n_out::Integer=1,
+                      out_form::Integer=2)
+    p = gck.params
+    N, k = p.tlwe_polynomial_degree, p.tlwe_mask_size
+    T = size(acc, 3)
+    size(acc)[1:2] == (N, k + 1) && T >= 1 || error("tfhe_mi355x: accumulators must be N x (k+1) x T")
+    words, B = size(rows)
+    steps = words - 1
+    1 <= steps <= 65536 || error("tfhe_mi355x: steps = ", steps, " (1 ... 65536)")
+    0 <= in_form <= 1 || error("tfhe_mi355x: in_form = ", in_form, " (0 LWE samples, 1 exponents)")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    in_form == 0 || all(e -> 0 <= e < 2N, rows) || error("tfhe_mi355x: every exponent must be 0 ... 2N - 1")
+    r = Matrix{Int32}(rows)
+    s = sel === nothing ? nothing : Int32.(collect(sel) .- 1)
+    s === nothing || length(s) == steps || error("tfhe_mi355x: sel must have one entry per step")
+    idx = acc_index === nothing ? nothing : Int32.(collect(acc_index) .- 1)
+    idx === nothing || length(idx) == B || error("tfhe_mi355x: acc_index must have one entry per row")
+    width = out_form == 2 ? p.lwe_size : k * N
+    out = out_form == 0 ? Array{Int32}(undef, N, k + 1, B) : Array{Int32}(undef, width + 1, n_out * B)
+    B == 0 && return out_form == 0 ? out : LweSample[]
+    GC.@preserve acc r s idx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_blind_rotate_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Int64, Int32),
+        gck.ctx, acc, Int64(T), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), r, Int32(steps), Int32(in_form),
+        s === nothing ? Ptr{Int32}(C_NULL) : pointer(s), Int32(n_out), out, Int64(B), Int32(out_form)))
     out_form == 0 ? out : unflatten(out, LweParams(width))
 end
 

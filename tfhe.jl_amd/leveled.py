@@ -33,11 +33,20 @@ X^(sum of weights) table[end state]: f(popcount(x)) of up to N - 1 encrypted bit
 w bits are packed N / w to a sample and leave as w outputs of one address walk (pack_words_to_tlwe, packed_words_net).  The same
 networks run on jointly encrypted variables under a multi-key cloud key (Engine.mk_rot_net, tfhe_mk_rot_net_batch; mk_rot_net_lookup,
 mk_packed_lookup): a table packed N entries to an MK TLWE sample is read at an address whose bits several parties own.
+
+The blind rotation of the caller's accumulators (Engine.blind_rotate, tfhe_blind_rotate_batch; blind_rotate_lookup) is the way back from
+the bootstrapped half: the bootstrapping key, loaded as a selector set (bootstrap_key_selectors), rotates a TLWE sample the caller
+supplies by an LWE sample that gates or lookups computed.  An encrypted test polynomial (private_lut_encrypt) is a lookup table the
+server evaluates without reading it; the output of a CMUX tree over TGSW address bits, rotated by an LWE digit, is a table of p 2^d
+entries addressed in part by a computed value (two_stage_lookup); and with out_form 0 a bootstrap's result leaves as a TLWE sample, an
+entry of the tables cmux_lookup / cmux_net_lookup read (pbs_to_tlwe).  The accumulator's own noise passes through unrefreshed; the
+rotation adds what a bootstrap's rotation adds.
 """
 import numpy as np
 
 from . import mk_keys
 from .keys import _tlwe_encrypt_zero_many, make_bootstrap_key
+from .lut import make_test_vector
 from .lwe import LweKey, LweSampleArray
 from .numeric import dtot32, negacyclic_mul_binary, rand_uniform_torus32, wrap32
 
@@ -442,6 +451,77 @@ def packed_lookup(ck, table, address_tgsw, out_form=2, device=0, encode=encode_g
         raise ValueError(f"a packed table of 2^{depth} entries has {net.entries} samples, got {data.shape[0]}")
     out = rot_net_lookup(ck, data, net, a, out_form=out_form, device=device)
     return out if out_form == 2 else out[:, 0]
+
+
+# ---- the blind rotation of the caller's accumulators: private tables, two-stage lookups, gate outputs as table entries ------------
+def bootstrap_key_selectors(ck):
+    """The bootstrapping key of the CloudKey ck as a selector set for Engine.tgsw_load: int32 [n][l][k+1][k+1][N], selector i the TGSW
+    encryption of bit i of the LWE key (bootstrap.jl:6-15) — the rotation key of Engine.blind_rotate with sel None."""
+    p = ck.params
+    return np.ascontiguousarray(ck.bootstrap_key, np.int32).reshape(p.lwe_size, p.bs_decomp_length, p.tlwe_mask_size + 1, p.tlwe_mask_size + 1,
+                                                                    p.tlwe_polynomial_degree)
+
+
+def private_lut_encrypt(rng, secret_key, f, p, q=None):
+    """A private lookup table: tlwe_encrypt of lut.make_test_vector(f, p, N, q), int32 [1][k+1][N] under secret_key.tlwe_key.  Rotated
+    by lut_encrypt(m, p) (blind_rotate_lookup) it returns f(m) in Z_q, and the server never sees f."""
+    return tlwe_encrypt(rng, secret_key, make_test_vector(f, p, _tlwe_key(secret_key).N, q))
+
+
+def _lwe_rows(lwe):
+    return lwe.data if isinstance(lwe, LweSampleArray) else np.asarray(lwe, np.int32)
+
+
+def blind_rotate_lookup(ck, acc, lwe, extra_tgsw=None, acc_index=None, n_out=1, out_form=2, device=0):
+    """acc[acc_index[g]] rotated by row g of `lwe` under ck's bootstrapping key (Engine.blind_rotate with in_form 0).  Loads the key's n
+    entries as selectors 0 ... n-1 and, behind them, the `extra_tgsw` samples int32 [E][l][k+1][k+1][N] (address bits for a later
+    cmux_tree on the same engine: selectors n ... n+E-1), once; then rotates.  acc: int32 [T][k+1][N] (or [k+1][N]); lwe: an
+    LweSampleArray or int32 [B][n+1].  out_form 2 (default): an LweSampleArray of B n_out samples under the gate key (row g's output j
+    at g n_out + j); 1: extracted int32 [B][n_out][k N + 1]; 0: the TLWE samples int32 [B][k+1][N]."""
+    eng = ck.engine(device)
+    sels = bootstrap_key_selectors(ck)
+    if extra_tgsw is not None:
+        extra = np.asarray(extra_tgsw, np.int32)
+        if extra.ndim != 5 or extra.shape[1:] != sels.shape[1:]:
+            raise ValueError(f"extra_tgsw must be [E]{list(sels.shape[1:])}, got {extra.shape}")
+        sels = np.concatenate([sels, extra])
+    eng.tgsw_load(sels)
+    sel = None if extra_tgsw is None else np.arange(ck.params.lwe_size, dtype=np.int32)
+    out = eng.blind_rotate(acc, _lwe_rows(lwe), sel=sel, acc_index=acc_index, in_form=0, n_out=n_out, out_form=out_form)
+    return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
+
+
+def two_stage_lookup(ck, tables, high_bits_tgsw, low_lwe, p, out_form=2, device=0):
+    """A table of p 2^d entries addressed by d TGSW-encrypted high bits and one LWE digit of Z_p that gates or lookups computed.
+    tables: int32 [2^d][k+1][N], sample h the test polynomial (trivial: tlwe_trivial(make_test_vector(...)); or private_lut_encrypt) of
+    the p entries whose high address is h; high_bits_tgsw: int32 [B][d][l][k+1][k+1][N], bit v of row g (bit 0 the lowest); low_lwe: an
+    LweSampleArray or int32 [B][n+1] of messages in Z_p (lut_encode).  A CMUX tree with out_form 0 picks row g's sample, the rotation
+    by its low digit reads the entry: 2^d - 1 external products plus one rotation per row.  out_form as blind_rotate_lookup (n_out 1)."""
+    a = np.asarray(high_bits_tgsw, np.int32)
+    if a.ndim != 6:
+        raise ValueError(f"high_bits_tgsw must be [B][depth][l][k+1][k+1][N], got {a.shape}")
+    B, depth = a.shape[:2]
+    rows = _lwe_rows(low_lwe)
+    if rows.shape[0] != B:
+        raise ValueError(f"low_lwe has {rows.shape[0]} rows, high_bits_tgsw {B}")
+    if int(p) < 2 or int(p) & (int(p) - 1) or int(p) > a.shape[-1] // 2:
+        raise ValueError(f"p = {p} (a power of two, 2 ... N/2)")
+    n = ck.params.lwe_size
+    eng = ck.engine(device)
+    eng.tgsw_load(np.concatenate([bootstrap_key_selectors(ck), a.reshape((B * depth,) + a.shape[2:])]))
+    picked = eng.cmux_tree(tables, n + np.arange(B * depth, dtype=np.int32).reshape(B, depth), out_form=0)
+    out = eng.blind_rotate(picked, rows, sel=np.arange(n, dtype=np.int32), acc_index=np.arange(B, dtype=np.int32), in_form=0, out_form=out_form)
+    return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
+
+
+def pbs_to_tlwe(ck, lwe, f, p, q=None, device=0):
+    """f(m) of every sample of m in Z_p as a TLWE sample int32 [B][k+1][N]: the rotation of the trivial accumulator (0, test vector)
+    with out_form 0.  The test polynomial is constant over each window, so coefficient 0 carries lut_encode(f(m), q) — where
+    cmux_lookup / cmux_net_lookup read their `data` and extract: a gate or lookup output becomes a table entry with no packing key and
+    no keyswitch noise.  f: a callable Z_p -> Z_q or an int32 test polynomial [N]."""
+    N, k = ck.params.tlwe_polynomial_degree, ck.params.tlwe_mask_size
+    tv = make_test_vector(f, p, N, q) if callable(f) else np.asarray(f, np.int32)
+    return blind_rotate_lookup(ck, tlwe_trivial(tv, k), lwe, out_form=0, device=device)
 
 
 # ---- under a multi-key cloud key -------------------------------------------------------------------------------------------------
