@@ -649,5 +649,15 @@ TFHE_HD void untwist_add2(const cplx (&y)[8], int32_t (&acc)[16], double *worst 
         }
     }
 }
+// untwist_add2's 16 rounded words by themselves, w[r] for coefficient t+64r and w[r + 8] for t+64r+512, from the same FP64
+// operations: for a caller that adds them where the accumulator lives (blind_rotate_kernel_v3: LDS atomic adds whose data operand
+// is the rounding FMA's low result word) instead of reading the accumulator first.
+template <bool MARGIN = false, bool FUSED = true>
+TFHE_HD void untwist_round2(const cplx (&y)[8], int32_t (&w)[16], double *worst = nullptr)
+{
+#pragma unroll
+    for (int r = 0; r < 16; r++) w[r] = 0;
+    untwist_add2<MARGIN, FUSED>(y, w, worst);
+}
 
 }  // namespace tfhe

@@ -288,6 +288,20 @@ __device__ __forceinline__ void accumulate_poly(int lane, const cplx (&y)[8], in
     untwist_add2<MARGIN, FUSED>(y, accr, worst);
     store_cur<16>(lane, accr, img);
 }
+// blind_rotate_kernel_v3's form: accumulate_poly without reading the accumulator.  Each rounded word goes into the image by an LDS
+// atomic add (ds_add_u32, no return value; its data operand is the low word of the rounding FMA's result), the last one also into the
+// mirror by ds_sub_u32: no vector add, and 17 LDS instructions where load / add / store takes 8 + 9.  The image is private to the wave
+// and a wave's LDS operations execute in order: it is not the atomicity that is used but the adder in the LDS.  The siblings keep
+// accumulate_poly (several sit at their register limits and none has been measured with this form).
+template <bool MARGIN>
+__device__ __forceinline__ void accumulate_poly_v3(int lane, const cplx (&y)[8], int32_t *img, double *worst)
+{
+    int32_t w[16];
+    untwist_round2<MARGIN, true>(y, w, worst);
+#pragma unroll
+    for (int m = 0; m < 16; m++) __hip_atomic_fetch_add(&img[kMir + lane + 64 * m], w[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_sub(&img[lane], w[15], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 // accum = (0, ..., 0, X^{-barb} * (mu, ..., mu))     bootstrap.jl:54-56,78 ; tlwe.jl:77-81
 __device__ __forceinline__ void init_body_poly(int lane, int barb, int32_t mu, int32_t *img)
 {

@@ -11,8 +11,8 @@ constexpr int kV3LdsBytes = 2 * kImg * 4 + (kXchElems + 64) * (int)sizeof(cplx);
 //     (br_core.hpp: LaneTan2, 15 registers' worth of doubles per lane) applied by the receiving lane of the second
 //     transposition in both directions, the register part of the twist as compile-time constants:
 //     no global loads on the critical path except the key;
-//   * the accumulator lives only in LDS (read at rotate time and at the final add), each polynomial with its mirror
-//     block so that the rotation's signs and block offsets are scalar (rotate_sub3);
+//   * the accumulator lives only in LDS (read at rotate time; the step's result is added there by ds_add_u32, accumulate_poly_v3),
+//     each polynomial with its mirror block so that the rotation's signs and block offsets are scalar (rotate_sub3);
 //   * key spectra of the next transform prefetched into registers while the current FFT runs;
 //   * wave-private LDS needs only compiler-level ordering, no s_barrier;
 //   * RW rotations per workgroup (RW = 1 or 4), one wave each with its own LDS region.  RW = 4: the four waves sit on the
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
             for (int q = 0; q < 8; q++) out[co][q] = cmulc(out[co][q], tw1f[q]);
             dft8<true>(out[co]);
             double worst = MARGIN ? worst_lds[lane] : 0.0;
-            accumulate_poly<MARGIN>(lane, out[co], acc_lds + co * kImg, &worst);
+            accumulate_poly_v3<MARGIN>(lane, out[co], acc_lds + co * kImg, &worst);
             if (MARGIN) worst_lds[lane] = worst;
         }
         WAVE_LDS_FENCE();
