@@ -4,7 +4,9 @@
 sample for large ones) plus decrypt checks, alternating the host-buffer API, the wire-table level API and — on a
 {0, 0} multi-device context — streamed submits, sharded levels and CHAINS of dependent sharded levels (every level reading a
 random selection of what earlier levels wrote on either device context, with the exchange path and the split threshold drawn at
-random) against the same chain on one device, every wire of the table."""
+random) against the same chain on one device, every wire of the table.  The chains here write fresh wires only and are compared with
+one device, not with a reference: rewrites, uploads over written wires, reads in the middle, refused levels, re-allocation and three
+replicas are what tests/test_wire_table_programs.py runs under pytest, against the host model of tests/wire_table_model.py."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # repo root
