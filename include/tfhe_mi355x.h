@@ -506,8 +506,8 @@ int32_t tfhe_rot_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_
  * [0, 2N) (the message names row and column); TFHE_ERR_NO_KEY: no selector set, or out_form 2 without the keyswitch key;
  * TFHE_ERR_STATE: a multi-key context, a multi-device context, measure_margin on.  The workspaces (the T accumulators, two samples
  * per row, the rows, the extractions) are compared with the device's free memory BEFORE anything is allocated: TFHE_ERR_NOMEM, the
- * context stays usable.  B = 0 returns TFHE_OK.  Out of scope: the multi-key form, and forms on the tuned rotation families' key
- * layouts (the call reads the selector set alone). */
+ * context stays usable.  B = 0 returns TFHE_OK.  The multi-key form is tfhe_mk_blind_rotate_batch below.  Out of scope: forms on
+ * the tuned rotation families' key layouts (the call reads the selector set alone). */
 int32_t tfhe_blind_rotate_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t steps,
                                 int32_t in_form, const int32_t *sel, int32_t n_out, int32_t *out, int64_t B, int32_t out_form);
 
@@ -589,6 +589,41 @@ int32_t tfhe_mk_cmux_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, in
 int32_t tfhe_mk_rot_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_t E, const int32_t *table_index,
                               const int32_t *widths, int32_t levels, const int32_t *nodes, const int32_t *sel, int32_t V,
                               int32_t *out, int64_t B, int32_t out_form);
+
+/* Multi-key blind rotation of the caller's MK TLWE accumulators (addition within ABI v7): tfhe_blind_rotate_batch's contract, argument
+ * for argument, under a multi-key cloud key — mk_blind_rotate (mk_internals.jl:473-485) on an accumulator the caller supplies.  For row g
+ *     A_0 = X^(-barb_g) acc[acc_index[g]]                            on all P + 1 polynomials (mk_mul_by_monomial, :79-85)
+ *     A_(i+1) = A_i + selector[sel[i]] (.) (X^(e_g,i) A_i - A_i)     i = 0 ... steps - 1        (mk_mux_rotate, :464-470)
+ * with the expanded RGSW selectors of tfhe_mk_tgsw_load / tfhe_mk_tgsw_expand_load, step i multiplying for party_of[sel[i]]
+ * (mk_tgsw_extern_mul).  A (party, bit) entry of the multi-key bootstrapping key is such a selector: with the key's P n entries loaded
+ * party-major as selectors 0 ... P n - 1, sel NULL and steps = P n, a row is a multi-key LWE sample as it lies in memory and the call
+ * is the reference's rotation, whichever kernel family serves the gates.  With MK TLWE encryptions of test polynomials as acc one
+ * party's private table is evaluated on jointly encrypted data; with the output of tfhe_mk_cmux_tree_batch (out_form 0 there) as acc a
+ * table of p 2^d entries is addressed in part by a digit computed by multi-key gates or lookups; with out_form 0 here a multi-key
+ * bootstrap's result leaves as an MK TLWE sample that the multi-key trees and networks accept as `data`.
+ * acc: host int32 [T][P+1][N], trivial or encrypted; acc_index: host int32 [B] in [0, T), or NULL = accumulator 0.  rows: host int32
+ * [B][steps+1], the step words then the body; in_form 0: LWE words, switched to Z_2N in the kernel (:502-503); in_form 1: exponents in
+ * [0, 2N).  A zero exponent adds exactly zero.  sel: host int32 [steps] in [0, S), shared by all rows, or NULL = selector i for step i.
+ * steps: 1 ... 65536.  out_form 0: the final accumulator, out int32 [B][P+1][N] (n_out must be 1); 1: for j < n_out its extraction at
+ * coefficient j N / n_out (tfhe_mk_bootstrap_tv_multi_batch's rule), [B][n_out][P*N+1]; 2: those through the multi-key keyswitch,
+ * [B][n_out][P*n+1], operands of every multi-key gate.  n_out: a power of two <= 32, and 1 or <= N / 4.  With acc = (0, ..., 0, tv) and
+ * the bootstrapping key as selectors the call equals tfhe_mk_bootstrap_tv_multi_batch word for word; with B = 1 and out_form 0 it
+ * equals the tfhe_mk_rot_net_batch chain "rotated copy by 2N - barb, then `steps` levels of width 1 with records (0, 0, i, 0, e_i)"
+ * word for word, in one launch instead of steps + 1.
+ * One kernel, one workgroup per row (csrc/kernels_mk_blind_rotate_tlwe.hpp; tfhe_last_kernel_name reports
+ * "mk_tlwe_rotate_kernel(N=..,P=..,l=..,steps=..[,spec=global])"; the option "anyn_spec" is honoured); tfhe_last_rotation_count = B;
+ * tfhe_last_timing_ms: 0 = the rotation, 1 = the keyswitch, 2 = both.  The refusals come in tfhe_blind_rotate_batch's order, everything
+ * validated on the host before anything is uploaded — TFHE_ERR_STATE: a single-key context, a multi-device context, measure_margin on,
+ * and with out_form 2 a keyswitch key loaded for another party count; TFHE_ERR_NO_KEY: no multi-key bootstrapping key, no selector
+ * set, or out_form 2 without the multi-key keyswitch key; TFHE_ERR_INVALID_ARG: NULL buffer, B < 0, steps / in_form / out_form / T /
+ * n_out out of range, n_out != 1 with out_form 0, a selector or accumulator index out of range, sel NULL with fewer than `steps`
+ * selectors loaded, with in_form 1 a word outside [0, 2N) (the message names row and column).  The workspaces are compared with the
+ * device's free memory BEFORE anything is allocated: TFHE_ERR_NOMEM, the context stays usable.  B = 0 returns TFHE_OK.
+ * tfhe_blind_rotate_batch keeps refusing a multi-key context.  Out of scope: an LDS-resident accumulator, and forms on the tuned
+ * multi-key families' key layouts (the call reads the selector set alone). */
+int32_t tfhe_mk_blind_rotate_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows,
+                                   int32_t steps, int32_t in_form, const int32_t *sel, int32_t n_out, int32_t *out, int64_t B,
+                                   int32_t out_form);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

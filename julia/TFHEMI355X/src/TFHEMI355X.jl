@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -1001,6 +1001,49 @@ function mk_rot_net(mck::GpuMKCloudKey, data::Array{Int32,4}, widths, nodes::Abs
     out_form == 2 || return out
     params = LweParams(n)
     [MKLweSample(params, reshape(out[1:n*P, r], n, P), out[n * P + 1, r], 0.) for r in 1:F*B]
+end
+
+"""
+    mk_blind_rotate(mck, acc::Array{Int32,3}, rows::AbstractMatrix, sel=nothing, acc_index=nothing; in_form=0, n_out=1, out_form=2)
+
+Multi-key blind rotation of the caller's MK TLWE accumulators (tfhe_mk_blind_rotate_batch): `blind_rotate` under a multi-key cloud key.
+`acc` is `N x (P+1) x T`, MK TLWE samples, trivial or encrypted; `rows` is `(steps+1) x B`, column `g` the step words then the body of row
+`g`: a multi-key LWE sample as it lies in memory (`in_form` 0) or exponents in `0:2N-1` (`in_form` 1), which pass unchanged.  Row `g` is
+`A = X^(-barb) acc[acc_index[g]]` on all `P + 1` polynomials, then `A += C_sel[i] ⊡ (X^e_i A - A)` for every step, with the selectors of
+`mk_tgsw_load!` and the product for the party of selector `sel[i]` (the `(party, bit)` entries of the multi-key bootstrapping key are
+such selectors).  `sel` (`steps` entries) and `acc_index` (`B` entries) are 1-based; `nothing` means selector `i` for step `i` and
+accumulator 1 for every row.  `out_form` 0: the accumulators `N x (P+1) x B`; 1: for `j < n_out` the extraction at coefficient
+`j N / n_out`, `(P N + 1) x n_out B`; 2 (default): those keyswitched — `n_out * B` `MKLweSample`s, row `g`'s output `j` at `g n_out + j`.
+"""
+function mk_blind_rotate(mck::GpuMKCloudKey, acc::Array{Int32,3}, rows::AbstractMatrix, sel=nothing, acc_index=nothing; in_form::Integer=0,
+                         n_out::Integer=1, out_form::Integer=2)
+    p, P = mck.params, mck.parties
+    N, n = p.tlwe_polynomial_degree, p.lwe_size
+    T = size(acc, 3)
+    size(acc)[1:2] == (N, P + 1) && T >= 1 || error("tfhe_mi355x: accumulators must be N x (P+1) x T")
+    words, B = size(rows)
+    steps = words - 1
+    1 <= steps <= 65536 || error("tfhe_mi355x: steps = ", steps, " (1 ... 65536)")
+    0 <= in_form <= 1 || error("tfhe_mi355x: in_form = ", in_form, " (0 LWE samples, 1 exponents)")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    in_form == 0 || all(e -> 0 <= e < 2N, rows) || error("tfhe_mi355x: every exponent must be 0 ... 2N - 1")
+    r = Matrix{Int32}(rows)
+    s = sel === nothing ? nothing : Int32.(collect(sel) .- 1)
+    s === nothing || length(s) == steps || error("tfhe_mi355x: sel must have one entry per step")
+    idx = acc_index === nothing ? nothing : Int32.(collect(acc_index) .- 1)
+    idx === nothing || length(idx) == B || error("tfhe_mi355x: acc_index must have one entry per row")
+    width = out_form == 2 ? P * n : P * N
+    out = out_form == 0 ? Array{Int32}(undef, N, P + 1, B) : Array{Int32}(undef, width + 1, n_out * B)
+    B == 0 && return out_form == 2 ? MKLweSample[] : out
+    GC.@preserve acc r s idx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_blind_rotate_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Int64, Int32),
+        mck.ctx, acc, Int64(T), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), r, Int32(steps), Int32(in_form),
+        s === nothing ? Ptr{Int32}(C_NULL) : pointer(s), Int32(n_out), out, Int64(B), Int32(out_form)))
+    out_form == 2 || return out
+    params = LweParams(n)
+    [MKLweSample(params, reshape(out[1:n*P, r], n, P), out[n * P + 1, r], 0.) for r in 1:n_out*B]
 end
 
 """

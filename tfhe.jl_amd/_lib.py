@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "tfhe_tgsw_load", "tfhe_extern_mul_batch", "tfhe_cmux_tree_batch", "tfhe_cmux_net_batch",
     "tfhe_mk_tgsw_load", "tfhe_mk_tgsw_expand_load", "tfhe_mk_extern_mul_batch", "tfhe_mk_cmux_tree_batch",
     "tfhe_mk_cmux_net_batch", "tfhe_rot_net_batch", "tfhe_mk_rot_net_batch", "tfhe_blind_rotate_batch",
+    "tfhe_mk_blind_rotate_batch",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -167,6 +168,8 @@ def load():
         lib.tfhe_mk_rot_net_batch.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, i32]
     if hasattr(lib, "tfhe_blind_rotate_batch"):
         lib.tfhe_blind_rotate_batch.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, i32, vp, i64, i32]
+    if hasattr(lib, "tfhe_mk_blind_rotate_batch"):
+        lib.tfhe_mk_blind_rotate_batch.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, i32, vp, i64, i32]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -657,6 +660,42 @@ class Engine:
         out = np.empty(shape, np.int32)      # (an out_form the library refuses: nothing written)
         self._check(self._lib.tfhe_mk_rot_net_batch(self._h, _ptr(d), d.shape[0], d.shape[1], _ptr(idx), _ptr(net.widths), net.levels, _ptr(net.nodes),
                                                     _ptr(sel), V, _ptr(out), B, int(out_form)))
+        return out
+
+    def mk_blind_rotate(self, acc, rows, sel=None, acc_index=None, in_form=0, n_out=1, out_form=2):
+        """Multi-key blind rotation of the caller's MK TLWE accumulators (tfhe_mk_blind_rotate_batch): blind_rotate under a multi-key
+        cloud key.  acc: int32 [T][P+1][N] MK TLWE samples, trivial or encrypted (or [P+1][N]: one accumulator); rows: int32
+        [B][steps+1], the step words then the body — multi-key LWE samples (in_form 0) or exponents in [0, 2N) (in_form 1); sel: int32
+        [steps] indices into the multi-key selector set, shared by all rows, or None (selector i for step i), step i multiplying for
+        the party of its selector; acc_index: [B] or None (accumulator 0).  Row g's result is the MK TLWE sample [B][P+1][N] (out_form
+        0, n_out 1), its extractions at the coefficients j N / n_out [B][n_out][P*N+1] (1), or those keyswitched to multi-key LWE
+        samples [B][n_out][P*n+1] (2), operands of every mk_gate."""
+        P = self._mk_width("mk_blind_rotate")
+        a = _i32c(acc)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (P + 1, self.N):
+            raise ValueError(f"accumulators must be [T][{P + 1}][{self.N}], got {a.shape}")
+        r = _i32c(rows)
+        if r.ndim != 2 or r.shape[1] < 2:
+            raise ValueError(f"rows must be [B][steps+1] with at least one step, got {r.shape}")
+        B, steps = r.shape[0], r.shape[1] - 1
+        s = None
+        if sel is not None:
+            s = _i32c(sel).reshape(-1)
+            if s.size != steps:
+                raise ValueError(f"sel must have one entry per step ({steps}), got {s.size}")
+        idx = None
+        if acc_index is not None:
+            idx = _i32c(acc_index).reshape(-1)
+            if idx.size != B:
+                raise ValueError(f"acc_index must have one entry per row ({B}), got {idx.size}")
+        n_out = int(n_out)
+        K = n_out if 1 <= n_out <= 32 else 0
+        shape = {0: (B, P + 1, self.N), 1: (B, K, P * self.N + 1), 2: (B, K, P * self.n + 1)}.get(int(out_form), (0,))
+        out = np.empty(shape, np.int32)      # (an out_form or n_out the library refuses: nothing written)
+        self._check(self._lib.tfhe_mk_blind_rotate_batch(self._h, _ptr(a), a.shape[0], _ptr(idx), _ptr(r), steps, int(in_form), _ptr(s), n_out, _ptr(out),
+                                                         B, int(out_form)))
         return out
 
     # ---- levelised circuits on the device-resident wire table ----

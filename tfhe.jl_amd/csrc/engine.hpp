@@ -19,6 +19,7 @@
 //   engine_rot_net.hip    leveled mode: CMUX networks with a monomial X^rot on every edge (packed tables, weighted automata)  ("rot net")
 //   engine_mk_rot_net.hip   the same networks with monomial edges under a multi-key cloud key                          ("mk rot net")
 //   engine_blind_rotate.hip   the blind rotation of the caller's TLWE accumulators by LWE samples, on the caller's selectors  ("blind rotate")
+//   engine_mk_blind_rotate.hip   the same rotation of MK TLWE accumulators under a multi-key cloud key                  ("mk blind rotate")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
 //   leveled_run.hpp       host-only: the one runner behind the eleven leveled entry points (workspaces, uploads, level loop, download)
 //   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share

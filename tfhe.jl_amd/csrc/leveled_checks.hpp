@@ -1,5 +1,5 @@
 // leveled_checks.hpp — host-only checks that more than one leveled unit makes before anything is uploaded: the state a multi-key
-// leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip) and the netlist of a CMUX network
+// leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip, engine_mk_blind_rotate.hip) and the netlist of a CMUX network
 // (engine_cmux_net.hip, engine_mk_cmux_net.hip; with monomial edges: engine_rot_net.hip, engine_mk_rot_net.hip).  Every function sets
 // the context's error message, naming the caller `who`, and returns its code.
 #pragma once

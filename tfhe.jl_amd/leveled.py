@@ -41,6 +41,12 @@ server evaluates without reading it; the output of a CMUX tree over TGSW address
 entries addressed in part by a computed value (two_stage_lookup); and with out_form 0 a bootstrap's result leaves as a TLWE sample, an
 entry of the tables cmux_lookup / cmux_net_lookup read (pbs_to_tlwe).  The accumulator's own noise passes through unrefreshed; the
 rotation adds what a bootstrap's rotation adds.
+
+Under a multi-key cloud key the same bridge is Engine.mk_blind_rotate (tfhe_mk_blind_rotate_batch; mk_blind_rotate_lookup): the multi-key
+bootstrapping key is a selector set of P n expanded RGSW samples, party-major (mk_bootstrap_key_selectors), and rotates an MK TLWE
+sample by a multi-key LWE sample as it lies in memory.  mk_private_lut_encrypt is one party's private function on jointly encrypted
+data, mk_two_stage_lookup a table of p 2^d entries addressed by jointly encrypted TGSW bits and a computed digit, mk_pbs_to_tlwe a
+multi-key bootstrap's result as an entry of the tables mk_cmux_lookup / mk_cmux_net_lookup read.
 """
 import numpy as np
 
@@ -651,3 +657,103 @@ def mk_packed_lookup(ck, table, uni_bits, party_of, out_form=2, expand="device",
         raise ValueError(f"a packed table of 2^{depth} entries has {net.entries} samples, got {data.shape[0]}")
     out = mk_rot_net_lookup(ck, data, net, uni_bits, party_of, out_form=out_form, expand=expand, device=device)
     return out if out_form == 2 else out[:, 0]
+
+
+# ---- the multi-key blind rotation of the caller's accumulators: one party's private table on jointly encrypted data ----------------
+def mk_bootstrap_key_selectors(ck):
+    """The bootstrapping key of the MKCloudKey ck as a selector set for Engine.mk_tgsw_load: (tgsw int32 [P n][2lP + 2l][N], party_of
+    int32 [P n]), party-major — selector i n + j the expanded RGSW encryption of bit j of party i's LWE key (mk_internals.jl:419-439),
+    the rotation key of Engine.mk_blind_rotate with sel None: a multi-key LWE sample's words line up with it."""
+    bk = np.ascontiguousarray(ck.bootstrap_key, np.int32)
+    P, n = bk.shape[:2]
+    return bk.reshape((P * n,) + bk.shape[2:]), np.repeat(np.arange(P, dtype=np.int32), n)
+
+
+def mk_private_lut_encrypt(rng, tlwe_keys, alpha, f, p, q=None):
+    """A private lookup table under P parties' TLWE keys: mk_tlwe_encrypt of lut.make_test_vector(f, p, N, q), int32 [1][P+1][N].
+    Rotated by mk_lut_encrypt(m, p) (mk_blind_rotate_lookup) it returns f(m) in Z_q, and the server never sees f."""
+    return mk_tlwe_encrypt(rng, tlwe_keys, alpha, make_test_vector(f, p, tlwe_keys[0].N, q))
+
+
+def _mk_load_key_selectors(ck, extra_uni_bits, extra_party_of, expand, device):
+    """ck's P n bootstrapping-key entries as selectors 0 ... P n - 1 of its engine on `device` and, behind them, the E samples of
+    extra_uni_bits (six arrays [E][l][N], sample e uni-encrypted by party extra_party_of[e]).  expand "device": RGSW.Expand of the
+    parts' uni-encryptions and the extra ones on the GPU; "host": the key's host expansion and mk_tgsw_expand.  Returns the engine."""
+    assert expand in ("device", "host")
+    P, n = ck.parties, ck.params.lwe_size
+    extra, who_extra = None, np.zeros(0, np.int32)
+    if extra_uni_bits is not None:
+        extra = [np.asarray(a, np.int32) for a in extra_uni_bits]
+        if len(extra) != 6 or extra[0].ndim != 3 or any(a.shape != extra[0].shape for a in extra):
+            raise ValueError("extra_uni_bits must be six arrays [E][l][N]")
+        who_extra = np.asarray(extra_party_of, np.int32).reshape(-1)
+        if who_extra.size != extra[0].shape[0]:
+            raise ValueError(f"extra_party_of must have one entry per extra sample ({extra[0].shape[0]}), got {who_extra.size}")
+    who = np.concatenate([np.repeat(np.arange(P, dtype=np.int32), n), who_extra])
+    pub = np.stack([part.public_b for part in ck._parts])
+    eng = ck.engine(device)
+    if expand == "device":
+        flat = [a.reshape((P * n,) + a.shape[2:]) for a in ck._part_arrays()[1:]]
+        if extra is not None:
+            flat = [np.concatenate([a, b]) for a, b in zip(flat, extra)]
+        eng.mk_tgsw_expand_load(pub, who, *flat)
+    else:
+        tg = mk_bootstrap_key_selectors(ck)[0]
+        if extra is not None:
+            more = np.zeros((who_extra.size,) + tg.shape[1:], np.int32)
+            for i in range(P):
+                mine = np.nonzero(who_extra == i)[0]
+                if mine.size:
+                    more[mine] = mk_tgsw_expand(ck.params, pub, i, *[a[mine] for a in extra])
+            tg = np.concatenate([tg, more])
+        eng.mk_tgsw_load(tg, who)
+    return eng
+
+
+def mk_blind_rotate_lookup(ck, acc, lwe, extra_uni_bits=None, extra_party_of=None, acc_index=None, n_out=1, out_form=2, expand="device", device=0):
+    """acc[acc_index[g]] rotated by row g of `lwe` under the MKCloudKey ck's bootstrapping key (Engine.mk_blind_rotate with in_form 0).
+    Loads the key's P n entries as selectors 0 ... P n - 1 and, behind them, the extra address bits (six arrays [E][l][N] of
+    mk_tgsw_uni_encrypt_bits, sample e by party extra_party_of[e]: selectors P n ... P n + E - 1, for a later mk_cmux_tree on the same
+    engine), once; then rotates.  expand "device": RGSW.Expand on the GPU (tfhe_mk_tgsw_expand_load) of the parts' uni-encryptions,
+    "host": the host expansion then mk_tgsw_load.  acc: int32 [T][P+1][N] (or [P+1][N]); lwe: int32 [B][P n + 1].  out_form 2
+    (default): multi-key LWE samples int32 [B n_out][P*n+1] for mk_decrypt / mk_gate_* (row g's output j at g n_out + j); 1: extracted
+    int32 [B][n_out][P*N+1]; 0: the MK TLWE samples int32 [B][P+1][N]."""
+    eng = _mk_load_key_selectors(ck, extra_uni_bits, extra_party_of, expand, device)
+    sel = None if extra_uni_bits is None else np.arange(ck.parties * ck.params.lwe_size, dtype=np.int32)
+    out = eng.mk_blind_rotate(acc, np.asarray(lwe, np.int32), sel=sel, acc_index=acc_index, in_form=0, n_out=n_out, out_form=out_form)
+    return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
+
+
+def mk_two_stage_lookup(ck, tables, high_uni_bits, party_of, low_lwe, p, out_form=2, expand="device", device=0):
+    """A table of p 2^d entries addressed by d jointly encrypted high bits and one multi-key LWE digit of Z_p that gates or lookups
+    computed.  tables: int32 [2^d][P+1][N], sample h the test polynomial (trivial: mk_tlwe_trivial(make_test_vector(...), P); or
+    mk_private_lut_encrypt) of the p entries whose high address is h; high_uni_bits: the six arrays of mk_tgsw_uni_encrypt_bits, each
+    [B][d][l][N], bit v of row g (bit 0 the lowest) uni-encrypted by party party_of[g][v] (party_of: [B][d], or [d] for every row);
+    low_lwe: int32 [B][P n + 1] of messages in Z_p (mk_lut_encrypt).  An MK CMUX tree with out_form 0 picks row g's sample, the
+    rotation by its low digit reads the entry: 2^d - 1 MK external products plus one MK rotation per row.  out_form as
+    mk_blind_rotate_lookup (n_out 1)."""
+    arrs = [np.asarray(a, np.int32) for a in high_uni_bits]
+    if len(arrs) != 6 or arrs[0].ndim != 4 or any(a.shape != arrs[0].shape for a in arrs):
+        raise ValueError("high_uni_bits must be six arrays [B][depth][l][N]")
+    B, depth = arrs[0].shape[:2]
+    rows = np.asarray(low_lwe, np.int32)
+    if rows.shape[0] != B:
+        raise ValueError(f"low_lwe has {rows.shape[0]} rows, high_uni_bits {B}")
+    if int(p) < 2 or int(p) & (int(p) - 1) or int(p) > arrs[0].shape[-1] // 2:
+        raise ValueError(f"p = {p} (a power of two, 2 ... N/2)")
+    who = np.broadcast_to(np.asarray(party_of, np.int32), (B, depth)).reshape(-1)
+    Pn = ck.parties * ck.params.lwe_size
+    eng = _mk_load_key_selectors(ck, [a.reshape((B * depth,) + a.shape[2:]) for a in arrs], who, expand, device)
+    picked = eng.mk_cmux_tree(tables, Pn + np.arange(B * depth, dtype=np.int32).reshape(B, depth), out_form=0)
+    out = eng.mk_blind_rotate(picked, rows, sel=np.arange(Pn, dtype=np.int32), acc_index=np.arange(B, dtype=np.int32), in_form=0, out_form=out_form)
+    return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
+
+
+def mk_pbs_to_tlwe(ck, lwe, f, p, q=None, device=0):
+    """f(m) of every multi-key sample of m in Z_p as an MK TLWE sample int32 [B][P+1][N]: the rotation of the trivial accumulator
+    (0, ..., 0, test vector) with out_form 0.  The test polynomial is constant over each window, so coefficient 0 carries
+    lut_encode(f(m), q) — where mk_cmux_lookup / mk_cmux_net_lookup read their `data` and extract: a multi-key gate or lookup output
+    becomes a table entry with no packing key and no keyswitch noise.  f: a callable Z_p -> Z_q or an int32 test polynomial [N]."""
+    N = ck.params.tlwe_polynomial_degree
+    tv = make_test_vector(f, p, N, q) if callable(f) else np.asarray(f, np.int32)
+    return mk_blind_rotate_lookup(ck, mk_tlwe_trivial(tv, ck.parties), lwe, out_form=0, device=device)
