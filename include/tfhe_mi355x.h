@@ -511,6 +511,64 @@ int32_t tfhe_rot_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_
 int32_t tfhe_blind_rotate_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t steps,
                                 int32_t in_form, const int32_t *sel, int32_t n_out, int32_t *out, int64_t B, int32_t out_form);
 
+/* ---- leveled mode on device-resident tables (additions within ABI v7) -----------------------------------
+ * The leveled half's own table beside the wire table: TLWE samples that stay on the device between leveled calls, and level calls
+ * that read and write both tables, so that a program of gates, private lookups and gates crosses PCIe only at its ends.  No new
+ * cryptography, no new key material: every result equals, word for word, the host-buffer batch call above on the same samples.
+ * Single-key, one-device contexts only (TFHE_ERR_STATE otherwise).
+ *
+ * tfhe_tlwe_alloc: a device table int32 [slots][k+1][N]; slots = 0 frees it; reallocating discards the old contents.  The size is
+ * compared with the device's free memory (the table being replaced counted as free) before anything is freed or allocated:
+ * TFHE_ERR_NOMEM, the context and its present table stay as they were.  Waits for the levels queued on the context.
+ * tfhe_tlwe_upload / tfhe_tlwe_download: slots [first, first + count) from / to host int32 [count][k+1][N], ordered behind the levels
+ * queued on the context; both return with the copy done.  TFHE_ERR_STATE without a table, TFHE_ERR_INVALID_ARG for a range outside
+ * it or a NULL buffer with count > 0. */
+int32_t tfhe_tlwe_alloc(tfhe_ctx *ctx, int64_t slots);
+int32_t tfhe_tlwe_upload(tfhe_ctx *ctx, int64_t first, int64_t count, const int32_t *host);
+int32_t tfhe_tlwe_download(tfhe_ctx *ctx, int64_t first, int64_t count, int32_t *host);
+
+/* Replaces selectors [first, first + count) of the set tfhe_tgsw_load loaded, in place: tgsw is int32 [count][l][k+1][k+1][N]; every
+ * other selector keeps its exact words, and the replaced ones are what a fresh tfhe_tgsw_load of the edited set would hold.  For a
+ * set "the key's n selectors, then a request's address bits": the key is loaded once and the address bits are swapped behind it.
+ * Waits for the work queued on the context first.  TFHE_ERR_NO_KEY: no set loaded; TFHE_ERR_INVALID_ARG: NULL pointer, count < 1, a
+ * range outside [0, S); TFHE_ERR_STATE: a multi-key or multi-device context. */
+int32_t tfhe_tgsw_update(tfhe_ctx *ctx, const int32_t *tgsw, int64_t first, int64_t count);
+
+/* tfhe_rot_net_batch between the tables.  Level 0 of row g reads source `src` at TLWE slot table_first[g] + src (table_first: host
+ * int32 [B]; NULL = 0 for every row, so src is an absolute slot); the network (E, widths, levels, nodes, sel, V) is that call's.
+ * out_form 0: output node i of row g goes to slot out_first + g F + i (F = widths[levels-1]); the range must lie inside the table and
+ * must not meet any row's read range [table_first[g], + E).  out_form 2: the sample extracted at coefficient 0 and keyswitched goes
+ * to wire out_wires[g F + i] (host int32 [B F]) of the single-key wire table; no wire may be named twice.  out_form 1 is refused
+ * (extracted rows have no table).  The words equal tfhe_rot_net_batch on the same samples — with every rotation 0 that is
+ * tfhe_cmux_net_batch, with a tree's netlist tfhe_cmux_tree_batch: one level call covers all three.  The same kernel
+ * (rot_net_level_kernel), unchanged; timing slots and tfhe_last_kernel_name as tfhe_rot_net_batch.
+ *
+ * tfhe_blind_rotate_batch between the tables.  Row g's rotating sample is formed exactly as tfhe_lut_level forms it,
+ *     x_g = sum over t in [term_start[g], term_start[g+1]) of term_coef[t] * wire[term_wire[t]], plus cst[g] on the body   (mod 2^32)
+ * (cst NULL: 0; a row without terms is the trivial sample), read as in_form 0 with steps = the context's n;
+ * A_0 = X^(-barb_g) slot[acc_slot[g]] (host int32 [B]; slots may repeat); sel: host int32 [n] or NULL, as in the batch call.
+ * out_form 0 (n_out must be 1): the final accumulator goes to slot out_slot[g] (host int32 [B]); the slots must be distinct and none
+ * may be an acc_slot of the same call.  out_form 2: the n_out extractions, keyswitched, go to wires out_wires[g n_out + j] (host int32
+ * [B n_out]); no wire may be named twice and none may be a term wire of the same call.  The unused one of out_slot / out_wires may
+ * be NULL.  The words equal tfhe_blind_rotate_batch(acc = those slots' samples, rows = x_g, steps = n, in_form 0, sel, n_out,
+ * out_form).  tfhe_lut_level's prologue stages the rows (linear_prologue_kernel), then one kernel, one workgroup per row
+ * (csrc/kernels_tlwe_levels.hpp; tfhe_last_kernel_name reports "tlwe_rotate_level_kernel(N=..,k=..,l=..,steps=..[,spec=global])";
+ * "anyn_spec" is honoured); tfhe_last_rotation_count = B; tfhe_last_timing_ms as the batch call.
+ *
+ * Both level calls: everything is validated on the host before anything is uploaded or written, the message names the offender, and
+ * a refused call changes no slot and no wire.  In this order — TFHE_ERR_STATE: a multi-key context, a multi-device context,
+ * measure_margin on, no TLWE table, no wire table when out_form 2 or terms need one, a wire table with multi-key rows;
+ * TFHE_ERR_INVALID_ARG: everything about the arguments; TFHE_ERR_NO_KEY: no selector set, or out_form 2 without the keyswitch key
+ * (a selector index is checked against the loaded set after that).  The workspaces are compared with the device's free memory
+ * before anything is allocated (TFHE_ERR_NOMEM, the context stays usable).  B = 0 returns TFHE_OK.  The calls are ordered behind
+ * the asynchronous levels queued on the context (tfhe_gates_level, tfhe_lut_level, ...) and SYNCHRONISE before they return: the
+ * slots and wires they wrote are complete, and the caller's arrays are free, on return. */
+int32_t tfhe_rot_net_level(tfhe_ctx *ctx, const int32_t *table_first, int32_t E, const int32_t *widths, int32_t levels, const int32_t *nodes,
+                           const int32_t *sel, int32_t V, int32_t out_form, int64_t out_first, const int32_t *out_wires, int64_t B);
+int32_t tfhe_blind_rotate_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,
+                                const int32_t *term_coef, const int32_t *cst, const int32_t *sel, int32_t n_out, int32_t out_form,
+                                const int32_t *out_slot, const int32_t *out_wires, int64_t B);
+
 /* ---- leveled mode under a multi-key cloud key (additions within ABI v7) ---------------------------------
  * The same two operations on multi-key samples, with no blind rotation: the selectors are the parties' uni-encryptions of address
  * bits (mk_tgsw_encrypt, RGSW.UniEnc, mk_internals.jl:185-227) expanded against all public keys (mk_tgsw_expand, :304-345), the

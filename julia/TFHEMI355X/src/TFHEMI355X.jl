@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate, tlwe_alloc!, tlwe_upload!, tlwe_download, tgsw_update!, rot_net_level!, blind_rotate_level!
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -629,6 +629,142 @@ function blind_rotate(gck::GpuCloudKey, acc::Array{Int32,3}, rows::AbstractMatri
         gck.ctx, acc, Int64(T), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), r, Int32(steps), Int32(in_form),
         s === nothing ? Ptr{Int32}(C_NULL) : pointer(s), Int32(n_out), out, Int64(B), Int32(out_form)))
     out_form == 0 ? out : unflatten(out, LweParams(width))
+end
+
+"""
+    tlwe_alloc!(gck, slots)
+
+The device-resident TLWE table of the leveled half (tfhe_tlwe_alloc): `slots` samples of `N x (k+1)` words beside the wire table; 0 frees
+it, reallocating discards the contents.  `rot_net_level!` and `blind_rotate_level!` read and write it; slots are 1-based here.
+"""
+function tlwe_alloc!(gck::GpuCloudKey, slots::Integer)
+    slots >= 0 || error("tfhe_mi355x: slots = ", slots, " (at least 0)")
+    @locked gck.ctx check(gck.ctx, ccall((:tfhe_tlwe_alloc, LIB), Int32, (Ptr{Cvoid}, Int64), gck.ctx, Int64(slots)))
+    gck
+end
+
+"""
+    tlwe_upload!(gck, first, samples::Array{Int32,3})
+
+`samples`, `N x (k+1) x count`, into slots `first : first + count - 1` (1-based) of the TLWE table (tfhe_tlwe_upload), behind the levels
+queued on the context.
+"""
+function tlwe_upload!(gck::GpuCloudKey, first::Integer, samples::Array{Int32,3})
+    p = gck.params
+    N, k = p.tlwe_polynomial_degree, p.tlwe_mask_size
+    size(samples)[1:2] == (N, k + 1) || error("tfhe_mi355x: TLWE samples must be N x (k+1) x count")
+    first >= 1 || error("tfhe_mi355x: slots are 1-based, first = ", first)
+    GC.@preserve samples @locked gck.ctx check(gck.ctx, ccall((:tfhe_tlwe_upload, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Int32}), gck.ctx, Int64(first - 1), Int64(size(samples, 3)), samples))
+    gck
+end
+
+"""
+    tlwe_download(gck, first, count)  ->  Array{Int32,3}
+
+Slots `first : first + count - 1` (1-based) of the TLWE table as `N x (k+1) x count` (tfhe_tlwe_download), behind the levels queued on
+the context.
+"""
+function tlwe_download(gck::GpuCloudKey, first::Integer, count::Integer)
+    p = gck.params
+    N, k = p.tlwe_polynomial_degree, p.tlwe_mask_size
+    first >= 1 && count >= 0 || error("tfhe_mi355x: slots are 1-based and count >= 0, got first = ", first, ", count = ", count)
+    out = Array{Int32}(undef, N, k + 1, count)
+    GC.@preserve out @locked gck.ctx check(gck.ctx, ccall((:tfhe_tlwe_download, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Int32}), gck.ctx, Int64(first - 1), Int64(count), out))
+    out
+end
+
+"""
+    tgsw_update!(gck, first, tgsw::Array{Int32})
+
+Replaces selectors `first : first + count - 1` (1-based) of the set `tgsw_load!` loaded, in place (tfhe_tgsw_update); `tgsw` as in
+`tgsw_load!`.  Every other selector keeps its words: the key's `n` selectors are loaded once, a request's address bits swapped behind them.
+"""
+function tgsw_update!(gck::GpuCloudKey, first::Integer, tgsw::Array{Int32})
+    p = gck.params
+    per = p.tlwe_polynomial_degree * (p.tlwe_mask_size + 1)^2 * p.bs_decomp_length
+    (length(tgsw) > 0 && length(tgsw) % per == 0) || error("tfhe_mi355x: TGSW samples must hold a positive multiple of ", per, " words")
+    first >= 1 || error("tfhe_mi355x: selectors are 1-based, first = ", first)
+    GC.@preserve tgsw @locked gck.ctx check(gck.ctx, ccall((:tfhe_tgsw_update, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Int64), gck.ctx, tgsw, Int64(first - 1), Int64(length(tgsw) ÷ per)))
+    gck
+end
+
+"""
+    rot_net_level!(gck, E, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_first=nothing; out_form=2, out_first=1, out_wires=nothing)
+
+`rot_net` between the device-resident tables (tfhe_rot_net_level).  Level 0 of row `g` reads source `src` at TLWE slot
+`table_first[g] + src - 1` (`table_first` 1-based, `B` entries; `nothing`: `src` is an absolute slot); `E`, `widths`, `nodes`, `sel` as in
+`rot_net`.  `out_form` 0: output node `i` of row `g` goes to slot `out_first + (g - 1) F + i - 1`; `out_form` 2: keyswitched, to wire
+`out_wires[(g - 1) F + i]` (1-based wires of the wire table).  The words are `rot_net`'s on the same samples.  Synchronous.
+"""
+function rot_net_level!(gck::GpuCloudKey, E::Integer, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_first=nothing; out_form::Integer=2,
+                        out_first::Integer=1, out_wires=nothing)
+    N = gck.params.tlwe_polynomial_degree
+    w = Int32.(collect(widths))
+    levels = length(w)
+    1 <= levels <= 1024 || error("tfhe_mi355x: levels = ", levels, " (1 ... 1024)")
+    all(x -> 1 <= x <= 4096, w) || error("tfhe_mi355x: every width must be 1 ... 4096")
+    size(nodes) == (5, sum(w)) || error("tfhe_mi355x: nodes must be 5 x sum(widths)")
+    all(r -> 0 <= r < 2N, view(nodes, 4:5, :)) || error("tfhe_mi355x: every rotation must be 0 ... 2N - 1")
+    E >= 1 || error("tfhe_mi355x: E = ", E, " (at least one entry)")
+    V, B = size(sel)
+    V >= 1 || error("tfhe_mi355x: sel must be V x B with V >= 1")
+    out_form == 0 || out_form == 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 into TLWE slots, 2 key-switched into wires)")
+    nd = Matrix{Int32}(vcat(nodes[1:3, :] .- 1, nodes[4:5, :]))
+    s = Matrix{Int32}(sel .- 1)
+    tf = table_first === nothing ? nothing : Int32.(collect(table_first) .- 1)
+    tf === nothing || length(tf) == B || error("tfhe_mi355x: table_first must have one entry per row")
+    F = Int(w[end])
+    ow = out_wires === nothing ? nothing : Int32.(collect(out_wires) .- 1)
+    out_form != 2 || (ow !== nothing && length(ow) == F * B) || error("tfhe_mi355x: out_wires must have F * B entries with out_form 2")
+    out_form != 0 || out_first >= 1 || error("tfhe_mi355x: slots are 1-based, out_first = ", out_first)
+    GC.@preserve w nd s tf ow @locked gck.ctx check(gck.ctx, ccall((:tfhe_rot_net_level, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Int64, Ptr{Int32}, Int64),
+        gck.ctx, tf === nothing ? Ptr{Int32}(C_NULL) : pointer(tf), Int32(E), w, Int32(levels), nd, s, Int32(V), Int32(out_form), Int64(out_first - 1),
+        ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
+    gck
+end
+
+"""
+    blind_rotate_level!(gck, acc_slot, term_start, term_wire, term_coef; cst=nothing, sel=nothing, n_out=1, out_form=2, out_slot=nothing, out_wires=nothing)
+
+`blind_rotate` between the device-resident tables (tfhe_blind_rotate_level).  Row `g` rotates the sample in TLWE slot `acc_slot[g]` by the
+LWE sample `sum_t term_coef[t] * wire[term_wire[t]] + cst[g]` over the terms `term_start[g] + 1 : term_start[g + 1]` (`term_start` is the
+0-based prefix sum of the rows' term counts, `B + 1` entries from 0, as tfhe_lut_level takes it; it and the coefficients pass unchanged;
+slots, wires and selectors are 1-based), over the context's `n` steps on the selectors `sel` (`nothing`: selector `i` for step `i`).
+`out_form` 0 (`n_out` 1): the final accumulator goes to slot `out_slot[g]`; `out_form` 2: the `n_out` extractions, keyswitched, go to
+wires `out_wires[(g - 1) n_out + j]`.  The words are `blind_rotate`'s on the same samples.  Synchronous.
+"""
+function blind_rotate_level!(gck::GpuCloudKey, acc_slot, term_start, term_wire, term_coef; cst=nothing, sel=nothing, n_out::Integer=1,
+                             out_form::Integer=2, out_slot=nothing, out_wires=nothing)
+    p = gck.params
+    N = p.tlwe_polynomial_degree
+    acc = Int32.(collect(acc_slot) .- 1)
+    B = length(acc)
+    start = Int32.(collect(term_start))
+    length(start) == B + 1 && start[1] == 0 && issorted(start) || error("tfhe_mi355x: term_start must be B + 1 non-decreasing entries from 0")
+    T = Int(start[end])
+    tw = Int32.(collect(term_wire) .- 1)
+    tc = Int32.(collect(term_coef))
+    length(tw) >= T && length(tc) >= T || error("tfhe_mi355x: term_wire and term_coef must have term_start[end] entries")
+    c = cst === nothing ? nothing : Int32.(collect(cst))
+    c === nothing || length(c) == B || error("tfhe_mi355x: cst must have one entry per row")
+    s = sel === nothing ? nothing : Int32.(collect(sel) .- 1)
+    s === nothing || length(s) == p.lwe_size || error("tfhe_mi355x: sel must have one entry per step (n)")
+    out_form == 0 || out_form == 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 into TLWE slots, 2 key-switched into wires)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    os = out_slot === nothing ? nothing : Int32.(collect(out_slot) .- 1)
+    ow = out_wires === nothing ? nothing : Int32.(collect(out_wires) .- 1)
+    out_form != 0 || (os !== nothing && length(os) == B) || error("tfhe_mi355x: out_slot must have one entry per row with out_form 0")
+    out_form != 2 || (ow !== nothing && length(ow) == n_out * B) || error("tfhe_mi355x: out_wires must have n_out * B entries with out_form 2")
+    GC.@preserve acc start tw tc c s os ow @locked gck.ctx check(gck.ctx, ccall((:tfhe_blind_rotate_level, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Int64),
+        gck.ctx, acc, start, tw, tc, c === nothing ? Ptr{Int32}(C_NULL) : pointer(c), s === nothing ? Ptr{Int32}(C_NULL) : pointer(s), Int32(n_out),
+        Int32(out_form), os === nothing ? Ptr{Int32}(C_NULL) : pointer(os), ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
+    gck
 end
 
 # page-locked Int32 matrix (tfhe_host_alloc): the copies of a streamed batch are then single DMA transfers that overlap kernels

@@ -28,7 +28,8 @@ ABI_SYMBOLS = [
     "tfhe_tgsw_load", "tfhe_extern_mul_batch", "tfhe_cmux_tree_batch", "tfhe_cmux_net_batch",
     "tfhe_mk_tgsw_load", "tfhe_mk_tgsw_expand_load", "tfhe_mk_extern_mul_batch", "tfhe_mk_cmux_tree_batch",
     "tfhe_mk_cmux_net_batch", "tfhe_rot_net_batch", "tfhe_mk_rot_net_batch", "tfhe_blind_rotate_batch",
-    "tfhe_mk_blind_rotate_batch",
+    "tfhe_mk_blind_rotate_batch", "tfhe_tlwe_alloc", "tfhe_tlwe_upload", "tfhe_tlwe_download", "tfhe_tgsw_update",
+    "tfhe_rot_net_level", "tfhe_blind_rotate_level",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -170,6 +171,13 @@ def load():
         lib.tfhe_blind_rotate_batch.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, i32, vp, i64, i32]
     if hasattr(lib, "tfhe_mk_blind_rotate_batch"):
         lib.tfhe_mk_blind_rotate_batch.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, i32, vp, i64, i32]
+    if hasattr(lib, "tfhe_tlwe_alloc"):
+        lib.tfhe_tlwe_alloc.argtypes = [vp, i64]
+        lib.tfhe_tlwe_upload.argtypes = [vp, i64, i64, vp]
+        lib.tfhe_tlwe_download.argtypes = [vp, i64, i64, vp]
+        lib.tfhe_tgsw_update.argtypes = [vp, vp, i64, i64]
+        lib.tfhe_rot_net_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, i64, vp, i64]
+        lib.tfhe_blind_rotate_level.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -565,6 +573,94 @@ class Engine:
         self._check(self._lib.tfhe_blind_rotate_batch(self._h, _ptr(a), a.shape[0], _ptr(idx), _ptr(r), steps, int(in_form), _ptr(s), n_out, _ptr(out), B,
                                                       int(out_form)))
         return out
+
+    # ---- leveled mode on device-resident tables: the TLWE table beside the wire table, levels that read and write both ----
+    def tlwe_alloc(self, slots):
+        """A device table of TLWE samples int32 [slots][k+1][N] (tfhe_tlwe_alloc); 0 frees it, reallocating discards the contents."""
+        self._check(self._lib.tfhe_tlwe_alloc(self._h, int(slots)))
+
+    def tlwe_upload(self, first, samples):
+        """samples int32 [count][k+1][N] into slots [first, first + count) (tfhe_tlwe_upload), behind the levels queued so far."""
+        m = _i32c(samples)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[1:] != (self.k + 1, self.N):
+            raise ValueError(f"TLWE samples must be [count][{self.k + 1}][{self.N}], got {m.shape}")
+        self._check(self._lib.tfhe_tlwe_upload(self._h, int(first), m.shape[0], _ptr(m)))
+
+    def tlwe_download(self, first, count):
+        """Slots [first, first + count) as int32 [count][k+1][N] (tfhe_tlwe_download), behind the levels queued so far."""
+        out = np.empty((max(int(count), 0), self.k + 1, self.N), np.int32)
+        self._check(self._lib.tfhe_tlwe_download(self._h, int(first), int(count), _ptr(out)))
+        return out
+
+    def tgsw_update(self, first, tgsw):
+        """Replaces selectors [first, first + count) of the loaded set in place (tfhe_tgsw_update): tgsw int32 [count][l][k+1][k+1][N];
+        every other selector keeps its words."""
+        t = _i32c(tgsw)
+        per = self.params.bs_decomp_length * (self.k + 1) ** 2 * self.N
+        if t.size == 0 or t.size % per:
+            raise ValueError(f"TGSW samples have {t.size} words, expected a positive multiple of {per}")
+        self._check(self._lib.tfhe_tgsw_update(self._h, _ptr(t), int(first), t.size // per))
+
+    def rot_net_level(self, net, sel, table_first=None, out_form=2, out_first=0, out_wires=None):
+        """rot_net between the tables (tfhe_rot_net_level).  net: a leveled.RotNet, or a leveled.CmuxNet (its rotation-0 case);
+        sel: int32 [B][V]; level 0 of row g reads source src at TLWE slot table_first[g] + src (None: absolute slots).  out_form 0:
+        output node i of row g goes to slot out_first + g F + i; out_form 2: keyswitched, to wire out_wires[g F + i].  Synchronous."""
+        nodes = _i32c(net.nodes)
+        if nodes.shape[1] == 3:      # a CmuxNet: every rotation 0
+            nodes = np.ascontiguousarray(np.concatenate([nodes, np.zeros((nodes.shape[0], 2), np.int32)], axis=1))
+        elif getattr(net, "degree", None) != self.N:
+            raise ValueError(f"the network's rotations are taken mod 2 * {getattr(net, 'degree', None)}, the engine's polynomials have {self.N} coefficients")
+        sel = _i32c(np.atleast_2d(sel))
+        B, V = sel.shape
+        if V < net.variables:
+            raise ValueError(f"the network reads variable {net.variables - 1}, sel has {V} per row")
+        first = None
+        if table_first is not None:
+            first = _i32c(table_first).reshape(-1)
+            if first.size != B:
+                raise ValueError(f"table_first must have one entry per row ({B}), got {first.size}")
+        F = int(net.widths[-1])
+        ow = None
+        if out_wires is not None:
+            ow = _i32c(out_wires).reshape(-1)
+            if ow.size != B * F:
+                raise ValueError(f"out_wires must have B F = {B * F} entries, got {ow.size}")
+        self._check(self._lib.tfhe_rot_net_level(self._h, _ptr(first), net.entries, _ptr(net.widths), net.levels, _ptr(nodes), _ptr(sel), V,
+                                                 int(out_form), int(out_first), _ptr(ow), B))
+
+    def blind_rotate_level(self, acc_slot, term_start, term_wire, term_coef, cst=None, sel=None, n_out=1, out_form=2, out_slot=None, out_wires=None):
+        """blind_rotate between the tables (tfhe_blind_rotate_level).  Row g rotates the sample in TLWE slot acc_slot[g] by lut_level's
+        combination of wires (term_start [B+1], term_wire, term_coef, cst) over the context's n steps; sel: int32 [n] or None.  out_form
+        0: the final accumulator goes to slot out_slot[g]; out_form 2: the n_out extractions, keyswitched, to wires
+        out_wires[g n_out + j].  Synchronous."""
+        acc = _i32c(acc_slot).reshape(-1)
+        start = _i32c(term_start).reshape(-1)
+        B = acc.size
+        if start.size != B + 1:
+            raise ValueError(f"term_start must have B + 1 = {B + 1} entries, got {start.size}")
+        T = int(start[-1])
+        wire, coef = _i32c(term_wire).reshape(-1), _i32c(term_coef).reshape(-1)
+        if wire.size != coef.size or wire.size < T:
+            raise ValueError(f"term_wire / term_coef must have term_start[B] = {T} entries, got {wire.size} / {coef.size}")
+        c = None if cst is None else _i32c(cst).reshape(-1)
+        if c is not None and c.size != B:
+            raise ValueError(f"cst must have one entry per row ({B}), got {c.size}")
+        s = None
+        if sel is not None:
+            s = _i32c(sel).reshape(-1)
+            if s.size != self.n:
+                raise ValueError(f"sel must have one entry per step ({self.n}), got {s.size}")
+        n_out = int(n_out)
+        os_ = None if out_slot is None else _i32c(out_slot).reshape(-1)
+        if os_ is not None and os_.size != B:
+            raise ValueError(f"out_slot must have one entry per row ({B}), got {os_.size}")
+        ow = None if out_wires is None else _i32c(out_wires).reshape(-1)
+        if ow is not None and ow.size != B * max(n_out, 1):
+            raise ValueError(f"out_wires must have B n_out = {B * max(n_out, 1)} entries, got {ow.size}")
+        self._check(self._lib.tfhe_blind_rotate_level(self._h, _ptr(acc), _ptr(start), _ptr(wire), _ptr(coef), _ptr(c), _ptr(s), n_out, int(out_form),
+                                                      _ptr(os_), _ptr(ow), B))
 
     # ---- leveled mode under a multi-key cloud key: expanded RGSW selectors, MK TLWE samples [P+1][N] ----
     def mk_tgsw_load(self, tgsw, party_of):

@@ -12,17 +12,39 @@ from one rotation, `linear(terms)` the combination itself.  A term is a wire or 
 added to the body.  Linear nodes are folded into the terms of whatever reads them through a LUT or another linear node (coefficients
 multiplied, constants summed mod 2^32), so a LUT never waits a level for one; a linear node is computed (tfhe_linear_level) only if
 a gate reads it or it is an output.  A level runs as one tfhe_gates_level, one tfhe_lut_level per distinct K and one
-tfhe_linear_level, all on the context's stream.  The caller chooses the coefficients: their noise growth is not checked."""
+tfhe_linear_level, all on the context's stream.  The caller chooses the coefficients: their noise growth is not checked.
+
+TLWE-valued nodes bring the leveled half into the same circuit (single-key, one-device): `tlwe_inputs(count)` are TLWE samples the caller
+supplies to run(..., tlwe_inputs=...), `rot_net(net, entries, selectors)` a CMUX network (a leveled.RotNet, or a CmuxNet / tree_net as its
+rotation-0 case) over E TLWE nodes, `blind_rotate(acc, terms)` the blind rotation of a TLWE node by the integer combination of wires that
+a LUT would rotate its table by.  Either leaves TLWE nodes (out="tlwe") or, extracted and keyswitched, ordinary wires (out="lwe").  The
+planner gives TLWE nodes slots of the engine's TLWE table as wires get rows of the wire table and levels them with the gate, LUT and
+linear nodes; a level issues one tfhe_blind_rotate_level per (n_out, out, sel) and one tfhe_rot_net_level per network node.  The
+selectors are indices into the engine's loaded set: loading it (Engine.tgsw_load: the bootstrapping key's n selectors for the rotations'
+sel=None, address-bit selectors behind them; Engine.tgsw_update swaps those per request) stays the caller's job."""
 import numbers
 
 import numpy as np
 
 from ._lib import OPCODES
+from types import SimpleNamespace
+
 from .numeric import wrap32
 from .lwe import LweSample, LweSampleArray
 from .mk_keys import MKCloudKey, MKLweSample
 
 _ARITY = {"NOT": 1, "COPY": 1, "CONST0": 0, "CONST1": 0, "MUX": 3}
+
+
+class TlweNode:
+    """A TLWE-valued node of a Circuit: slot `slot` of the engine's TLWE table while the circuit runs."""
+    __slots__ = ("slot",)
+
+    def __init__(self, slot):
+        self.slot = slot
+
+    def __repr__(self):
+        return f"TlweNode({self.slot})"
 
 
 class Circuit:
@@ -34,6 +56,10 @@ class Circuit:
         self._gate_wire = []      # output wire of gate g
         self._linear = {}         # wire -> ({base wire: coefficient mod 2^32}, constant mod 2^32), terms folded to non-linear wires
         self._luts = []           # (table key, K, terms {base wire: coefficient}, constant, [output wires])
+        self._tlwe_level = []     # level per TLWE slot (inputs: 0)
+        self._n_tlwe_inputs = 0
+        self._rot_nets = []       # (level, E, widths, nodes [..][5] with absolute level-0 sources, selectors [V], out_form, first out slot, [output wires])
+        self._rotations = []      # (level, acc slot, terms, constant, n_out, out_form, sel tuple or None, out slot, [output wires])
 
     # ---- building -----------------------------------------------------------------------------------
     def input(self):
@@ -119,6 +145,80 @@ class Circuit:
             raise ValueError("lut_multi takes callables")
         return self._add_lut(("multi", fs, p, q), K, terms, const)
 
+    # ---- TLWE-valued nodes --------------------------------------------------------------------------
+    def tlwe_inputs(self, count):
+        """`count` TLWE samples supplied to run(..., tlwe_inputs=...): the first slots of the TLWE table, in order."""
+        if len(self._tlwe_level) != self._n_tlwe_inputs:
+            raise ValueError("declare all TLWE inputs before the first TLWE-valued node")
+        first = self._n_tlwe_inputs
+        self._n_tlwe_inputs += int(count)
+        self._tlwe_level += [0] * int(count)
+        return [TlweNode(first + i) for i in range(int(count))]
+
+    def _check_tlwe(self, t):
+        if not isinstance(t, TlweNode) or not 0 <= t.slot < len(self._tlwe_level):
+            raise ValueError(f"{t!r} is not a TLWE node of this circuit")
+        return t.slot
+
+    @staticmethod
+    def _out_form(out):
+        if out not in ("lwe", "tlwe"):
+            raise ValueError(f"out = {out!r}: 'lwe' (wires) or 'tlwe' (TLWE nodes)")
+        return 2 if out == "lwe" else 0
+
+    def _new_tlwe(self, level, count):
+        first = len(self._tlwe_level)
+        self._tlwe_level += [level] * count
+        return first
+
+    def rot_net(self, net, entries, selectors, out="lwe"):
+        """The F outputs of the CMUX network `net` (leveled.RotNet; a CmuxNet or tree_net is its rotation-0 case) over the E TLWE nodes
+        `entries`, variable v selected by selector `selectors[v]` of the engine's loaded set: F wires (out="lwe": extracted at
+        coefficient 0 and keyswitched) or F TLWE nodes (out="tlwe")."""
+        form = self._out_form(out)
+        slots = [self._check_tlwe(t) for t in entries]
+        if len(slots) != net.entries:
+            raise ValueError(f"the network reads {net.entries} entries, got {len(slots)}")
+        sel = [int(v) for v in selectors]
+        if len(sel) != net.variables or any(v < 0 for v in sel):
+            raise ValueError(f"the network has {net.variables} variables, got {len(sel)} selector indices (each >= 0)")
+        nodes = np.asarray(net.nodes, np.int32)
+        if nodes.shape[1] == 3:
+            nodes = np.concatenate([nodes, np.zeros((nodes.shape[0], 2), np.int32)], axis=1)
+        nodes = np.ascontiguousarray(nodes).copy()
+        w0 = int(net.widths[0])
+        nodes[:w0, 0] = np.asarray(slots, np.int32)[nodes[:w0, 0]]          # level 0 reads absolute slots (table_first NULL)
+        nodes[:w0, 1] = np.asarray(slots, np.int32)[nodes[:w0, 1]]
+        level = 1 + max(self._tlwe_level[s] for s in slots)
+        F = int(net.widths[-1])
+        first = self._new_tlwe(level, F) if form == 0 else -1
+        wires = [self._new_wire(level) for _ in range(F)] if form == 2 else []
+        self._rot_nets.append((level, max(slots) + 1, np.asarray(net.widths, np.int32), nodes, sel, form, first, wires, getattr(net, "degree", None)))
+        return wires if form == 2 else [TlweNode(first + i) for i in range(F)]
+
+    def blind_rotate(self, acc, terms, const=0, n_out=1, out="lwe", sel=None):
+        """The TLWE node `acc` rotated by the combination of `terms` + const (as lut's; the context's n steps, selector sel[i] — None: i
+        — of the engine's loaded set for step i): one TLWE node (out="tlwe", n_out 1) or the n_out extractions at the coefficients
+        j N / n_out, keyswitched, as wires (out="lwe"; n_out = 1: one wire, else a list)."""
+        form = self._out_form(out)
+        slot = self._check_tlwe(acc)
+        n_out = int(n_out)
+        if n_out < 1 or n_out > 32 or n_out & (n_out - 1) or (form == 0 and n_out != 1):
+            raise ValueError(f"n_out = {n_out}: a power of two, 1 ... 32, and 1 with out='tlwe'")
+        folded, cst = self._fold(terms, const)
+        level = 1 + max([self._level[b] for b in folded] + [self._tlwe_level[slot]])
+        key = None if sel is None else tuple(int(v) for v in sel)
+        first = self._new_tlwe(level, 1) if form == 0 else -1
+        wires = [self._new_wire(level) for _ in range(n_out)] if form == 2 else []
+        self._rotations.append((level, slot, folded, cst, n_out, form, key, first, wires))
+        if form == 0:
+            return TlweNode(first)
+        return wires[0] if n_out == 1 else wires
+
+    @property
+    def num_tlwe(self):
+        return len(self._tlwe_level)
+
     def gate(self, name, *operands):
         name = name.upper()
         if name not in OPCODES:
@@ -165,7 +265,7 @@ class Circuit:
     def levels(self):
         """List of levels; each level is a list of gate indices (gate g drives wire gate_wire(g): n_inputs + g in a circuit of
         gates only)."""
-        depth = max(self._level, default=0)
+        depth = max(self._level + self._tlwe_level, default=0)
         out = [[] for _ in range(depth)]
         for g in range(len(self._gates)):
             out[self._level[self._gate_wire[g]] - 1].append(g)
@@ -244,6 +344,23 @@ class Circuit:
             lin = [(t, cst, [w]) for w, (t, cst) in self._linear.items()
                    if self._level[w] == level and (w in read_by_gate or w in outputs)]
             plan.append({"gates": gates, "lut": luts, "linear": rows(lin, 1) if lin else None})
+            if self._tlwe_level:
+                if M != 1:
+                    raise ValueError("a circuit with TLWE nodes runs one instance at a time (run, not run_batch)")
+                groups = {}
+                for r in self._rotations:
+                    if r[0] == level:
+                        groups.setdefault((r[4], r[5], r[6]), []).append(r)
+                rot = []
+                for (n_out, form, sel), rs in groups.items():
+                    start, wire, coef, cst, _ = rows([(r[2], r[3], [0]) for r in rs], 1)
+                    rot.append((np.array([r[1] for r in rs], np.int32), start, wire, coef, cst, None if sel is None else np.array(sel, np.int32), n_out, form,
+                                np.array([r[7] for r in rs], np.int32) if form == 0 else None,
+                                np.array([w for r in rs for w in r[8]], np.int32) if form == 2 else None))
+                nets = [(SimpleNamespace(entries=E, widths=widths, levels=int(widths.size), nodes=nodes, variables=len(sel), degree=N if degree is None else degree),
+                         np.array([sel], np.int32), form, max(first, 0), np.array(wires, np.int32) if form == 2 else None)
+                        for (lv, E, widths, nodes, sel, form, first, wires, degree) in self._rot_nets if lv == level]
+                plan[-1]["blind_rotate"], plan[-1]["rot_net"] = rot, nets
         return plan
 
     def _run_plan(self, eng, plan, mk):
@@ -257,16 +374,30 @@ class Circuit:
                 lut_level(tv, start, wire, coef, cst, out, index=index, n_out=K)
             if lv["linear"] is not None:
                 linear_level(*lv["linear"])
+            for acc, start, wire, coef, cst, sel, n_out, form, out_slot, out_wires in lv.get("blind_rotate", ()):
+                eng.blind_rotate_level(acc, start, wire, coef, cst=cst, sel=sel, n_out=n_out, out_form=form, out_slot=out_slot, out_wires=out_wires)
+            for net, sel, form, out_first, out_wires in lv.get("rot_net", ()):
+                eng.rot_net_level(net, sel, out_form=form, out_first=out_first, out_wires=out_wires)
 
     # ---- execution ----------------------------------------------------------------------------------
-    def run(self, ck, inputs, device=0):
+    def run(self, ck, inputs, device=0, tlwe_inputs=None):
         """inputs: LweSampleArray / list of LweSample / int32 [n_inputs][n+1].  Returns an LweSampleArray
         of the output wires.  Everything between upload and download runs on the GPU.
         Under an MKCloudKey: inputs int32 [n_inputs][P*n+1] (or a list of flat samples / MKLweSample), result int32
         [n_outputs][P*n+1]; the levels run on a multi-key wire table (tfhe_mk_wires_alloc, tfhe_mk_gates_level, tfhe_mk_lut_level,
-        tfhe_mk_linear_level)."""
-        eng = ck.engine(device)
+        tfhe_mk_linear_level).
+        A circuit with TLWE nodes (single-key only) also takes tlwe_inputs, int32 [tlwe input count][k+1][N], into the first slots of a
+        TLWE table of num_tlwe slots; the engine's selector set must be loaded (see the module's text)."""
         mk = isinstance(ck, MKCloudKey)
+        if self._tlwe_level and mk:
+            raise ValueError("a circuit with TLWE nodes runs under a single-key CloudKey (the TLWE table is single-key)")
+        eng = ck.engine(device)
+        if self._tlwe_level:
+            t = np.zeros((0, eng.k + 1, eng.N), np.int32) if tlwe_inputs is None else np.asarray(tlwe_inputs, np.int32)
+            if t.ndim != 3 or t.shape[0] != self._n_tlwe_inputs:
+                raise ValueError(f"circuit has {self._n_tlwe_inputs} TLWE inputs [k+1][N], got shape {t.shape}")
+        elif tlwe_inputs is not None:
+            raise ValueError("the circuit has no TLWE nodes")
         if isinstance(inputs, LweSampleArray):
             m = inputs.data
         elif isinstance(inputs, (list, tuple)):
@@ -279,6 +410,10 @@ class Circuit:
         if self._n_inputs:
             eng.wires_upload(0, m)
         plan = self.level_plan(eng.N)
+        if self._tlwe_level:
+            eng.tlwe_alloc(self.num_tlwe)
+            if self._n_tlwe_inputs:
+                eng.tlwe_upload(0, t)
         # no per-phase timing events while the levels run: each record keeps the stream's next kernel waiting ~5 us, and a level
         # of a narrow circuit is six short operations around one single-rotation kernel (tutorial circuit: 30.5 -> 30.1 ms)
         timing_before = eng.get_option("timing_events")              # (the engine is shared through ck.engine(): put the caller's setting back)
@@ -297,6 +432,8 @@ class Circuit:
         (rotations of the widest level) instances cost what one does; beyond that the levels run at batch throughput.
         Wire w of instance i is row w * M + i of the wire table: the inputs go up as one block, the outputs come down as one gather.
         Under an MKCloudKey the rows are multi-key samples: inputs [M][n_inputs][P*n+1], result [M][n_outputs][P*n+1]."""
+        if self._tlwe_level:
+            raise ValueError("a circuit with TLWE nodes runs one instance at a time (run, not run_batch)")
         eng = ck.engine(device)
         mk = isinstance(ck, MKCloudKey)
         if isinstance(inputs, (list, tuple)):

@@ -20,6 +20,8 @@
 //   engine_mk_rot_net.hip   the same networks with monomial edges under a multi-key cloud key                          ("mk rot net")
 //   engine_blind_rotate.hip   the blind rotation of the caller's TLWE accumulators by LWE samples, on the caller's selectors  ("blind rotate")
 //   engine_mk_blind_rotate.hip   the same rotation of MK TLWE accumulators under a multi-key cloud key                  ("mk blind rotate")
+//   engine_tlwe_levels.hip    the device-resident TLWE table and the blind rotation between it and the wire table (tfhe_tlwe_*, tfhe_blind_rotate_level;
+//                             tfhe_rot_net_level is engine_rot_net.hip's, tfhe_tgsw_update engine_keys.hip's)              ("tlwe levels")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
 //   leveled_run.hpp       host-only: the one runner behind the eleven leveled entry points (workspaces, uploads, level loop, download)
 //   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share
@@ -207,6 +209,9 @@ struct tfhe_ctx {
     int32_t *d_wires = nullptr; int64_t num_wires = 0;
     int wires_parties = 0;
     size_t wire_words() const { return wires_parties ? (size_t)wires_parties * P.n + 1 : (size_t)P.n + 1; }
+    // device-resident TLWE table of the leveled half (tfhe_tlwe_alloc, engine_tlwe_levels.hip): int32 [tlwe_slots][k+1][N], single-key,
+    // one-device contexts only; tfhe_rot_net_level and tfhe_blind_rotate_level read and write it
+    int32_t *d_tlwe = nullptr; int64_t tlwe_slots = 0;
 
     // workspaces
     DevBuf bara, ext, map, io[4], diag, abar, mk_acc, spec;

@@ -322,6 +322,42 @@ int32_t tfhe_tgsw_load(tfhe_ctx *c, const int32_t *tgsw, int64_t S) try
 }
 ABI_CATCH(c, "tfhe_tgsw_load")
 
+// selectors [first, first + count) of the loaded set replaced in place, every other selector's words untouched: the key's n selectors
+// are loaded once and a request's address-bit selectors are swapped behind them
+int32_t tfhe_tgsw_update(tfhe_ctx *c, const int32_t *tgsw, int64_t first, int64_t count) try
+{
+    ENTER_CTX(c);
+    if (c->P.parties != 1) return c->set_err(TFHE_ERR_STATE, "tgsw_update: context is multi-key (leveled operations are single-key)");
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "tgsw_update: multi-device context (leveled operations run on a one-device context)");
+    if (!tgsw) return c->set_err(TFHE_ERR_INVALID_ARG, "tgsw_update: NULL pointer");
+    if (count < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "tgsw_update: count = %lld (at least one selector)", (long long)count);
+    if (!c->d_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "tgsw_update: no selector set loaded (tfhe_tgsw_load)");
+    if (first < 0 || first >= c->tgsw_count || count > c->tgsw_count - first)
+        return c->set_err(TFHE_ERR_INVALID_ARG, "tgsw_update: selectors [%lld, %lld + %lld) are outside the %lld loaded ones", (long long)first, (long long)first,
+                          (long long)count, (long long)c->tgsw_count);
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int32_t rcp = check_key_source(c, tgsw, "tgsw_update"); if (rcp) return rcp; }
+    const size_t per = (size_t)c->P.bs_l * (c->P.k + 1) * (c->P.k + 1);
+    const size_t npolys = (size_t)count * per, M = (size_t)(c->P.N / 2 > 0 ? c->P.N / 2 : 1), bytes_in = npolys * (size_t)c->P.N * 4;
+    quiesce(c);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+    if ((double)bytes_in > (double)free_b)
+        return c->set_err(TFHE_ERR_NOMEM, "tgsw_update: the staging of %lld samples does not fit the device's free memory", (long long)count);
+    void *d_in = nullptr;
+    hipError_t e = hipMalloc(&d_in, bytes_in);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, tgsw, bytes_in, hipMemcpyDefault, c->stream);
+    int32_t rc = TFHE_OK;
+    if (e == hipSuccess) rc = tgsw_prepare(c, (const int32_t *)d_in, c->d_tgsw + (size_t)first * per * M, npolys, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on failure: d_in is freed below)
+    if (e == hipSuccess) e = es;
+    if (d_in) (void)hipFree(d_in);
+    if (rc) return rc;
+    if (e != hipSuccess) return c->set_err(TFHE_ERR_DEVICE, "tgsw_update: %s", hipGetErrorString(e));
+    return TFHE_OK;
+}
+ABI_CATCH(c, "tfhe_tgsw_update")
+
 static int32_t mk_load_bk_common(tfhe_ctx *c, const void *bk, int32_t parties, bool is_c128)
 {
     ENTER_CTX(c);

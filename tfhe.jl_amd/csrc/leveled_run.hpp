@@ -1,7 +1,8 @@
 // leveled_run.hpp — host-only: the one runner behind the leveled entry points (engine_leveled.hip, engine_mk_leveled.hip,
 // engine_cmux_net.hip, engine_rot_net.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip).  An entry point validates its arguments, describes the call in a
 // LevelPlan and names its kernel; the workspace protocol, the uploads, the level loop, the keyswitch, the download and the timing are
-// here and nowhere else.
+// here and nowhere else.  tfhe_rot_net_level runs through it too: its sources and destinations are the device-resident TLWE and wire tables
+// (LevelPlan's d_* fields), so nothing is uploaded but the maps and nothing is downloaded.
 #pragma once
 #include "engine.hpp"
 #include "kernels_leveled_core.hpp"
@@ -31,6 +32,13 @@ struct LevelPlan {
     int64_t B;
     int32_t *out;             // host, by out_form 0: the samples [B F][polys][N], 1: extracted at coefficient 0 [B F][ext_w], 2: that
     int32_t out_form;         //   keyswitched [B F][ks_w] (launch_keyswitch with identity maps)
+    // device-resident sources and destinations (tfhe_rot_net_level; all NULL for the host-buffer calls above):
+    const int32_t *d_data;    // level 0 reads this device table instead of an upload of `data` (`data` NULL): row g's E samples at
+                              //   d_data[row_index[g]] with `data_row_words` words between two indices (0: E samples)
+    int64_t data_row_words;
+    int32_t *d_out;           // out_form 0: the last level writes its B F samples here, nothing is downloaded (`out` NULL)
+    const int32_t *dst_rows;  // out_form 2: host [B F], the row of `d_ks_out` each keyswitched sample goes to (launch_keyswitch's dst
+    int32_t *d_ks_out;        //   map), nothing is downloaded (`out` NULL)
 };
 
 // KERNEL takes A, one of the argument structs on leveled::LevelArgs; set(a, lv, d_nodes) fills the fields A adds to it, with d_nodes the
@@ -54,16 +62,17 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
     const bool fits = leveled::lds_bytes(N, p.nspec) <= 160 * 1024;
     const bool spec_lds = c->anyn_spec < 0 ? fits : (c->anyn_spec == 0 && fits);      // option anyn_spec: 1 = accumulators in global memory
     auto up = [](size_t words) { return (words + 63) / 64 * 64; };
-    // e0 [B F] (the keyswitch's identity map) | row_index [B] | sel [B][V] | nodes [total][words]
-    const size_t o_idx = up(G), o_sel = o_idx + up(B_), o_nodes = o_sel + up(B_ * (size_t)p.V), map_bytes = (o_nodes + p.words * total_nodes) * 4;
-    const size_t data_bytes = (size_t)p.T * (size_t)p.E * sample * 4;
+    // e0 [B F] (the keyswitch's identity map) | row_index [B] | sel [B][V] | nodes [total][words] | dst_rows [B F] (if any)
+    const size_t o_idx = up(G), o_sel = o_idx + up(B_), o_nodes = o_sel + up(B_ * (size_t)p.V);
+    const size_t o_dst = p.dst_rows ? o_nodes + up(p.words * total_nodes) : 0, map_bytes = p.dst_rows ? (o_dst + G) * 4 : (o_nodes + p.words * total_nodes) * 4;
+    const size_t data_bytes = p.d_data ? 0 : (size_t)p.T * (size_t)p.E * sample * 4;
     const LvlWant want[] = {
         {&c->lvl_data, data_bytes},
         {&c->lvl_ws[0], B_ * wmax[0] * sample * 4},
         {&c->lvl_ws[1], B_ * wmax[1] * sample * 4},
         {&c->lvl_spec, spec_lds ? 0 : B_ * wall * p.nspec * M * sizeof(cplx)},
         {&c->ext, p.out_form >= 1 ? G * p.ext_w * 4 : 0},
-        {&c->io[3], p.out_form == 2 ? G * p.ks_w * 4 : 0},
+        {&c->io[3], p.out_form == 2 && !p.d_ks_out ? G * p.ks_w * 4 : 0},
         {&c->map, map_bytes},
     };
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }       // (the workspaces may still be in use by a call on another stream)
@@ -80,8 +89,9 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
     else for (size_t g = 0; g < B_; g++) h[o_idx + g] = p.row_default_g ? (int32_t)g : 0;
     memcpy(h + o_sel, p.sel, B_ * (size_t)p.V * 4);
     if (p.words) memcpy(h + o_nodes, p.nodes, p.words * total_nodes * 4);
+    if (p.dst_rows) memcpy(h + o_dst, p.dst_rows, G * 4);
     HIP_TRY(c, hipMemcpyAsync(c->map.p, c->h_map, map_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->lvl_data.p, p.data, data_bytes, hipMemcpyHostToDevice, s));
+    if (!p.d_data) HIP_TRY(c, hipMemcpyAsync(c->lvl_data.p, p.data, data_bytes, hipMemcpyHostToDevice, s));
     const int32_t *d_map = (const int32_t *)c->map.p;
 
     A a;
@@ -105,11 +115,11 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
     for (int lv = 0; lv < p.levels; lv++) {
         const size_t w = (size_t)p.widths[lv];
         const bool last = lv == p.levels - 1;
-        a.in = lv == 0 ? (const int32_t *)c->lvl_data.p : (const int32_t *)c->lvl_ws[(lv - 1) & 1].p;
+        a.in = lv == 0 ? (p.d_data ? p.d_data : (const int32_t *)c->lvl_data.p) : (const int32_t *)c->lvl_ws[(lv - 1) & 1].p;
         a.row_index = lv == 0 ? d_map + o_idx : nullptr;
-        a.row_words = (int64_t)((lv == 0 ? (size_t)p.E : (size_t)p.widths[lv - 1]) * sample);
+        a.row_words = lv == 0 && p.d_data && p.data_row_words ? p.data_row_words : (int64_t)((lv == 0 ? (size_t)p.E : (size_t)p.widths[lv - 1]) * sample);
         a.nodes_out = (int32_t)w;
-        a.out = last && p.out_form != 0 ? nullptr : (int32_t *)c->lvl_ws[lv & 1].p;
+        a.out = last && p.out_form != 0 ? nullptr : last && p.d_out ? p.d_out : (int32_t *)c->lvl_ws[lv & 1].p;
         a.ext = last && p.out_form != 0 ? (int32_t *)c->ext.p : nullptr;
         set(a, lv, d_map + o_nodes + p.words * first_node);
         if (last) final_tlwe = a.out;
@@ -119,11 +129,13 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
     }
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
     if (p.out_form == 2) {
-        rc = launch_keyswitch(c, G, d_map, nullptr, nullptr, (const int32_t *)c->ext.p, (int32_t *)c->io[3].p, s);
+        rc = launch_keyswitch(c, G, d_map, nullptr, p.dst_rows ? d_map + o_dst : nullptr, (const int32_t *)c->ext.p,
+                              p.d_ks_out ? p.d_ks_out : (int32_t *)c->io[3].p, s);
         if (rc) return rc;
     }
     HIP_TRY(c, hipEventRecord(c->ev[3], s));
-    if (p.out_form == 0) HIP_TRY(c, hipMemcpyAsync(p.out, final_tlwe, G * sample * 4, hipMemcpyDeviceToHost, s));
+    if (p.out_form == 0 ? p.d_out != nullptr : p.d_ks_out != nullptr) { /* the result stays on the device */ }
+    else if (p.out_form == 0) HIP_TRY(c, hipMemcpyAsync(p.out, final_tlwe, G * sample * 4, hipMemcpyDeviceToHost, s));
     else if (p.out_form == 1) HIP_TRY(c, hipMemcpyAsync(p.out, c->ext.p, G * p.ext_w * 4, hipMemcpyDeviceToHost, s));
     else HIP_TRY(c, hipMemcpyAsync(p.out, c->io[3].p, G * p.ks_w * 4, hipMemcpyDeviceToHost, s));
     rc = leave_stream(c, s);
