@@ -683,6 +683,74 @@ int32_t tfhe_mk_blind_rotate_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T,
                                    int32_t steps, int32_t in_form, const int32_t *sel, int32_t n_out, int32_t *out, int64_t B,
                                    int32_t out_form);
 
+/* ---- multi-key leveled mode on device-resident tables (additions within ABI v7) ---------------------------
+ * The single-key block "leveled mode on device-resident tables" above, under a multi-key cloud key: MK TLWE samples that stay on the
+ * device between leveled calls, an in-place update of the expanded selector set, and two level calls between the MK TLWE table and
+ * the multi-key wire table (tfhe_mk_wires_alloc).  No new cryptography, no new key material: every result equals, word for word,
+ * tfhe_mk_rot_net_batch / tfhe_mk_blind_rotate_batch on the same samples.  P = the parties of the loaded multi-key bootstrapping key;
+ * a sample is int32 [P+1][N], a wire row P n + 1 words.  One-device multi-key contexts only (TFHE_ERR_STATE otherwise; the single-key
+ * calls above keep refusing a multi-key context).
+ *
+ * tfhe_mk_tlwe_alloc: a device table int32 [slots][P+1][N]; slots = 0 frees it; reallocating discards the old contents.  The table
+ * records the party count it was allocated for, as tfhe_mk_wires_alloc does for the wires: TFHE_ERR_NO_KEY without the multi-key
+ * bootstrapping key (it fixes P).  The size is compared with the device's free memory (the table being replaced counted as free)
+ * before anything is freed or allocated: TFHE_ERR_NOMEM, the context and its present table stay as they were.  Waits for the levels
+ * queued on the context.  Freed with the context.
+ * tfhe_mk_tlwe_upload / tfhe_mk_tlwe_download: slots [first, first + count) from / to host int32 [count][P+1][N], ordered behind the
+ * levels queued on the context; both return with the copy done.  TFHE_ERR_STATE without a table, TFHE_ERR_INVALID_ARG for a range
+ * outside it or a NULL buffer with count > 0. */
+int32_t tfhe_mk_tlwe_alloc(tfhe_ctx *ctx, int64_t slots);
+int32_t tfhe_mk_tlwe_upload(tfhe_ctx *ctx, int64_t first, int64_t count, const int32_t *host);
+int32_t tfhe_mk_tlwe_download(tfhe_ctx *ctx, int64_t first, int64_t count, int32_t *host);
+
+/* Replace selectors [first, first + count) of the set tfhe_mk_tgsw_load / tfhe_mk_tgsw_expand_load loaded, in place, spectra and
+ * party_of entries alike: every other selector keeps its exact words, and the replaced ones are what a fresh load of the edited set
+ * would hold.  tfhe_mk_tgsw_update: tgsw is int32 [count][2 l P + 2 l][N] (expanded samples), party_of int32 [count].
+ * tfhe_mk_tgsw_expand_update: the uni-encryptions c0 ... f1, int32 [count][l][N] each, and party_of [count], expanded against pub_b
+ * [P][l][N] with tfhe_mk_tgsw_expand_load's per-party grouping over the count new samples only; expanded_out, if not NULL, receives
+ * int32 [count][2 l P + 2 l][N].  For a set "the key's P n selectors, then a request's address bits": the key is loaded once and the
+ * address bits are swapped behind it.  Both wait for the work queued on the context first.  TFHE_ERR_STATE: a single-key or
+ * multi-device context, parties other than the bootstrapping key's; TFHE_ERR_NO_KEY: no set loaded; TFHE_ERR_INVALID_ARG: a NULL
+ * pointer, count < 1, a range outside [0, S), a party outside [0, P); TFHE_ERR_NOMEM: the staging does not fit the device's free
+ * memory, before anything is allocated. */
+int32_t tfhe_mk_tgsw_update(tfhe_ctx *ctx, const int32_t *tgsw, const int32_t *party_of, int64_t first, int64_t count, int32_t parties);
+int32_t tfhe_mk_tgsw_expand_update(tfhe_ctx *ctx, int32_t parties, const int32_t *pub_b, const int32_t *party_of, const int32_t *c0,
+                                   const int32_t *c1, const int32_t *d0, const int32_t *d1, const int32_t *f0, const int32_t *f1,
+                                   int64_t first, int64_t count, int32_t *expanded_out);
+
+/* tfhe_mk_rot_net_batch between the tables: tfhe_rot_net_level's contract argument for argument, with "slot" an MK TLWE slot, "wire"
+ * a row of the multi-key wire table and the keyswitch the multi-key one.  The words equal tfhe_mk_rot_net_batch on the same samples —
+ * with every rotation 0 that is tfhe_mk_cmux_net_batch, with a tree's netlist tfhe_mk_cmux_tree_batch.  The same kernel
+ * (mk_rot_net_level_kernel), unchanged; timing slots and tfhe_last_kernel_name as tfhe_mk_rot_net_batch.
+ *
+ * tfhe_mk_blind_rotate_batch between the tables: tfhe_blind_rotate_level's contract with steps = P n.  Row g's rotating sample x_g is
+ * tfhe_mk_lut_level's combination of multi-key wire rows (cst NULL: 0; a row without terms is the trivial sample and reads no wire);
+ * A_0 = X^(-barb_g) slot[acc_slot[g]] (slots may repeat); sel: host int32 [P n] or NULL = selector i for step i (the key loaded
+ * party-major).  out_form 0 (n_out must be 1): the final accumulator goes to slot out_slot[g]; the slots must be distinct and none may
+ * be an acc_slot of the same call.  out_form 2: the n_out extractions go through the multi-key keyswitch to wires
+ * out_wires[g n_out + j]; no wire may be named twice and none may be a term wire of the same call.  The words equal
+ * tfhe_mk_blind_rotate_batch(acc = those slots' samples, rows = x_g, steps = P n, in_form 0, sel, n_out, out_form).
+ * tfhe_mk_lut_level's prologue stages the rows (linear_prologue_kernel), then one kernel, one workgroup per row
+ * (csrc/kernels_mk_tlwe_levels.hpp; tfhe_last_kernel_name reports "mk_tlwe_rotate_level_kernel(N=..,P=..,l=..,steps=..[,spec=global])";
+ * "anyn_spec" is honoured); tfhe_last_rotation_count = B; tfhe_last_timing_ms as the batch call.
+ *
+ * Both level calls: everything is validated on the host before anything is uploaded or written, the message names the offender, and
+ * a refused call changes no slot and no wire.  In this order — TFHE_ERR_STATE: a single-key context, a multi-device context,
+ * measure_margin on, no MK TLWE table, no wire table when out_form 2 or terms need one, a wire table with single-key rows, a table,
+ * wire table or keyswitch key whose parties differ from the bootstrapping key's; TFHE_ERR_NO_KEY: no multi-key bootstrapping key;
+ * TFHE_ERR_INVALID_ARG: everything about the arguments, by the single-key calls' slot / wire / overlap rules; TFHE_ERR_NO_KEY: no
+ * selector set, or out_form 2 without the multi-key keyswitch key (a selector index is checked against the loaded set after that).
+ * The workspaces are compared with the device's free memory before anything is allocated (TFHE_ERR_NOMEM, the context stays usable).
+ * B = 0 returns TFHE_OK.  The calls are ordered behind the asynchronous levels queued on the context (tfhe_mk_gates_level,
+ * tfhe_mk_lut_level, ...) and SYNCHRONISE before they return.  Out of scope: multi-device contexts, circuits (Circuit.run keeps
+ * refusing TLWE nodes under a multi-key cloud key). */
+int32_t tfhe_mk_rot_net_level(tfhe_ctx *ctx, const int32_t *table_first, int32_t E, const int32_t *widths, int32_t levels,
+                              const int32_t *nodes, const int32_t *sel, int32_t V, int32_t out_form, int64_t out_first,
+                              const int32_t *out_wires, int64_t B);
+int32_t tfhe_mk_blind_rotate_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,
+                                   const int32_t *term_coef, const int32_t *cst, const int32_t *sel, int32_t n_out, int32_t out_form,
+                                   const int32_t *out_slot, const int32_t *out_wires, int64_t B);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Timing of the most recent batch call on ctx, from HIP events recorded on the stream the kernels

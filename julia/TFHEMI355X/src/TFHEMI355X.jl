@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate, tlwe_alloc!, tlwe_upload!, tlwe_download, tgsw_update!, rot_net_level!, blind_rotate_level!
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate, tlwe_alloc!, tlwe_upload!, tlwe_download, tgsw_update!, rot_net_level!, blind_rotate_level!, mk_tlwe_alloc!, mk_tlwe_upload!, mk_tlwe_download, mk_tgsw_update!, mk_tgsw_expand_update!, mk_rot_net_level!, mk_blind_rotate_level!
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -1180,6 +1180,168 @@ function mk_blind_rotate(mck::GpuMKCloudKey, acc::Array{Int32,3}, rows::Abstract
     out_form == 2 || return out
     params = LweParams(n)
     [MKLweSample(params, reshape(out[1:n*P, r], n, P), out[n * P + 1, r], 0.) for r in 1:n_out*B]
+end
+
+"""
+    mk_tlwe_alloc!(mck, slots)
+
+The device-resident MK TLWE table of the multi-key leveled half (tfhe_mk_tlwe_alloc): `slots` samples of `N x (P+1)` words beside the
+multi-key wire table; 0 frees it, reallocating discards the contents.  `mk_rot_net_level!` and `mk_blind_rotate_level!` read and write
+it; slots are 1-based here.
+"""
+function mk_tlwe_alloc!(mck::GpuMKCloudKey, slots::Integer)
+    slots >= 0 || error("tfhe_mi355x: slots = ", slots, " (at least 0)")
+    @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_tlwe_alloc, LIB), Int32, (Ptr{Cvoid}, Int64), mck.ctx, Int64(slots)))
+    mck
+end
+
+"""
+    mk_tlwe_upload!(mck, first, samples::Array{Int32,3})
+
+`samples`, `N x (P+1) x count`, into slots `first : first + count - 1` (1-based) of the MK TLWE table (tfhe_mk_tlwe_upload), behind the
+levels queued on the context.
+"""
+function mk_tlwe_upload!(mck::GpuMKCloudKey, first::Integer, samples::Array{Int32,3})
+    p, P = mck.params, mck.parties
+    size(samples)[1:2] == (p.tlwe_polynomial_degree, P + 1) || error("tfhe_mi355x: MK TLWE samples must be N x (P+1) x count")
+    first >= 1 || error("tfhe_mi355x: slots are 1-based, first = ", first)
+    GC.@preserve samples @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_tlwe_upload, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Int32}), mck.ctx, Int64(first - 1), Int64(size(samples, 3)), samples))
+    mck
+end
+
+"""
+    mk_tlwe_download(mck, first, count)  ->  Array{Int32,3}
+
+Slots `first : first + count - 1` (1-based) of the MK TLWE table as `N x (P+1) x count` (tfhe_mk_tlwe_download), behind the levels queued
+on the context.
+"""
+function mk_tlwe_download(mck::GpuMKCloudKey, first::Integer, count::Integer)
+    p, P = mck.params, mck.parties
+    first >= 1 && count >= 0 || error("tfhe_mi355x: slots are 1-based and count >= 0, got first = ", first, ", count = ", count)
+    out = Array{Int32}(undef, p.tlwe_polynomial_degree, P + 1, count)
+    GC.@preserve out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_tlwe_download, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Int32}), mck.ctx, Int64(first - 1), Int64(count), out))
+    out
+end
+
+"""
+    mk_tgsw_update!(mck, first, tgsw::Array{Int32}, party_of)
+
+Replaces selectors `first : first + count - 1` (1-based) of the set `mk_tgsw_load!` loaded, in place, spectra and parties alike
+(tfhe_mk_tgsw_update); `tgsw` and `party_of` (1-based) as in `mk_tgsw_load!`.  Every other selector keeps its words: the key's `P n`
+selectors are loaded once, a request's address bits swapped behind them.
+"""
+function mk_tgsw_update!(mck::GpuMKCloudKey, first::Integer, tgsw::Array{Int32}, party_of)
+    p, P = mck.params, mck.parties
+    per = p.tlwe_polynomial_degree * (2 * p.bs_decomp_length * P + 2 * p.bs_decomp_length)
+    who = Int32.(collect(party_of) .- 1)
+    (length(who) > 0 && length(tgsw) == per * length(who)) || error("tfhe_mi355x: expanded samples must hold ", per, " words for each entry of party_of")
+    first >= 1 || error("tfhe_mi355x: selectors are 1-based, first = ", first)
+    GC.@preserve tgsw who @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_tgsw_update, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int64, Int64, Int32), mck.ctx, tgsw, who, Int64(first - 1), Int64(length(who)), Int32(P)))
+    mck
+end
+
+"""
+    mk_tgsw_expand_update!(mck, first, pub_b, party_of, c0, c1, d0, d1, f0, f1)
+
+The same update from what the parties publish (tfhe_mk_tgsw_expand_update): `pub_b` is Int32 `N x l x P`, the public keys; `c0 ... f1`
+are Int32 `N x l x count`, sample `s` uni-encrypted (`mk_tgsw_encrypt`, src/mk_internals.jl:185-227) by party `party_of[s]` (1-based).
+RGSW.Expand (:304-345) runs on the device over the `count` new samples only.
+"""
+function mk_tgsw_expand_update!(mck::GpuMKCloudKey, first::Integer, pub_b::Array{Int32,3}, party_of, c0::Array{Int32,3}, c1::Array{Int32,3},
+                                d0::Array{Int32,3}, d1::Array{Int32,3}, f0::Array{Int32,3}, f1::Array{Int32,3})
+    p, P = mck.params, mck.parties
+    N, l = p.tlwe_polynomial_degree, p.bs_decomp_length
+    who = Int32.(collect(party_of) .- 1)
+    count = length(who)
+    count >= 1 || error("tfhe_mi355x: at least one selector")
+    size(pub_b) == (N, l, P) || error("tfhe_mi355x: public keys must be N x l x P")
+    all(a -> size(a) == (N, l, count), (c0, c1, d0, d1, f0, f1)) || error("tfhe_mi355x: uni-encryption arrays must be N x l x count")
+    first >= 1 || error("tfhe_mi355x: selectors are 1-based, first = ", first)
+    GC.@preserve pub_b who c0 c1 d0 d1 f0 f1 @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_tgsw_expand_update, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Int64, Ptr{Int32}),
+        mck.ctx, Int32(P), pub_b, who, c0, c1, d0, d1, f0, f1, Int64(first - 1), Int64(count), Ptr{Int32}(C_NULL)))
+    mck
+end
+
+"""
+    mk_rot_net_level!(mck, E, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_first=nothing; out_form=2, out_first=1, out_wires=nothing)
+
+`mk_rot_net` between the device-resident tables (tfhe_mk_rot_net_level): `rot_net_level!` with MK TLWE slots, the multi-key selector set
+and the multi-key wire table.  Level 0 of row `g` reads source `src` at slot `table_first[g] + src - 1` (`table_first` 1-based, `B`
+entries; `nothing`: `src` is an absolute slot).  `out_form` 0: output node `i` of row `g` goes to slot `out_first + (g - 1) F + i - 1`;
+`out_form` 2: through the multi-key keyswitch to wire `out_wires[(g - 1) F + i]` (1-based).  The words are `mk_rot_net`'s on the same
+samples.  Synchronous.
+"""
+function mk_rot_net_level!(mck::GpuMKCloudKey, E::Integer, widths, nodes::AbstractMatrix, sel::AbstractMatrix, table_first=nothing; out_form::Integer=2,
+                           out_first::Integer=1, out_wires=nothing)
+    N = mck.params.tlwe_polynomial_degree
+    w = Int32.(collect(widths))
+    levels = length(w)
+    1 <= levels <= 1024 || error("tfhe_mi355x: levels = ", levels, " (1 ... 1024)")
+    all(x -> 1 <= x <= 4096, w) || error("tfhe_mi355x: every width must be 1 ... 4096")
+    size(nodes) == (5, sum(w)) || error("tfhe_mi355x: nodes must be 5 x sum(widths)")
+    all(r -> 0 <= r < 2N, view(nodes, 4:5, :)) || error("tfhe_mi355x: every rotation must be 0 ... 2N - 1")
+    E >= 1 || error("tfhe_mi355x: E = ", E, " (at least one entry)")
+    V, B = size(sel)
+    V >= 1 || error("tfhe_mi355x: sel must be V x B with V >= 1")
+    out_form == 0 || out_form == 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 into MK TLWE slots, 2 key-switched into wires)")
+    nd = Matrix{Int32}(vcat(nodes[1:3, :] .- 1, nodes[4:5, :]))
+    s = Matrix{Int32}(sel .- 1)
+    tf = table_first === nothing ? nothing : Int32.(collect(table_first) .- 1)
+    tf === nothing || length(tf) == B || error("tfhe_mi355x: table_first must have one entry per row")
+    F = Int(w[end])
+    ow = out_wires === nothing ? nothing : Int32.(collect(out_wires) .- 1)
+    out_form != 2 || (ow !== nothing && length(ow) == F * B) || error("tfhe_mi355x: out_wires must have F * B entries with out_form 2")
+    out_form != 0 || out_first >= 1 || error("tfhe_mi355x: slots are 1-based, out_first = ", out_first)
+    GC.@preserve w nd s tf ow @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_rot_net_level, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Int64, Ptr{Int32}, Int64),
+        mck.ctx, tf === nothing ? Ptr{Int32}(C_NULL) : pointer(tf), Int32(E), w, Int32(levels), nd, s, Int32(V), Int32(out_form), Int64(out_first - 1),
+        ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
+    mck
+end
+
+"""
+    mk_blind_rotate_level!(mck, acc_slot, term_start, term_wire, term_coef; cst=nothing, sel=nothing, n_out=1, out_form=2, out_slot=nothing, out_wires=nothing)
+
+`mk_blind_rotate` between the device-resident tables (tfhe_mk_blind_rotate_level): `blind_rotate_level!` with MK TLWE slots, rows of the
+multi-key wire table and `P n` steps.  Row `g` rotates the sample in slot `acc_slot[g]` by the multi-key LWE sample
+`sum_t term_coef[t] * wire[term_wire[t]] + cst[g]` over the terms `term_start[g] + 1 : term_start[g + 1]` (`term_start` is the 0-based
+prefix sum of the rows' term counts, `B + 1` entries from 0; it and the coefficients pass unchanged; slots, wires and selectors are
+1-based) on the selectors `sel` (`P n` entries; `nothing`: selector `i` for step `i`, the key loaded party-major).  `out_form` 0 (`n_out`
+1): the final accumulator goes to slot `out_slot[g]`; `out_form` 2: the `n_out` extractions go through the multi-key keyswitch to wires
+`out_wires[(g - 1) n_out + j]`.  The words are `mk_blind_rotate`'s on the same samples.  Synchronous.
+"""
+function mk_blind_rotate_level!(mck::GpuMKCloudKey, acc_slot, term_start, term_wire, term_coef; cst=nothing, sel=nothing, n_out::Integer=1,
+                                out_form::Integer=2, out_slot=nothing, out_wires=nothing)
+    p, P = mck.params, mck.parties
+    N = p.tlwe_polynomial_degree
+    acc = Int32.(collect(acc_slot) .- 1)
+    B = length(acc)
+    start = Int32.(collect(term_start))
+    length(start) == B + 1 && start[1] == 0 && issorted(start) || error("tfhe_mi355x: term_start must be B + 1 non-decreasing entries from 0")
+    T = Int(start[end])
+    tw = Int32.(collect(term_wire) .- 1)
+    tc = Int32.(collect(term_coef))
+    length(tw) >= T && length(tc) >= T || error("tfhe_mi355x: term_wire and term_coef must have term_start[end] entries")
+    c = cst === nothing ? nothing : Int32.(collect(cst))
+    c === nothing || length(c) == B || error("tfhe_mi355x: cst must have one entry per row")
+    s = sel === nothing ? nothing : Int32.(collect(sel) .- 1)
+    s === nothing || length(s) == P * p.lwe_size || error("tfhe_mi355x: sel must have one entry per step (P n)")
+    out_form == 0 || out_form == 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 into MK TLWE slots, 2 key-switched into wires)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    os = out_slot === nothing ? nothing : Int32.(collect(out_slot) .- 1)
+    ow = out_wires === nothing ? nothing : Int32.(collect(out_wires) .- 1)
+    out_form != 0 || (os !== nothing && length(os) == B) || error("tfhe_mi355x: out_slot must have one entry per row with out_form 0")
+    out_form != 2 || (ow !== nothing && length(ow) == n_out * B) || error("tfhe_mi355x: out_wires must have n_out * B entries with out_form 2")
+    GC.@preserve acc start tw tc c s os ow @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_blind_rotate_level, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Int64),
+        mck.ctx, acc, start, tw, tc, c === nothing ? Ptr{Int32}(C_NULL) : pointer(c), s === nothing ? Ptr{Int32}(C_NULL) : pointer(s), Int32(n_out),
+        Int32(out_form), os === nothing ? Ptr{Int32}(C_NULL) : pointer(os), ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
+    mck
 end
 
 """

@@ -24,6 +24,7 @@ from .leveled import mk_tlwe_trivial, mk_tlwe_encrypt, mk_tlwe_phase, mk_tgsw_un
 from .leveled import packed_words_net, pack_words_to_tlwe, mk_rot_net_lookup, mk_packed_lookup
 from .leveled import bootstrap_key_selectors, private_lut_encrypt, blind_rotate_lookup, two_stage_lookup, pbs_to_tlwe
 from .leveled import mk_bootstrap_key_selectors, mk_private_lut_encrypt, mk_blind_rotate_lookup, mk_two_stage_lookup, mk_pbs_to_tlwe
+from .leveled import mk_two_stage_lookup_device
 from ._lib import Engine, EngineError, OPCODES, LIB_PATH, pinned_empty
 
 __all__ = [
@@ -43,5 +44,6 @@ __all__ = [
     "packed_words_net", "pack_words_to_tlwe", "mk_rot_net_lookup", "mk_packed_lookup",
     "bootstrap_key_selectors", "private_lut_encrypt", "blind_rotate_lookup", "two_stage_lookup", "pbs_to_tlwe",
     "mk_bootstrap_key_selectors", "mk_private_lut_encrypt", "mk_blind_rotate_lookup", "mk_two_stage_lookup", "mk_pbs_to_tlwe",
+    "mk_two_stage_lookup_device",
     "save_cloud_key", "load_cloud_key", "Engine", "EngineError", "OPCODES", "LIB_PATH", "pinned_empty",
 ]

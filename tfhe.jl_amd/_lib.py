@@ -29,7 +29,8 @@ ABI_SYMBOLS = [
     "tfhe_mk_tgsw_load", "tfhe_mk_tgsw_expand_load", "tfhe_mk_extern_mul_batch", "tfhe_mk_cmux_tree_batch",
     "tfhe_mk_cmux_net_batch", "tfhe_rot_net_batch", "tfhe_mk_rot_net_batch", "tfhe_blind_rotate_batch",
     "tfhe_mk_blind_rotate_batch", "tfhe_tlwe_alloc", "tfhe_tlwe_upload", "tfhe_tlwe_download", "tfhe_tgsw_update",
-    "tfhe_rot_net_level", "tfhe_blind_rotate_level",
+    "tfhe_rot_net_level", "tfhe_blind_rotate_level", "tfhe_mk_tlwe_alloc", "tfhe_mk_tlwe_upload", "tfhe_mk_tlwe_download",
+    "tfhe_mk_tgsw_update", "tfhe_mk_tgsw_expand_update", "tfhe_mk_rot_net_level", "tfhe_mk_blind_rotate_level",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -178,6 +179,14 @@ def load():
         lib.tfhe_tgsw_update.argtypes = [vp, vp, i64, i64]
         lib.tfhe_rot_net_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, i64, vp, i64]
         lib.tfhe_blind_rotate_level.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64]
+    if hasattr(lib, "tfhe_mk_tlwe_alloc"):
+        lib.tfhe_mk_tlwe_alloc.argtypes = [vp, i64]
+        lib.tfhe_mk_tlwe_upload.argtypes = [vp, i64, i64, vp]
+        lib.tfhe_mk_tlwe_download.argtypes = [vp, i64, i64, vp]
+        lib.tfhe_mk_tgsw_update.argtypes = [vp, vp, vp, i64, i64, i32]
+        lib.tfhe_mk_tgsw_expand_update.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]
+        lib.tfhe_mk_rot_net_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, i64, vp, i64]
+        lib.tfhe_mk_blind_rotate_level.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -607,6 +616,9 @@ class Engine:
         """rot_net between the tables (tfhe_rot_net_level).  net: a leveled.RotNet, or a leveled.CmuxNet (its rotation-0 case);
         sel: int32 [B][V]; level 0 of row g reads source src at TLWE slot table_first[g] + src (None: absolute slots).  out_form 0:
         output node i of row g goes to slot out_first + g F + i; out_form 2: keyswitched, to wire out_wires[g F + i].  Synchronous."""
+        self._rot_net_level(self._lib.tfhe_rot_net_level, net, sel, table_first, out_form, out_first, out_wires)
+
+    def _rot_net_level(self, call, net, sel, table_first, out_form, out_first, out_wires):
         nodes = _i32c(net.nodes)
         if nodes.shape[1] == 3:      # a CmuxNet: every rotation 0
             nodes = np.ascontiguousarray(np.concatenate([nodes, np.zeros((nodes.shape[0], 2), np.int32)], axis=1))
@@ -627,14 +639,18 @@ class Engine:
             ow = _i32c(out_wires).reshape(-1)
             if ow.size != B * F:
                 raise ValueError(f"out_wires must have B F = {B * F} entries, got {ow.size}")
-        self._check(self._lib.tfhe_rot_net_level(self._h, _ptr(first), net.entries, _ptr(net.widths), net.levels, _ptr(nodes), _ptr(sel), V,
-                                                 int(out_form), int(out_first), _ptr(ow), B))
+        self._check(call(self._h, _ptr(first), net.entries, _ptr(net.widths), net.levels, _ptr(nodes), _ptr(sel), V, int(out_form), int(out_first),
+                         _ptr(ow), B))
 
     def blind_rotate_level(self, acc_slot, term_start, term_wire, term_coef, cst=None, sel=None, n_out=1, out_form=2, out_slot=None, out_wires=None):
         """blind_rotate between the tables (tfhe_blind_rotate_level).  Row g rotates the sample in TLWE slot acc_slot[g] by lut_level's
         combination of wires (term_start [B+1], term_wire, term_coef, cst) over the context's n steps; sel: int32 [n] or None.  out_form
         0: the final accumulator goes to slot out_slot[g]; out_form 2: the n_out extractions, keyswitched, to wires
         out_wires[g n_out + j].  Synchronous."""
+        self._blind_rotate_level(self._lib.tfhe_blind_rotate_level, self.n, acc_slot, term_start, term_wire, term_coef, cst, sel, n_out, out_form,
+                                 out_slot, out_wires)
+
+    def _blind_rotate_level(self, call, steps, acc_slot, term_start, term_wire, term_coef, cst, sel, n_out, out_form, out_slot, out_wires):
         acc = _i32c(acc_slot).reshape(-1)
         start = _i32c(term_start).reshape(-1)
         B = acc.size
@@ -650,8 +666,8 @@ class Engine:
         s = None
         if sel is not None:
             s = _i32c(sel).reshape(-1)
-            if s.size != self.n:
-                raise ValueError(f"sel must have one entry per step ({self.n}), got {s.size}")
+            if s.size != steps:
+                raise ValueError(f"sel must have one entry per step ({steps}), got {s.size}")
         n_out = int(n_out)
         os_ = None if out_slot is None else _i32c(out_slot).reshape(-1)
         if os_ is not None and os_.size != B:
@@ -659,8 +675,7 @@ class Engine:
         ow = None if out_wires is None else _i32c(out_wires).reshape(-1)
         if ow is not None and ow.size != B * max(n_out, 1):
             raise ValueError(f"out_wires must have B n_out = {B * max(n_out, 1)} entries, got {ow.size}")
-        self._check(self._lib.tfhe_blind_rotate_level(self._h, _ptr(acc), _ptr(start), _ptr(wire), _ptr(coef), _ptr(c), _ptr(s), n_out, int(out_form),
-                                                      _ptr(os_), _ptr(ow), B))
+        self._check(call(self._h, _ptr(acc), _ptr(start), _ptr(wire), _ptr(coef), _ptr(c), _ptr(s), n_out, int(out_form), _ptr(os_), _ptr(ow), B))
 
     # ---- leveled mode under a multi-key cloud key: expanded RGSW selectors, MK TLWE samples [P+1][N] ----
     def mk_tgsw_load(self, tgsw, party_of):
@@ -668,6 +683,7 @@ class Engine:
         the multi-key bootstrapping key (leveled.mk_tgsw_expand makes them), and party_of [S], the party each was expanded for.
         Replaces any earlier set."""
         P = self._mk_width("mk_tgsw_load")
+        self._mk_key_extra = None      # (leveled.mk_two_stage_lookup_device: the set is no longer the one it loaded)
         t, who = _i32c(tgsw), _i32c(party_of).reshape(-1)
         per = (2 * self.params.bs_decomp_length * P + 2 * self.params.bs_decomp_length) * self.N
         if who.size == 0 or t.size != who.size * per:
@@ -679,6 +695,7 @@ class Engine:
         sample s uni-encrypted by party party_of[s] (leveled.mk_tgsw_uni_encrypt_bits).  Returns the expanded samples
         [S][2lP + 2l][N] if want_expanded."""
         P, l = self._mk_width("mk_tgsw_expand_load"), self.params.bs_decomp_length
+        self._mk_key_extra = None      # (leveled.mk_two_stage_lookup_device: the set is no longer the one it loaded)
         who = _i32c(party_of).reshape(-1)
         S = who.size
         arrs = [_i32c(a) for a in (pub_b, c0, c1, d0, d1, f0, f1)]
@@ -793,6 +810,69 @@ class Engine:
         self._check(self._lib.tfhe_mk_blind_rotate_batch(self._h, _ptr(a), a.shape[0], _ptr(idx), _ptr(r), steps, int(in_form), _ptr(s), n_out, _ptr(out),
                                                          B, int(out_form)))
         return out
+
+    # ---- multi-key leveled mode on device-resident tables: the MK TLWE table beside the multi-key wire table ----
+    def mk_tlwe_alloc(self, slots):
+        """A device table of MK TLWE samples int32 [slots][P+1][N] for the parties of the loaded multi-key bootstrapping key
+        (tfhe_mk_tlwe_alloc); 0 frees it, reallocating discards the contents."""
+        self._check(self._lib.tfhe_mk_tlwe_alloc(self._h, int(slots)))
+
+    def mk_tlwe_upload(self, first, samples):
+        """samples int32 [count][P+1][N] into slots [first, first + count) (tfhe_mk_tlwe_upload), behind the levels queued so far."""
+        P = self._mk_width("mk_tlwe_upload")
+        m = _i32c(samples)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[1:] != (P + 1, self.N):
+            raise ValueError(f"MK TLWE samples must be [count][{P + 1}][{self.N}], got {m.shape}")
+        self._check(self._lib.tfhe_mk_tlwe_upload(self._h, int(first), m.shape[0], _ptr(m)))
+
+    def mk_tlwe_download(self, first, count):
+        """Slots [first, first + count) as int32 [count][P+1][N] (tfhe_mk_tlwe_download), behind the levels queued so far."""
+        P = self._mk_width("mk_tlwe_download")
+        out = np.empty((max(int(count), 0), P + 1, self.N), np.int32)
+        self._check(self._lib.tfhe_mk_tlwe_download(self._h, int(first), int(count), _ptr(out)))
+        return out
+
+    def mk_tgsw_update(self, first, tgsw, party_of):
+        """Replaces selectors [first, first + count) of the loaded multi-key set in place (tfhe_mk_tgsw_update): tgsw int32
+        [count][2lP + 2l][N] expanded samples, party_of [count]; every other selector keeps its words."""
+        P = self._mk_width("mk_tgsw_update")
+        t, who = _i32c(tgsw), _i32c(party_of).reshape(-1)
+        per = (2 * self.params.bs_decomp_length * P + 2 * self.params.bs_decomp_length) * self.N
+        if who.size == 0 or t.size != who.size * per:
+            raise ValueError(f"expanded samples have {t.size} words, expected {per} for each of the {who.size} entries of party_of")
+        self._check(self._lib.tfhe_mk_tgsw_update(self._h, _ptr(t), _ptr(who), int(first), who.size, P))
+
+    def mk_tgsw_expand_update(self, first, pub_b, party_of, c0, c1, d0, d1, f0, f1, want_expanded=False):
+        """The same update expanded on the device (tfhe_mk_tgsw_expand_update).  pub_b: [P][l][N]; party_of: [count]; c0 .. f1:
+        [count][l][N], sample s uni-encrypted by party party_of[s].  Returns the expanded samples [count][2lP + 2l][N] if want_expanded."""
+        P, l = self._mk_width("mk_tgsw_expand_update"), self.params.bs_decomp_length
+        who = _i32c(party_of).reshape(-1)
+        S = who.size
+        arrs = [_i32c(a) for a in (pub_b, c0, c1, d0, d1, f0, f1)]
+        if arrs[0].shape != (P, l, self.N):
+            raise ValueError(f"public keys must be [{P}][{l}][{self.N}], got {arrs[0].shape}")
+        for a in arrs[1:]:
+            if S == 0 or a.shape != (S, l, self.N):
+                raise ValueError(f"uni-encryption arrays must be [{S}][{l}][{self.N}] with count >= 1, got {a.shape}")
+        out = np.empty((S, 2 * l * P + 2 * l, self.N), np.int32) if want_expanded else None
+        self._check(self._lib.tfhe_mk_tgsw_expand_update(self._h, P, _ptr(arrs[0]), _ptr(who), *[_ptr(a) for a in arrs[1:]], int(first), S, _ptr(out)))
+        return out
+
+    def mk_rot_net_level(self, net, sel, table_first=None, out_form=2, out_first=0, out_wires=None):
+        """mk_rot_net between the tables (tfhe_mk_rot_net_level): rot_net_level with MK TLWE slots, multi-key wires and the multi-key
+        selector set.  Synchronous."""
+        self._mk_width("mk_rot_net_level")
+        self._rot_net_level(self._lib.tfhe_mk_rot_net_level, net, sel, table_first, out_form, out_first, out_wires)
+
+    def mk_blind_rotate_level(self, acc_slot, term_start, term_wire, term_coef, cst=None, sel=None, n_out=1, out_form=2, out_slot=None, out_wires=None):
+        """mk_blind_rotate between the tables (tfhe_mk_blind_rotate_level): blind_rotate_level with MK TLWE slots, mk_lut_level's
+        combination of multi-key wires over P n steps (sel: int32 [P n] or None, selector i for step i) and the multi-key keyswitch.
+        Synchronous."""
+        P = self._mk_width("mk_blind_rotate_level")
+        self._blind_rotate_level(self._lib.tfhe_mk_blind_rotate_level, P * self.n, acc_slot, term_start, term_wire, term_coef, cst, sel, n_out,
+                                 out_form, out_slot, out_wires)
 
     # ---- levelised circuits on the device-resident wire table ----
     def wires_alloc(self, num_wires):

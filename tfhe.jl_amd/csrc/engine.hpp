@@ -22,8 +22,10 @@
 //   engine_mk_blind_rotate.hip   the same rotation of MK TLWE accumulators under a multi-key cloud key                  ("mk blind rotate")
 //   engine_tlwe_levels.hip    the device-resident TLWE table and the blind rotation between it and the wire table (tfhe_tlwe_*, tfhe_blind_rotate_level;
 //                             tfhe_rot_net_level is engine_rot_net.hip's, tfhe_tgsw_update engine_keys.hip's)              ("tlwe levels")
+//   engine_mk_tlwe_levels.hip   the same under a multi-key cloud key: the MK TLWE table and tfhe_mk_blind_rotate_level (tfhe_mk_tlwe_*;
+//                             tfhe_mk_rot_net_level is engine_mk_rot_net.hip's, tfhe_mk_tgsw_update / _expand_update engine_keys.hip's)  ("mk tlwe levels")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
-//   leveled_run.hpp       host-only: the one runner behind the eleven leveled entry points (workspaces, uploads, level loop, download)
+//   leveled_run.hpp       host-only: the one runner behind the twelve leveled entry points (workspaces, uploads, level loop, download)
 //   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share
 //
 // Every kernel is compiled in exactly one translation unit: the kernel headers define their non-template __global__ functions
@@ -212,6 +214,11 @@ struct tfhe_ctx {
     // device-resident TLWE table of the leveled half (tfhe_tlwe_alloc, engine_tlwe_levels.hip): int32 [tlwe_slots][k+1][N], single-key,
     // one-device contexts only; tfhe_rot_net_level and tfhe_blind_rotate_level read and write it
     int32_t *d_tlwe = nullptr; int64_t tlwe_slots = 0;
+    // its multi-key form (tfhe_mk_tlwe_alloc, engine_mk_tlwe_levels.hip): int32 [mk_tlwe_slots][P+1][N] for the parties of the multi-key
+    // bootstrapping key loaded when it was allocated (mk_tlwe_parties, as wires_parties for the wires); tfhe_mk_rot_net_level and
+    // tfhe_mk_blind_rotate_level read and write it
+    int32_t *d_mk_tlwe = nullptr; int64_t mk_tlwe_slots = 0;
+    int mk_tlwe_parties = 0;
 
     // workspaces
     DevBuf bara, ext, map, io[4], diag, abar, mk_acc, spec;

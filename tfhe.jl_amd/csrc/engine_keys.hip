@@ -679,6 +679,119 @@ int32_t tfhe_mk_tgsw_expand_load(tfhe_ctx *c, int32_t parties, const int32_t *pu
 }
 ABI_CATCH(c, "tfhe_mk_tgsw_expand_load")
 
+// ---- selectors [first, first + count) of the loaded multi-key set replaced in place (tfhe_tgsw_update's order: quiesce, stage,
+// tgsw_prepare into the range), spectra and party_of entries alike; every other selector keeps its exact words.  The key's P n selectors
+// are loaded once and a request's address-bit selectors are swapped behind them.
+// what both updates refuse before they touch the device; *per = polynomials of one expanded sample
+static int32_t mk_tgsw_update_check(tfhe_ctx *c, const char *who, const int32_t *party_of, int64_t first, int64_t count, int32_t parties, size_t *per)
+{
+    if (c->P.parties < 2) return c->set_err(TFHE_ERR_STATE, "%s: context is single-key (tfhe_tgsw_update is its selector update)", who);
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "%s: multi-device context (leveled operations run on a one-device context)", who);
+    if (!party_of) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL pointer", who);
+    if (count < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: count = %lld (at least one selector)", who, (long long)count);
+    if (!c->have_mk_bk || !c->d_mk_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (tfhe_mk_tgsw_load)", who);
+    if (parties != c->mk_parties)
+        return c->set_err(TFHE_ERR_STATE, "%s: parties = %d, the multi-key bootstrapping key was loaded for %d", who, parties, c->mk_parties);
+    if (first < 0 || first >= c->mk_tgsw_count || count > c->mk_tgsw_count - first)
+        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: selectors [%lld, %lld + %lld) are outside the %lld loaded ones", who, (long long)first, (long long)first,
+                          (long long)count, (long long)c->mk_tgsw_count);
+    for (int64_t s = 0; s < count; s++)
+        if (party_of[s] < 0 || party_of[s] >= parties)
+            return c->set_err(TFHE_ERR_INVALID_ARG, "%s: party_of[%lld] = %d is outside the %d parties", who, (long long)s, party_of[s], parties);
+    *per = (size_t)2 * c->P.bs_l * parties + 2 * c->P.bs_l;
+    return TFHE_OK;
+}
+
+// `count` caller-expanded RGSW samples, int32 [count][2 l P + 2 l][N], and the party each was expanded for
+int32_t tfhe_mk_tgsw_update(tfhe_ctx *c, const int32_t *tgsw, const int32_t *party_of, int64_t first, int64_t count, int32_t parties) try
+{
+    ENTER_CTX(c);
+    if (!tgsw) return c->set_err(TFHE_ERR_INVALID_ARG, "mk_tgsw_update: NULL pointer");
+    size_t per = 0;
+    int32_t rc = mk_tgsw_update_check(c, "mk_tgsw_update", party_of, first, count, parties, &per);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = check_key_source(c, tgsw, "mk_tgsw_update");
+    if (rc) return rc;
+    const size_t npolys = (size_t)count * per, M = (size_t)(c->P.N / 2 > 0 ? c->P.N / 2 : 1), bytes_in = npolys * (size_t)c->P.N * 4;
+    quiesce(c);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+    if ((double)bytes_in > (double)free_b)
+        return c->set_err(TFHE_ERR_NOMEM, "mk_tgsw_update: the staging of %lld samples does not fit the device's free memory", (long long)count);
+    void *d_in = nullptr;
+    hipError_t e = hipMalloc(&d_in, bytes_in);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, tgsw, bytes_in, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_mk_tgsw_party + first, party_of, (size_t)count * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) rc = tgsw_prepare(c, (const int32_t *)d_in, c->d_mk_tgsw + (size_t)first * per * M, npolys, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on failure: d_in is freed below)
+    if (e == hipSuccess) e = es;
+    if (d_in) (void)hipFree(d_in);
+    if (rc) return rc;
+    if (e != hipSuccess) return c->set_err(TFHE_ERR_DEVICE, "mk_tgsw_update: %s", hipGetErrorString(e));
+    return TFHE_OK;
+}
+ABI_CATCH(c, "tfhe_mk_tgsw_update")
+
+// The same from what the parties publish: tfhe_mk_tgsw_expand_load's per-party grouping over the `count` new samples only (c0 ... f1:
+// int32 [count][l][N], party_of [count]); expanded_out, if not NULL, receives the `count` expanded samples [count][2 l P + 2 l][N].
+int32_t tfhe_mk_tgsw_expand_update(tfhe_ctx *c, int32_t parties, const int32_t *pub_b, const int32_t *party_of, const int32_t *c0, const int32_t *c1,
+                                   const int32_t *d0, const int32_t *d1, const int32_t *f0, const int32_t *f1, int64_t first, int64_t count,
+                                   int32_t *expanded_out) try
+{
+    ENTER_CTX(c);
+    if (!pub_b || !c0 || !c1 || !d0 || !d1 || !f0 || !f1) return c->set_err(TFHE_ERR_INVALID_ARG, "mk_tgsw_expand_update: NULL argument");
+    size_t per = 0;
+    int32_t rc = mk_tgsw_update_check(c, "mk_tgsw_expand_update", party_of, first, count, parties, &per);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int l = c->P.bs_l, P = parties;
+    const size_t N = (size_t)c->P.N, M = N / 2 > 0 ? N / 2 : 1, lN = (size_t)l * N;
+    alloc_checkpoint();
+    std::vector<std::vector<int64_t>> of((size_t)P);      // the new selectors of each party, in the caller's order
+    for (int64_t s = 0; s < count; s++) of[(size_t)party_of[s]].push_back(s);
+    size_t cap = 0;
+    for (const auto &v : of) cap = std::max(cap, v.size());
+    const size_t ndec = (size_t)(P - 1) * l * l;
+    const double scratch = (6.0 * cap * lN + (double)ndec * N + (double)cap * per * N) * 4 + ((double)ndec + 2.0 * cap * l) * M * sizeof(cplx);
+    quiesce(c);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+    if (scratch > (double)free_b)
+        return c->set_err(TFHE_ERR_NOMEM, "mk_tgsw_expand_update: the expansion of %lld samples does not fit the device's free memory", (long long)count);
+    MkExpandWork w;
+    auto guard = on_exit([&] { (void)hipStreamSynchronize(c->stream); w.release(); });
+    rc = mk_expand_alloc(c, w, P, cap);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    std::vector<int32_t> h_in(6 * cap * lN), h_key(expanded_out ? cap * per * N : 0);
+    HIP_TRY(c, hipMemcpyAsync(c->d_mk_tgsw_party + first, party_of, (size_t)count * 4, hipMemcpyHostToDevice, s));
+    const int32_t *arr[6] = {c0, c1, d0, d1, f0, f1};
+    for (int i = 0; i < P; i++) {
+        const std::vector<int64_t> &mine = of[(size_t)i];
+        const size_t cnt = mine.size();
+        if (cnt == 0) continue;
+        const int32_t *src[6];
+        for (int a = 0; a < 6; a++) {
+            int32_t *dst = h_in.data() + (size_t)a * cnt * lN;
+            for (size_t j = 0; j < cnt; j++) memcpy(dst + j * lN, arr[a] + (size_t)mine[j] * lN, lN * 4);
+            src[a] = dst;
+        }
+        rc = mk_expand_party(c, w, true, P, i, (int)cnt, pub_b, src, s);
+        if (rc) return rc;
+        for (size_t j = 0; j < cnt; j++) {      // sample j of the group is selector first + mine[j]
+            rc = tgsw_prepare(c, w.d_key + j * per * N, c->d_mk_tgsw + (size_t)(first + mine[j]) * per * M, per, s);
+            if (rc) return rc;
+        }
+        if (expanded_out) HIP_TRY(c, hipMemcpyAsync(h_key.data(), w.d_key, cnt * per * N * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));      // h_in, h_dec and the scratch buffers are reused by the next party
+        if (expanded_out)
+            for (size_t j = 0; j < cnt; j++) memcpy(expanded_out + (size_t)mine[j] * per * N, h_key.data() + j * per * N, per * N * 4);
+    }
+    return TFHE_OK;
+}
+ABI_CATCH(c, "tfhe_mk_tgsw_expand_update")
+
 int32_t tfhe_mk_load_keyswitch_key(tfhe_ctx *c, const int32_t *ks, int32_t parties) try
 {
     ENTER_CTX(c);

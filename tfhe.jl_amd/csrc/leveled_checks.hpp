@@ -1,5 +1,6 @@
 // leveled_checks.hpp — host-only checks that more than one leveled unit makes before anything is uploaded: the state a multi-key
-// leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip, engine_mk_blind_rotate.hip) and the netlist of a CMUX network
+// leveled call needs (engine_mk_leveled.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip, engine_mk_blind_rotate.hip; on the device-resident
+// tables: engine_mk_rot_net.hip, engine_mk_tlwe_levels.hip) and the netlist of a CMUX network
 // (engine_cmux_net.hip, engine_mk_cmux_net.hip; with monomial edges: engine_rot_net.hip, engine_mk_rot_net.hip).  Every function sets
 // the context's error message, naming the caller `who`, and returns its code.
 #pragma once
@@ -24,6 +25,33 @@ inline int32_t mk_leveled_state(tfhe_ctx *c, const char *who)
     if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the CMUX level kernel has no DIAG instantiation)", who);
     if (!c->have_mk_bk) return c->set_err(TFHE_ERR_NO_KEY, "%s: no multi-key bootstrapping key loaded", who);
     if (!c->d_mk_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (tfhe_mk_tgsw_load)", who);
+    return TFHE_OK;
+}
+
+// what the multi-key level calls on the device-resident tables (tfhe_mk_rot_net_level, tfhe_mk_blind_rotate_level) refuse before they
+// look at their arguments: the state first, then the key that fixes P.  `needs_wires`: the call reads or writes the wire table;
+// `keyswitches`: out_form 2.  (The selector set and the keyswitch key are asked for after the arguments, as in the single-key calls.)
+inline int32_t mk_level_state(tfhe_ctx *c, const char *who, bool needs_wires, bool keyswitches)
+{
+    if (c->P.parties < 2) return c->set_err(TFHE_ERR_STATE, "%s: context is single-key (tfhe_rot_net_level / tfhe_blind_rotate_level are its level calls)", who);
+    if (c->multi()) return c->set_err(TFHE_ERR_STATE, "%s: multi-device context (leveled operations run on a one-device context)", who);
+    if (c->measure_margin) return c->set_err(TFHE_ERR_STATE, "%s: measure_margin is on (the CMUX level kernel has no DIAG instantiation)", who);
+    if (!c->d_mk_tlwe) return c->set_err(TFHE_ERR_STATE, "%s: no MK TLWE table allocated (tfhe_mk_tlwe_alloc)", who);
+    if (needs_wires && !c->d_wires) return c->set_err(TFHE_ERR_STATE, "%s: no wire table allocated (out_form 2 and terms need one)", who);
+    if (needs_wires && !c->wires_parties)
+        return c->set_err(TFHE_ERR_STATE, "%s: the wire table has single-key rows (tfhe_wires_alloc): allocate it with tfhe_mk_wires_alloc", who);
+    if (c->have_mk_bk) {
+        if (c->mk_tlwe_parties != c->mk_parties)
+            return c->set_err(TFHE_ERR_STATE, "%s: the MK TLWE table holds %d-party samples, the bootstrapping key is for %d parties", who, c->mk_tlwe_parties,
+                              c->mk_parties);
+        if (needs_wires && c->wires_parties != c->mk_parties)
+            return c->set_err(TFHE_ERR_STATE, "%s: the wire table holds %d-party rows, the bootstrapping key is for %d parties", who, c->wires_parties, c->mk_parties);
+        // (the keyswitch addresses rows by ITS key's parties, the levels write them by the bootstrapping key's: they must agree)
+        if (keyswitches && c->have_mk_ks() && c->ks.parties != c->mk_parties)
+            return c->set_err(TFHE_ERR_STATE, "%s: the bootstrapping key was loaded for %d parties, the keyswitch key for %d: load both for the same parties", who,
+                              c->mk_parties, c->ks.parties);
+    }
+    if (!c->have_mk_bk) return c->set_err(TFHE_ERR_NO_KEY, "%s: no multi-key bootstrapping key loaded", who);
     return TFHE_OK;
 }
 

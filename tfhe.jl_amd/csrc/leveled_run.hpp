@@ -1,8 +1,8 @@
 // leveled_run.hpp — host-only: the one runner behind the leveled entry points (engine_leveled.hip, engine_mk_leveled.hip,
 // engine_cmux_net.hip, engine_rot_net.hip, engine_mk_cmux_net.hip, engine_mk_rot_net.hip).  An entry point validates its arguments, describes the call in a
 // LevelPlan and names its kernel; the workspace protocol, the uploads, the level loop, the keyswitch, the download and the timing are
-// here and nowhere else.  tfhe_rot_net_level runs through it too: its sources and destinations are the device-resident TLWE and wire tables
-// (LevelPlan's d_* fields), so nothing is uploaded but the maps and nothing is downloaded.
+// here and nowhere else.  tfhe_rot_net_level and tfhe_mk_rot_net_level run through it too: their sources and destinations are the
+// device-resident (MK) TLWE and wire tables (LevelPlan's d_* fields), so nothing is uploaded but the maps and nothing is downloaded.
 #pragma once
 #include "engine.hpp"
 #include "kernels_leveled_core.hpp"

@@ -47,6 +47,11 @@ bootstrapping key is a selector set of P n expanded RGSW samples, party-major (m
 sample by a multi-key LWE sample as it lies in memory.  mk_private_lut_encrypt is one party's private function on jointly encrypted
 data, mk_two_stage_lookup a table of p 2^d entries addressed by jointly encrypted TGSW bits and a computed digit, mk_pbs_to_tlwe a
 multi-key bootstrap's result as an entry of the tables mk_cmux_lookup / mk_cmux_net_lookup read.
+
+mk_two_stage_lookup_device is mk_two_stage_lookup's program between the device-resident tables of a multi-key engine (the MK TLWE table
+of Engine.mk_tlwe_alloc and the multi-key wire table): the key's selectors are loaded once, a request's address bits are swapped
+behind them (Engine.mk_tgsw_expand_update), the tree writes slots (Engine.mk_rot_net_level) and the rotation reads its digit from a wire
+and writes wires (Engine.mk_blind_rotate_level).
 """
 import numpy as np
 
@@ -707,6 +712,7 @@ def _mk_load_key_selectors(ck, extra_uni_bits, extra_party_of, expand, device):
                     more[mine] = mk_tgsw_expand(ck.params, pub, i, *[a[mine] for a in extra])
             tg = np.concatenate([tg, more])
         eng.mk_tgsw_load(tg, who)
+    eng._mk_key_extra = int(who_extra.size)      # (mk_two_stage_lookup_device: the key is resident with this many selectors behind it)
     return eng
 
 
@@ -757,3 +763,34 @@ def mk_pbs_to_tlwe(ck, lwe, f, p, q=None, device=0):
     N = ck.params.tlwe_polynomial_degree
     tv = make_test_vector(f, p, N, q) if callable(f) else np.asarray(f, np.int32)
     return mk_blind_rotate_lookup(ck, mk_tlwe_trivial(tv, ck.parties), lwe, out_form=0, device=device)
+
+
+def mk_two_stage_lookup_device(ck, table_slot, high_uni_bits, party_of, low_wires, out_wires, work_slot, device=0):
+    """mk_two_stage_lookup between the device-resident tables of ck's engine: the 2^d test polynomials are in MK TLWE slots
+    [table_slot, table_slot + 2^d) (Engine.mk_tlwe_upload), row g's low digit is multi-key wire low_wires[g] (what mk_lut_level or
+    mk_gates_level left there) and its answer goes, keyswitched, to wire out_wires[g]; slots [work_slot, work_slot + B) receive the
+    picked samples.  The key's P n selectors are loaded once per engine, with the first request's address bits behind them
+    (tfhe_mk_tgsw_expand_load); every later request of the same shape swaps only its B d address bits in (Engine.mk_tgsw_expand_update)
+    instead of re-expanding the key.  Then Engine.mk_rot_net_level (the tree, into slots) and Engine.mk_blind_rotate_level (into wires):
+    nothing but the uni-encryptions and the index maps crosses PCIe.  The words in out_wires equal mk_two_stage_lookup's on the same
+    samples.  Returns the engine."""
+    arrs = [np.asarray(a, np.int32) for a in high_uni_bits]
+    if len(arrs) != 6 or arrs[0].ndim != 4 or any(a.shape != arrs[0].shape for a in arrs):
+        raise ValueError("high_uni_bits must be six arrays [B][depth][l][N]")
+    B, depth = arrs[0].shape[:2]
+    low = np.asarray(low_wires, np.int32).reshape(-1)
+    if low.size != B:
+        raise ValueError(f"low_wires has {low.size} entries, high_uni_bits {B} rows")
+    who = np.ascontiguousarray(np.broadcast_to(np.asarray(party_of, np.int32), (B, depth)).reshape(-1))
+    flat = [a.reshape((B * depth,) + a.shape[2:]) for a in arrs]
+    Pn = ck.parties * ck.params.lwe_size
+    eng = ck.engine(device)
+    if getattr(eng, "_mk_key_extra", None) == B * depth:
+        eng.mk_tgsw_expand_update(Pn, np.stack([part.public_b for part in ck._parts]), who, *flat)
+    else:
+        _mk_load_key_selectors(ck, flat, who, "device", device)
+    eng.mk_rot_net_level(tree_net(depth), Pn + np.arange(B * depth, dtype=np.int32).reshape(B, depth), table_first=np.full(B, int(table_slot), np.int32),
+                         out_form=0, out_first=int(work_slot))
+    eng.mk_blind_rotate_level(int(work_slot) + np.arange(B, dtype=np.int32), np.arange(B + 1, dtype=np.int32), low, np.ones(B, np.int32),
+                              sel=np.arange(Pn, dtype=np.int32), out_form=2, out_wires=out_wires)
+    return eng
