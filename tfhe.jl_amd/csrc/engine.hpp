@@ -20,10 +20,11 @@
 //   engine_mk_rot_net.hip   the same networks with monomial edges under a multi-key cloud key                          ("mk rot net")
 //   engine_blind_rotate.hip   the blind rotation of the caller's TLWE accumulators by LWE samples, on the caller's selectors  ("blind rotate")
 //   engine_mk_blind_rotate.hip   the same rotation of MK TLWE accumulators under a multi-key cloud key                  ("mk blind rotate")
-//   engine_tlwe_levels.hip    the device-resident TLWE table and the blind rotation between it and the wire table (tfhe_tlwe_*, tfhe_blind_rotate_level;
-//                             tfhe_rot_net_level is engine_rot_net.hip's, tfhe_tgsw_update engine_keys.hip's)              ("tlwe levels")
-//   engine_mk_tlwe_levels.hip   the same under a multi-key cloud key: the MK TLWE table and tfhe_mk_blind_rotate_level (tfhe_mk_tlwe_*;
-//                             tfhe_mk_rot_net_level is engine_mk_rot_net.hip's, tfhe_mk_tgsw_update / _expand_update engine_keys.hip's)  ("mk tlwe levels")
+//   engine_tlwe_levels.hip    the device-resident TLWE table of both kinds and the blind rotation between it and the wire table (tfhe_tlwe_*,
+//                             tfhe_mk_tlwe_*, tfhe_blind_rotate_level; tfhe_rot_net_level is engine_rot_net.hip's, tfhe_tgsw_update
+//                             engine_keys.hip's)                                                                            ("tlwe levels")
+//   engine_mk_tlwe_levels.hip   the rotation under a multi-key cloud key: tfhe_mk_blind_rotate_level (tfhe_mk_rot_net_level is
+//                             engine_mk_rot_net.hip's, tfhe_mk_tgsw_update / _expand_update engine_keys.hip's)              ("mk tlwe levels")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
 //   leveled_run.hpp       host-only: the one runner behind the twelve leveled entry points (workspaces, uploads, level loop, download)
 //   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share
@@ -211,14 +212,15 @@ struct tfhe_ctx {
     int32_t *d_wires = nullptr; int64_t num_wires = 0;
     int wires_parties = 0;
     size_t wire_words() const { return wires_parties ? (size_t)wires_parties * P.n + 1 : (size_t)P.n + 1; }
-    // device-resident TLWE table of the leveled half (tfhe_tlwe_alloc, engine_tlwe_levels.hip): int32 [tlwe_slots][k+1][N], single-key,
-    // one-device contexts only; tfhe_rot_net_level and tfhe_blind_rotate_level read and write it
-    int32_t *d_tlwe = nullptr; int64_t tlwe_slots = 0;
-    // its multi-key form (tfhe_mk_tlwe_alloc, engine_mk_tlwe_levels.hip): int32 [mk_tlwe_slots][P+1][N] for the parties of the multi-key
-    // bootstrapping key loaded when it was allocated (mk_tlwe_parties, as wires_parties for the wires); tfhe_mk_rot_net_level and
-    // tfhe_mk_blind_rotate_level read and write it
-    int32_t *d_mk_tlwe = nullptr; int64_t mk_tlwe_slots = 0;
-    int mk_tlwe_parties = 0;
+    // device-resident TLWE table of the leveled half (tfhe_tlwe_alloc / tfhe_mk_tlwe_alloc, engine_tlwe_levels.hip): int32 [slots][k+1][N],
+    // or [slots][P+1][N] on a multi-key context for the parties of the multi-key bootstrapping key loaded when it was allocated
+    // (parties = P, as wires_parties for the wires; 0 = single-key samples).  One-device contexts only; a context is single-key or
+    // multi-key for life, so it owns one table.  The level network and level rotation calls read and write it.
+    struct TlweTable {
+        int32_t *d = nullptr; int64_t slots = 0;
+        int parties = 0;
+    } tlwe;
+    size_t sample_words() const { return (size_t)(tlwe.parties ? tlwe.parties + 1 : P.k + 1) * P.N; }
 
     // workspaces
     DevBuf bara, ext, map, io[4], diag, abar, mk_acc, spec;

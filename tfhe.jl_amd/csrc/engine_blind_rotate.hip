@@ -6,96 +6,9 @@
 #include "engine.hpp"
 #include "kernels_blind_rotate_tlwe.hpp"
 #include "leveled_checks.hpp"
+#include "rotate_run.hpp"
 
 static const char *const WHO = "blind_rotate_batch";
-enum { ROTATE_MAX_STEPS = 65536 };
-
-// One validated call on a device context: one launch over B rows, then the keyswitch of the B n_out extractions if asked.  The
-// workspace protocol, the timing slots and the download are leveled_run.hpp's, for a call that is one launch and not a level loop.
-static int32_t run_rotate(tfhe_ctx *c, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t steps, int32_t in_form,
-                          const int32_t *sel, int32_t n_out, int32_t *out, int64_t B, int32_t out_form)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const int N = c->P.N, M = N / 2 > 0 ? N / 2 : 1, K1 = c->P.k + 1;
-    const size_t sample = (size_t)K1 * N, ext_w = (size_t)c->P.k * N + 1, ks_w = (size_t)c->P.n + 1;
-    const size_t B_ = (size_t)B, G = B_ * (size_t)n_out, row_w = (size_t)steps + 1;
-    const bool fits = leveled::lds_bytes(N, K1) <= 160 * 1024;
-    const bool spec_lds = c->anyn_spec < 0 ? fits : (c->anyn_spec == 0 && fits);      // option anyn_spec: 1 = accumulators in global memory
-    auto up = [](size_t words) { return (words + 63) / 64 * 64; };
-    // e0 [B n_out] (the keyswitch's identity map) | acc_index [B] | sel [steps]
-    const size_t o_idx = up(G), o_sel = o_idx + up(B_), map_bytes = (o_sel + (size_t)steps) * 4;
-    const size_t acc_bytes = (size_t)T * sample * 4;
-    const LvlWant want[] = {
-        {&c->lvl_data, acc_bytes},
-        {&c->lvl_ws[0], B_ * 2 * sample * 4},
-        {&c->lvl_ws[1], out_form == 0 ? B_ * sample * 4 : 0},
-        {&c->lvl_spec, spec_lds ? 0 : B_ * K1 * M * sizeof(cplx)},
-        {&c->bara, B_ * row_w * 4},
-        {&c->ext, out_form >= 1 ? G * ext_w * 4 : 0},
-        {&c->io[3], out_form == 2 ? G * ks_w * 4 : 0},
-        {&c->map, map_bytes},
-    };
-    { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }       // (the workspaces may still be in use by a call on another stream)
-    int32_t rc = leveled_reserve(c, WHO, want, (int)(sizeof want / sizeof want[0]));
-    if (rc) return rc;
-
-    rc = ensure_host_map(c, map_bytes);
-    if (rc) return rc;
-    int32_t *h = (int32_t *)c->h_map;
-    for (size_t r = 0; r < G; r++) h[r] = (int32_t)r;
-    if (acc_index) memcpy(h + o_idx, acc_index, B_ * 4);
-    else memset(h + o_idx, 0, B_ * 4);
-    if (sel) memcpy(h + o_sel, sel, (size_t)steps * 4);
-    else for (int32_t i = 0; i < steps; i++) h[o_sel + i] = i;
-    HIP_TRY(c, hipMemcpyAsync(c->map.p, c->h_map, map_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->lvl_data.p, acc, acc_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->bara.p, rows, B_ * row_w * 4, hipMemcpyHostToDevice, s));
-    const int32_t *d_map = (const int32_t *)c->map.p;
-
-    leveled::RotateArgs a;
-    a.in = (const int32_t *)c->lvl_data.p;
-    a.row_index = d_map + o_idx;
-    a.sel = d_map + o_sel;
-    a.tgsw = c->d_tgsw;
-    a.out = out_form == 0 ? (int32_t *)c->lvl_ws[1].p : nullptr;
-    a.ext = out_form == 0 ? nullptr : (int32_t *)c->ext.p;
-    a.spec_g = spec_lds ? nullptr : (cplx *)c->lvl_spec.p;
-    a.wtab = c->d_anyn_tab; a.twist = c->d_anyn_tab + N / 2;
-    a.g = c->g;
-    a.row_words = (int64_t)sample;
-    a.L = c->P.bs_l; a.log2N = ilog2i(N);
-    a.nodes_out = 1;
-    a.rows = (const int32_t *)c->bara.p;
-    a.ws = (int32_t *)c->lvl_ws[0].p;
-    a.K1 = K1, a.steps = steps, a.in_form = in_form, a.log2_n_out = ilog2i(n_out);
-    const size_t lds = leveled::lds_bytes(N, spec_lds ? K1 : 0);
-    if (lds > 64 * 1024) LDS_TRY(c, lds, leveled::tlwe_rotate_kernel);
-    const unsigned nt = (unsigned)anyn::threads_for(N);
-
-    next_timing_slot(c);
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    hipLaunchKernelGGL(leveled::tlwe_rotate_kernel, dim3((unsigned)B_), dim3(nt), lds, s, a);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    if (out_form == 2) {
-        rc = launch_keyswitch(c, G, d_map, nullptr, nullptr, (const int32_t *)c->ext.p, (int32_t *)c->io[3].p, s);
-        if (rc) return rc;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[3], s));
-    if (out_form == 0) HIP_TRY(c, hipMemcpyAsync(out, c->lvl_ws[1].p, B_ * sample * 4, hipMemcpyDeviceToHost, s));
-    else if (out_form == 1) HIP_TRY(c, hipMemcpyAsync(out, c->ext.p, G * ext_w * 4, hipMemcpyDeviceToHost, s));
-    else HIP_TRY(c, hipMemcpyAsync(out, c->io[3].p, G * ks_w * 4, hipMemcpyDeviceToHost, s));
-    rc = leave_stream(c, s);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    commit_timing_slot(c);
-    c->last_rotations = B;
-    c->diag_rows = 0;
-    name_kernel(c, "tlwe_rotate_kernel(N=%d,k=%d,l=%d,steps=%d%s)", N, c->P.k, c->P.bs_l, steps, spec_lds ? "" : ",spec=global");
-    return TFHE_OK;
-}
 
 int32_t tfhe_blind_rotate_batch(tfhe_ctx *c, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t steps, int32_t in_form,
                                 const int32_t *sel, int32_t n_out, int32_t *out, int64_t B, int32_t out_form) try
@@ -106,38 +19,15 @@ int32_t tfhe_blind_rotate_batch(tfhe_ctx *c, const int32_t *acc, int64_t T, cons
     if (B > 0 && (!acc || !rows || !out)) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL argument (acc, rows, out)", WHO);
     int32_t rc = leveled_state(c, WHO);
     if (rc) return rc;
-    const int N = c->P.N;
-    if (steps < 1 || steps > ROTATE_MAX_STEPS) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: steps = %d (1 ... %d)", WHO, steps, (int)ROTATE_MAX_STEPS);
-    if (in_form < 0 || in_form > 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: in_form = %d (0 LWE samples, 1 exponents)", WHO, in_form);
-    if (out_form < 0 || out_form > 2) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: out_form = %d (0 TLWE, 1 extracted, 2 key-switched)", WHO, out_form);
-    if (T < 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: T = %lld (at least one accumulator)", WHO, (long long)T);
-    if (T > 2147483647LL) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: T = %lld accumulators (at most 2^31 - 1)", WHO, (long long)T);
-    if (n_out < 1 || n_out > 32 || (n_out & (n_out - 1)) || (n_out > 1 && n_out > N / 4))
-        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: n_out = %d (a power of two, at most 32, and 1 or at most N / 4 = %d)", WHO, n_out, N / 4);
-    if (out_form == 0 && n_out != 1) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: n_out = %d with out_form 0 (the accumulator is one sample: n_out must be 1)", WHO, n_out);
-    if ((double)B * (double)n_out > 2147483647.0)
-        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: B * n_out = %.0f rows exceed one launch", WHO, (double)B * (double)n_out);
-    if (!c->d_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (tfhe_tgsw_load)", WHO);
-    if (out_form == 2 && !c->have_ks()) return c->set_err(TFHE_ERR_NO_KEY, "%s: out_form 2 needs the keyswitch key", WHO);
-    if (sel) {
-        for (int32_t i = 0; i < steps; i++)
-            if (sel[i] < 0 || sel[i] >= c->tgsw_count)
-                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: sel[%d] = %d is outside the %lld loaded selectors", WHO, (int)i, sel[i], (long long)c->tgsw_count);
-    } else if (steps > c->tgsw_count) {
-        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: sel NULL names selector i for step i, steps = %d, %lld selectors are loaded", WHO, steps, (long long)c->tgsw_count);
-    }
-    if (acc_index)
-        for (int64_t g = 0; g < B; g++)
-            if (acc_index[g] < 0 || acc_index[g] >= T)
-                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: acc_index[%lld] = %d is outside [0, %lld)", WHO, (long long)g, acc_index[g], (long long)T);
-    if (in_form == 1)
-        for (int64_t g = 0; g < B; g++)
-            for (int32_t i = 0; i <= steps; i++) {
-                const int32_t e = rows[g * ((int64_t)steps + 1) + i];
-                if (e < 0 || e >= 2 * N)
-                    return c->set_err(TFHE_ERR_INVALID_ARG, "%s: rows[%lld][%d] = %d is outside [0, %d) (in_form 1: exponents)", WHO, (long long)g, (int)i, e, 2 * N);
-            }
-    if (B == 0) return TFHE_OK;
-    return run_rotate(c, acc, T, acc_index, rows, steps, in_form, sel, n_out, out, B, out_form);
+    rc = rotate_batch_check(c, WHO, SINGLE_KEY, T, acc_index, rows, steps, in_form, sel, n_out, B, out_form);
+    if (rc || B == 0) return rc;
+    RotatePlan p = {single_key_shape(c, "tlwe_rotate_kernel"), steps, sel, n_out, out_form, B};
+    p.acc = acc, p.T = T, p.acc_index = acc_index, p.rows = rows, p.in_form = in_form, p.out = out;
+    return run_rotation<leveled::RotateArgs, leveled::tlwe_rotate_kernel>(c, WHO, p, [&](leveled::RotateArgs &a, const int32_t *d_rows, const int32_t *) {
+        a.tgsw = c->d_tgsw;
+        a.rows = d_rows;
+        a.ws = (int32_t *)c->lvl_ws[0].p;
+        a.K1 = p.shape.polys, a.steps = steps, a.in_form = in_form, a.log2_n_out = ilog2i(n_out);
+    });
 }
 ABI_CATCH(c, "tfhe_blind_rotate_batch")

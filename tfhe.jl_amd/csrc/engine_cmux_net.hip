@@ -28,12 +28,12 @@ int32_t tfhe_cmux_net_batch(tfhe_ctx *c, const int32_t *data, int64_t T, int32_t
     if (rc) return rc;
     if (B == 0) return TFHE_OK;
     LevelPlan p = {data, T, E, table_index, false, sel, V, widths, levels, "the widest level", nodes, 3};
-    plan_single_key(p, c, "cmux_net_level_kernel");
+    p.shape = single_key_shape(c, "cmux_net_level_kernel");
     p.B = B, p.out = out, p.out_form = out_form;
     return run_leveled<leveled::NetArgs, leveled::cmux_net_level_kernel>(c, WHO, p, [&](leveled::NetArgs &a, int, const int32_t *d_nodes) {
         a.tgsw = c->d_tgsw;
         a.nodes = d_nodes;
-        a.K1 = p.polys;
+        a.K1 = p.shape.polys;
         a.V = V;
     });
 }

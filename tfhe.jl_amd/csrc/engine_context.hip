@@ -320,8 +320,7 @@ void tfhe_ctx_destroy(tfhe_ctx *c)
     if (c->d_bk) (void)hipFree(c->d_bk);
     release(c->ks);
     if (c->d_wires) (void)hipFree(c->d_wires);
-    if (c->d_tlwe) (void)hipFree(c->d_tlwe);
-    if (c->d_mk_tlwe) (void)hipFree(c->d_mk_tlwe);
+    if (c->tlwe.d) (void)hipFree(c->tlwe.d);
     if (c->d_mk_bk) (void)hipFree(c->d_mk_bk);
     if (c->d_tgsw) (void)hipFree(c->d_tgsw);
     mk_tgsw_drop(c);

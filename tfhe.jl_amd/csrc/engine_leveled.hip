@@ -37,11 +37,11 @@ static int32_t run_tree(tfhe_ctx *c, const char *who, const int32_t *in, int64_t
     int32_t widths[12];
     tree_widths(widths, depth);
     LevelPlan p = {in, in_rows, d0_zero ? 1 : 1 << depth, row_index, d0_zero, sel, depth, widths, depth, "2^(depth-1)", nullptr, 0};
-    plan_single_key(p, c, "cmux_level_kernel");
+    p.shape = single_key_shape(c, "cmux_level_kernel");
     p.B = B, p.out = out, p.out_form = out_form;
     return run_leveled<leveled::Args, leveled::cmux_level_kernel>(c, who, p, [&](leveled::Args &a, int lv, const int32_t *) {
         a.tgsw = c->d_tgsw;
-        a.K1 = p.polys;
+        a.K1 = p.shape.polys;
         a.depth = depth, a.level = lv;
         a.d0_zero = d0_zero ? 1 : 0;
     });

@@ -31,7 +31,7 @@ int32_t tfhe_mk_cmux_net_batch(tfhe_ctx *c, const int32_t *data, int64_t T, int3
     if (rc) return rc;
     if (B == 0) return TFHE_OK;
     LevelPlan p = {data, T, E, table_index, false, sel, V, widths, levels, "the widest level", nodes, 3};
-    plan_multi_key(p, c, "mk_cmux_net_level_kernel");
+    p.shape = multi_key_shape(c, "mk_cmux_net_level_kernel");
     p.B = B, p.out = out, p.out_form = out_form;
     return run_leveled<leveled::MkNetArgs, leveled::mk_cmux_net_level_kernel>(c, WHO, p, [&](leveled::MkNetArgs &a, int, const int32_t *d_nodes) {
         a.tgsw = c->d_mk_tgsw;

@@ -14,7 +14,7 @@ static int32_t run_mk_tree(tfhe_ctx *c, const char *who, const int32_t *in, int6
     int32_t widths[12];
     tree_widths(widths, depth);
     LevelPlan p = {in, in_rows, d0_zero ? 1 : 1 << depth, row_index, d0_zero, sel, depth, widths, depth, "2^(depth-1)", nullptr, 0};
-    plan_multi_key(p, c, "mk_cmux_level_kernel");
+    p.shape = multi_key_shape(c, "mk_cmux_level_kernel");
     p.B = B, p.out = out, p.out_form = out_form;
     return run_leveled<leveled::MkArgs, leveled::mk_cmux_level_kernel>(c, who, p, [&](leveled::MkArgs &a, int lv, const int32_t *) {
         a.tgsw = c->d_mk_tgsw;

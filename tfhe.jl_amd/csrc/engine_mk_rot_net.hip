@@ -7,7 +7,6 @@
 #include "kernels_mk_rot_net.hpp"
 #include "leveled_run.hpp"
 #include "leveled_checks.hpp"
-#include <unordered_set>
 
 static const char *const WHO = "mk_rot_net_batch";
 
@@ -33,7 +32,7 @@ int32_t tfhe_mk_rot_net_batch(tfhe_ctx *c, const int32_t *data, int64_t T, int32
     if (rc) return rc;
     if (B == 0) return TFHE_OK;
     LevelPlan p = {data, T, E, table_index, false, sel, V, widths, levels, "the widest level", nodes, 5};
-    plan_multi_key(p, c, "mk_rot_net_level_kernel");
+    p.shape = multi_key_shape(c, "mk_rot_net_level_kernel");
     p.B = B, p.out = out, p.out_form = out_form;
     return run_leveled<leveled::MkRotNetArgs, leveled::mk_rot_net_level_kernel>(c, WHO, p, [&](leveled::MkRotNetArgs &a, int, const int32_t *d_nodes) {
         a.tgsw = c->d_mk_tgsw;
@@ -57,56 +56,29 @@ int32_t tfhe_mk_rot_net_level(tfhe_ctx *c, const int32_t *table_first, int32_t E
 {
     ENTER_CTX(c);
     const char *const who = WHO_LEVEL;
+    const LevelKind &K = MULTI_KEY;
     if (B < 0) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: B = %lld is negative", who, (long long)B);
     if (!widths || !nodes) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL network (widths, nodes)", who);
     if (B > 0 && !sel) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL argument (sel)", who);
-    int32_t rc = mk_level_state(c, who, out_form == 2, out_form == 2);
+    int32_t rc = level_state(c, who, K, out_form == 2, out_form == 2);
     if (rc) return rc;
     if (out_form != 0 && out_form != 2)
-        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: out_form = %d (0 into MK TLWE slots, 2 key-switched into wires; extracted rows have no table)", who, out_form);
+        return c->set_err(TFHE_ERR_INVALID_ARG, "%s: out_form = %d (0 into %s slots, 2 key-switched into wires; extracted rows have no table)", who, out_form, K.tlwe);
     size_t total_nodes = 0;
     rc = rot_check_netlist(c, who, 1, E, widths, levels, nodes, V, c->P.N, B, out_form, &total_nodes);
     if (rc) return rc;
-    const int64_t slots = c->mk_tlwe_slots, F = widths[levels - 1], G = B * F;
-    if (E > slots) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: E = %d entries, the MK TLWE table has %lld slots", who, E, (long long)slots);
-    if (table_first)
-        for (int64_t g = 0; g < B; g++)
-            if (table_first[g] < 0 || table_first[g] > slots - E)
-                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: table_first[%lld] = %d: slots [%d, %d + %d) are outside the table of %lld slots", who, (long long)g,
-                                  table_first[g], table_first[g], table_first[g], E, (long long)slots);
-    if (B > 0 && out_form == 0) {
-        if (out_first < 0 || out_first > slots || G > slots - out_first)
-            return c->set_err(TFHE_ERR_INVALID_ARG, "%s: output slots [%lld, %lld + %lld) are outside the table of %lld slots", who, (long long)out_first,
-                              (long long)out_first, (long long)G, (long long)slots);
-        for (int64_t g = 0; g < B; g++) {
-            const int64_t lo = table_first ? table_first[g] : 0;
-            if (lo < out_first + G && out_first < lo + E)
-                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: output slots [%lld, %lld + %lld) meet the slots [%lld, %lld + %d) that row %lld reads", who,
-                                  (long long)out_first, (long long)out_first, (long long)G, (long long)lo, (long long)lo, E, (long long)g);
-            if (!table_first) break;      // (every row reads the same range)
-        }
-    }
-    if (B > 0 && out_form == 2) {
-        if (!out_wires) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: NULL out_wires with out_form 2", who);
-        alloc_checkpoint();
-        std::unordered_set<int32_t> written;
-        written.reserve((size_t)G * 2);
-        for (int64_t r = 0; r < G; r++) {
-            if (out_wires[r] < 0 || out_wires[r] >= c->num_wires)
-                return c->set_err(TFHE_ERR_INVALID_ARG, "%s: output %lld is wire %d, outside the table of %lld wires", who, (long long)r, out_wires[r], (long long)c->num_wires);
-            if (!written.insert(out_wires[r]).second) return c->set_err(TFHE_ERR_INVALID_ARG, "%s: wire %d written twice in one call", who, out_wires[r]);
-        }
-    }
-    if (!c->d_mk_tgsw) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (tfhe_mk_tgsw_load)", who);
-    if (out_form == 2 && !c->have_mk_ks()) return c->set_err(TFHE_ERR_NO_KEY, "%s: out_form 2 needs the multi-key keyswitch key", who);
-    rc = net_check_rows(c, who, sel, V, B, c->mk_tgsw_count, nullptr, 1);
+    rc = net_level_check(c, who, K, table_first, E, B * widths[levels - 1], B, out_form, out_first, out_wires);
+    if (rc) return rc;
+    rc = level_keys_check(c, who, K, out_form);
+    if (rc) return rc;
+    rc = net_check_rows(c, who, sel, V, B, K.selectors(c), nullptr, 1);
     if (rc) return rc;
     if (B == 0) return TFHE_OK;
     LevelPlan p = {nullptr, 1, E, table_first, false, sel, V, widths, levels, "the widest level", nodes, 5};
-    plan_multi_key(p, c, "mk_rot_net_level_kernel");
+    p.shape = multi_key_shape(c, "mk_rot_net_level_kernel");
     p.B = B, p.out = nullptr, p.out_form = out_form;
-    p.d_data = c->d_mk_tlwe, p.data_row_words = (int64_t)p.polys * c->P.N;
-    if (out_form == 0) p.d_out = c->d_mk_tlwe + (size_t)out_first * (size_t)p.polys * c->P.N;
+    p.d_data = c->tlwe.d, p.data_row_words = (int64_t)c->sample_words();
+    if (out_form == 0) p.d_out = c->tlwe.d + (size_t)out_first * c->sample_words();
     else p.dst_rows = out_wires, p.d_ks_out = c->d_wires;
     return run_leveled<leveled::MkRotNetArgs, leveled::mk_rot_net_level_kernel>(c, who, p, [&](leveled::MkRotNetArgs &a, int, const int32_t *d_nodes) {
         a.tgsw = c->d_mk_tgsw;

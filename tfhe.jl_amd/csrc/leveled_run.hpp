@@ -3,9 +3,19 @@
 // LevelPlan and names its kernel; the workspace protocol, the uploads, the level loop, the keyswitch, the download and the timing are
 // here and nowhere else.  tfhe_rot_net_level and tfhe_mk_rot_net_level run through it too: their sources and destinations are the
 // device-resident (MK) TLWE and wire tables (LevelPlan's d_* fields), so nothing is uploaded but the maps and nothing is downloaded.
+// (The four single-launch rotations have a runner of their own, rotate_run.hpp, on the same SampleShape.)
 #pragma once
 #include "engine.hpp"
 #include "kernels_leveled_core.hpp"
+
+// The samples a leveled call works on and the kernel it names: single_key_shape / multi_key_shape below.
+struct SampleShape {
+    int polys, nspec;         // polynomials per sample (k + 1 | P + 1); spectrum accumulators per workgroup (k + 1 | 3)
+    size_t ext_w, ks_w;       // words of an extracted row (k N + 1 | P N + 1) and of a key-switched row (n + 1 | P n + 1)
+    const char *kernel;       // tfhe_last_kernel_name: "<kernel>(N=..,<mid_name>=<mid>,l=..[,spec=global])"
+    const char *mid_name;
+    int mid;
+};
 
 // One validated call on a device context: `levels` launches over B rows.  Level 0 reads row g's E samples at data[row_index[g]],
 // level v > 0 the widths[v-1] outputs of the level below; the F = widths[levels-1] outputs of the last level are the result.  A CMUX
@@ -24,11 +34,7 @@ struct LevelPlan {
     const char *widest;       // how the caller's refusal of more than one launch's workgroups names its widest level
     const int32_t *nodes;     // host [sum of widths][words], or NULL with words = 0
     int words;
-    int polys, nspec;         // polynomials per sample (k + 1 | P + 1); spectrum accumulators per workgroup (k + 1 | 3)
-    size_t ext_w, ks_w;       // words of an extracted row (k N + 1 | P N + 1) and of a key-switched row (n + 1 | P n + 1)
-    const char *kernel;       // tfhe_last_kernel_name: "<kernel>(N=..,<mid_name>=<mid>,l=..[,spec=global])"
-    const char *mid_name;
-    int mid;
+    SampleShape shape;
     int64_t B;
     int32_t *out;             // host, by out_form 0: the samples [B F][polys][N], 1: extracted at coefficient 0 [B F][ext_w], 2: that
     int32_t out_form;         //   keyswitched [B F][ks_w] (launch_keyswitch with identity maps)
@@ -50,7 +56,7 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int N = c->P.N, M = N / 2 > 0 ? N / 2 : 1;
-    const size_t sample = (size_t)p.polys * N;
+    const size_t sample = (size_t)p.shape.polys * N;
     size_t wmax[2] = {0, 0}, wall = 0, total_nodes = 0;             // the widest even level, the widest odd level, the widest level
     for (int lv = 0; lv < p.levels; lv++) {
         const size_t w = (size_t)p.widths[lv];
@@ -59,7 +65,7 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
         total_nodes += w;
     }
     const size_t B_ = (size_t)p.B, F = (size_t)p.widths[p.levels - 1], G = B_ * F;
-    const bool fits = leveled::lds_bytes(N, p.nspec) <= 160 * 1024;
+    const bool fits = leveled::lds_bytes(N, p.shape.nspec) <= 160 * 1024;
     const bool spec_lds = c->anyn_spec < 0 ? fits : (c->anyn_spec == 0 && fits);      // option anyn_spec: 1 = accumulators in global memory
     auto up = [](size_t words) { return (words + 63) / 64 * 64; };
     // e0 [B F] (the keyswitch's identity map) | row_index [B] | sel [B][V] | nodes [total][words] | dst_rows [B F] (if any)
@@ -70,9 +76,9 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
         {&c->lvl_data, data_bytes},
         {&c->lvl_ws[0], B_ * wmax[0] * sample * 4},
         {&c->lvl_ws[1], B_ * wmax[1] * sample * 4},
-        {&c->lvl_spec, spec_lds ? 0 : B_ * wall * p.nspec * M * sizeof(cplx)},
-        {&c->ext, p.out_form >= 1 ? G * p.ext_w * 4 : 0},
-        {&c->io[3], p.out_form == 2 && !p.d_ks_out ? G * p.ks_w * 4 : 0},
+        {&c->lvl_spec, spec_lds ? 0 : B_ * wall * p.shape.nspec * M * sizeof(cplx)},
+        {&c->ext, p.out_form >= 1 ? G * p.shape.ext_w * 4 : 0},
+        {&c->io[3], p.out_form == 2 && !p.d_ks_out ? G * p.shape.ks_w * 4 : 0},
         {&c->map, map_bytes},
     };
     { const int32_t rc0 = enter_stream(c, s); if (rc0) return rc0; }       // (the workspaces may still be in use by a call on another stream)
@@ -100,9 +106,9 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
     a.wtab = c->d_anyn_tab; a.twist = c->d_anyn_tab + N / 2;
     a.g = c->g;
     a.L = c->P.bs_l; a.log2N = ilog2i(N);
-    const size_t lds = leveled::lds_bytes(N, spec_lds ? p.nspec : 0);
+    const size_t lds = leveled::lds_bytes(N, spec_lds ? p.shape.nspec : 0);
     if (lds > 64 * 1024) {      // (LDS_TRY's call, spelt out: the macro would name the template parameter, not the kernel, in its error)
-        rc = ensure_dyn_lds(c, (const void *)KERNEL, lds, (std::string("leveled::") + p.kernel).c_str());
+        rc = ensure_dyn_lds(c, (const void *)KERNEL, lds, (std::string("leveled::") + p.shape.kernel).c_str());
         if (rc) return rc;
     }
     const unsigned nt = (unsigned)anyn::threads_for(N);
@@ -136,32 +142,28 @@ static int32_t run_leveled(tfhe_ctx *c, const char *who, const LevelPlan &p, Set
     HIP_TRY(c, hipEventRecord(c->ev[3], s));
     if (p.out_form == 0 ? p.d_out != nullptr : p.d_ks_out != nullptr) { /* the result stays on the device */ }
     else if (p.out_form == 0) HIP_TRY(c, hipMemcpyAsync(p.out, final_tlwe, G * sample * 4, hipMemcpyDeviceToHost, s));
-    else if (p.out_form == 1) HIP_TRY(c, hipMemcpyAsync(p.out, c->ext.p, G * p.ext_w * 4, hipMemcpyDeviceToHost, s));
-    else HIP_TRY(c, hipMemcpyAsync(p.out, c->io[3].p, G * p.ks_w * 4, hipMemcpyDeviceToHost, s));
+    else if (p.out_form == 1) HIP_TRY(c, hipMemcpyAsync(p.out, c->ext.p, G * p.shape.ext_w * 4, hipMemcpyDeviceToHost, s));
+    else HIP_TRY(c, hipMemcpyAsync(p.out, c->io[3].p, G * p.shape.ks_w * 4, hipMemcpyDeviceToHost, s));
     rc = leave_stream(c, s);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     commit_timing_slot(c);
     c->last_rotations = 0;
     c->diag_rows = 0;
-    name_kernel(c, "%s(N=%d,%s=%d,l=%d%s)", p.kernel, N, p.mid_name, p.mid, c->P.bs_l, spec_lds ? "" : ",spec=global");
+    name_kernel(c, "%s(N=%d,%s=%d,l=%d%s)", p.shape.kernel, N, p.shape.mid_name, p.shape.mid, c->P.bs_l, spec_lds ? "" : ",spec=global");
     return TFHE_OK;
 }
 
 // the single-key sample shape of a context: k + 1 polynomials and as many accumulators, rows of k N + 1 and n + 1 words
-inline void plan_single_key(LevelPlan &p, const tfhe_ctx *c, const char *kernel)
+inline SampleShape single_key_shape(const tfhe_ctx *c, const char *kernel)
 {
-    p.polys = p.nspec = c->P.k + 1;
-    p.ext_w = (size_t)c->P.k * c->P.N + 1, p.ks_w = (size_t)c->P.n + 1;
-    p.kernel = kernel, p.mid_name = "k", p.mid = c->P.k;
+    return {c->P.k + 1, c->P.k + 1, (size_t)c->P.k * c->P.N + 1, (size_t)c->P.n + 1, kernel, "k", c->P.k};
 }
 
 // the multi-key one: P + 1 polynomials, three accumulators whatever P is, rows of P N + 1 and P n + 1 words
-inline void plan_multi_key(LevelPlan &p, const tfhe_ctx *c, const char *kernel)
+inline SampleShape multi_key_shape(const tfhe_ctx *c, const char *kernel)
 {
-    p.polys = c->mk_parties + 1, p.nspec = 3;
-    p.ext_w = (size_t)c->mk_parties * c->P.N + 1, p.ks_w = (size_t)c->mk_parties * c->P.n + 1;
-    p.kernel = kernel, p.mid_name = "P", p.mid = c->mk_parties;
+    return {c->mk_parties + 1, 3, (size_t)c->mk_parties * c->P.N + 1, (size_t)c->mk_parties * c->P.n + 1, kernel, "P", c->mk_parties};
 }
 
 // the widths of a CMUX tree of `depth` <= 12 levels: 2^(depth-1-lv)
