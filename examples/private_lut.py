@@ -14,8 +14,13 @@ rotations per address, and the answer comes as three bits.  (Masking the eight l
 lookup in Z_16 needs 17 rotations, but its +-1/64 window does not hold a bootstrap's output noise at this parameter set: it was tried
 and fails to decrypt.)
 
-    python examples/private_lut.py
+    python examples/private_lut.py [--tuned]
+
+--tuned: the two-stage lookup is also run with its rotation on the gates' own kernel and key (two_stage_lookup(..., tuned=True);
+tfhe_bootstrap_acc_batch: the accumulator stays in LDS, the bootstrapping key is not loaded a second time as selectors), the same program
+both ways: equal words, both times.
 """
+import argparse
 import os
 import sys
 import time
@@ -66,7 +71,7 @@ def timed(call):
     return out, (time.perf_counter() - t0) * 1e3
 
 
-def main():
+def main(tuned=False):
     rng = np.random.default_rng(2026)
     params = tfhe.tfhe_parameters_80()
     sk, ck = tfhe.make_key_pair(rng, params)
@@ -91,6 +96,14 @@ def main():
     out_new, ms_new = timed(new_way)
     got_new = tfhe.lut_decrypt(sk, out_new, P)
     assert np.array_equal(got_new, want), "the two-stage lookup decrypts wrongly"
+    ms_tuned = None
+    if tuned:
+        def tuned_way():
+            low = digit_circuit(P).run_batch(ck, digits)[:, 0]
+            return tfhe.two_stage_lookup(ck, enc_table, tgsw, low, P, tuned=True)
+
+        out_tuned, ms_tuned = timed(tuned_way)
+        assert np.array_equal(out_tuned.data, out_new.data), "the tuned rotation's words differ"
 
     hlwe = tfhe.encrypt(rng, sk, hbits.reshape(-1)).data.reshape(ADDRESSES, DEPTH, -1)                                 # [B][3][n+1]
     old_inputs = np.concatenate([digits, hlwe], axis=1)
@@ -102,10 +115,14 @@ def main():
 
     print(f"{ADDRESSES} addresses into a {P << DEPTH}-entry table, all answers correct both ways")
     print(f"  private table, TGSW high bits, computed LWE digit : {ms_new:8.2f} ms  (2 rotations + {(1 << DEPTH) - 1} external products per address)")
+    if tuned:
+        print(f"  the same with the rotation on the gates' kernel   : {ms_tuned:8.2f} ms  (equal words)")
     print(f"  public table, LWE high bits, lookups and MUX gates: {ms_old:8.2f} ms  ({1 + 3 * ((1 << DEPTH) + 2 * ((1 << DEPTH) - 1))} rotations per address)")
     ck.close()
     return ms_new, ms_old
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tuned", action="store_true", help="also run the lookup with its rotation on the gates' kernel (tfhe_bootstrap_acc_batch)")
+    main(ap.parse_args().tuned)

@@ -506,8 +506,8 @@ int32_t tfhe_rot_net_batch(tfhe_ctx *ctx, const int32_t *data, int64_t T, int32_
  * [0, 2N) (the message names row and column); TFHE_ERR_NO_KEY: no selector set, or out_form 2 without the keyswitch key;
  * TFHE_ERR_STATE: a multi-key context, a multi-device context, measure_margin on.  The workspaces (the T accumulators, two samples
  * per row, the rows, the extractions) are compared with the device's free memory BEFORE anything is allocated: TFHE_ERR_NOMEM, the
- * context stays usable.  B = 0 returns TFHE_OK.  The multi-key form is tfhe_mk_blind_rotate_batch below.  Out of scope: forms on
- * the tuned rotation families' key layouts (the call reads the selector set alone). */
+ * context stays usable.  B = 0 returns TFHE_OK.  The multi-key form is tfhe_mk_blind_rotate_batch below.  The form on the gates'
+ * own kernel and key layout is tfhe_bootstrap_acc_batch below (N = 1024, k = 1); this call reads the selector set alone. */
 int32_t tfhe_blind_rotate_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t steps,
                                 int32_t in_form, const int32_t *sel, int32_t n_out, int32_t *out, int64_t B, int32_t out_form);
 
@@ -568,6 +568,35 @@ int32_t tfhe_rot_net_level(tfhe_ctx *ctx, const int32_t *table_first, int32_t E,
 int32_t tfhe_blind_rotate_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,
                                 const int32_t *term_coef, const int32_t *cst, const int32_t *sel, int32_t n_out, int32_t out_form,
                                 const int32_t *out_slot, const int32_t *out_wires, int64_t B);
+
+/* The same two rotations on the gates' own kernel and key (additions within ABI v7): tfhe_blind_rotate_batch and
+ * tfhe_blind_rotate_level with steps = the context's n, in_form 0 and sel NULL, run by the ACC form of the one-wave-per-rotation
+ * kernel of the gates (csrc/kernels_v3.hpp, compiled a third time in csrc/engine_bootstrap_acc.hip): the accumulator stays in LDS for
+ * all n steps and a row costs one wave, not one workgroup.  The calls read the context's bootstrapping key in the layout the gates
+ * read (tfhe_load_bootstrap_key_*, tfhe_keygen_cloud_key); they need no selector set and leave a loaded one alone.  The result
+ * equals, word for word, that of tfhe_blind_rotate_batch(acc, T, acc_index, rows, steps = n, in_form 0, sel NULL, n_out, out, B,
+ * out_form), respectively tfhe_blind_rotate_level(..., sel NULL, ...), where the selector set holds the loaded bootstrapping key's n
+ * entries in order.
+ * Buffer shapes (acc, acc_index, out), the n_out rule, the out_forms 0 / 1 / 2 and, for the level call, the terms, the slot, wire and
+ * overlap rules are those of tfhe_blind_rotate_batch and tfhe_blind_rotate_level above.  rows: host int32 [B][n+1], LWE samples, staged
+ * by tfhe_bootstrap_tv_batch's modulus switch; the level call's rows by tfhe_lut_level's prologue, as tfhe_blind_rotate_level's.
+ * Geometry: the gates' — four rotations per workgroup from 6 rotations per CU up (option "v3_rw": 0 = by batch size, 1, 4), the
+ * l = 2 and l = 3 instantiations and the run-time-l one for every other l (option "br_rt_l").  tfhe_last_kernel_name reports
+ * "blind_rotate_kernel_v3_acc<L,8,tw2reg[,rw4]>" ("<0,...>(l=..)" for the run-time-l form); tfhe_last_rotation_count = B;
+ * tfhe_last_timing_ms: 0 = the rotation, 1 = the keyswitch, 2 = both.
+ * Everything is validated on the host before anything is uploaded, and a refused call changes no slot and no wire.  TFHE_ERR_STATE:
+ * a multi-key context, a multi-device context, measure_margin on (the level call: and a missing or unfit table, as
+ * tfhe_blind_rotate_level), then a shape the kernel does not serve (N != 1024 or k != 1) or a key that is not in its layout (option
+ * "br_anyn") — the message names the shape and points to tfhe_blind_rotate_batch; TFHE_ERR_INVALID_ARG: as the two calls above;
+ * TFHE_ERR_NO_KEY: no bootstrapping key, or out_form 2 without the keyswitch key; TFHE_ERR_NOMEM: the workspaces compared with the
+ * device's free memory before anything is allocated.  B = 0 returns TFHE_OK.  tfhe_get_option(ctx, "bootstrap_acc") answers 1
+ * where the context's shape and key layout are served, 0 otherwise.  Out of scope: the multi-wave families (h2, w2) for small
+ * batches, k = 2, N = 512 and N = 2048, Circuit, and the multi-key forms (tfhe_mk_blind_rotate_batch / _level keep the any-N kernel). */
+int32_t tfhe_bootstrap_acc_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t n_out,
+                                 int32_t out_form, int32_t *out, int64_t B);
+int32_t tfhe_bootstrap_acc_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,
+                                 const int32_t *term_coef, const int32_t *cst, int32_t n_out, int32_t out_form, const int32_t *out_slot,
+                                 const int32_t *out_wires, int64_t B);
 
 /* ---- leveled mode under a multi-key cloud key (additions within ABI v7) ---------------------------------
  * The same two operations on multi-key samples, with no blind rotation: the selectors are the parties' uni-encryptions of address

@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate, tlwe_alloc!, tlwe_upload!, tlwe_download, tgsw_update!, rot_net_level!, blind_rotate_level!, mk_tlwe_alloc!, mk_tlwe_upload!, mk_tlwe_download, mk_tgsw_update!, mk_tgsw_expand_update!, mk_rot_net_level!, mk_blind_rotate_level!
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate, tlwe_alloc!, tlwe_upload!, tlwe_download, tgsw_update!, rot_net_level!, blind_rotate_level!, mk_tlwe_alloc!, mk_tlwe_upload!, mk_tlwe_download, mk_tgsw_update!, mk_tgsw_expand_update!, mk_rot_net_level!, mk_blind_rotate_level!, bootstrap_acc, bootstrap_acc_level!
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -632,6 +632,36 @@ function blind_rotate(gck::GpuCloudKey, acc::Array{Int32,3}, rows::AbstractMatri
 end
 
 """
+    bootstrap_acc(gck, acc::Array{Int32,3}, rows::AbstractMatrix, acc_index=nothing; n_out=1, out_form=2)
+
+`blind_rotate` on the gates' own kernel and key (tfhe_bootstrap_acc_batch): `rows` is `(n+1) x B`, LWE samples, which pass unchanged;
+the steps are the context's `n` under the loaded bootstrapping key and no selector set is read.  `acc`, the 1-based `acc_index`,
+`n_out`, `out_form` and the result are `blind_rotate`'s, and so are the words where the selector set holds the key's `n` entries in
+order.  Served at `N = 1024`, `k = 1` (option "bootstrap_acc").
+"""
+function bootstrap_acc(gck::GpuCloudKey, acc::Array{Int32,3}, rows::AbstractMatrix, acc_index=nothing; n_out::Integer=1, out_form::Integer=2)
+    p = gck.params
+    N, k = p.tlwe_polynomial_degree, p.tlwe_mask_size
+    T = size(acc, 3)
+    size(acc)[1:2] == (N, k + 1) && T >= 1 || error("tfhe_mi355x: accumulators must be N x (k+1) x T")
+    words, B = size(rows)
+    words == p.lwe_size + 1 || error("tfhe_mi355x: rows must be LWE samples, (n+1) x B")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    r = Matrix{Int32}(rows)
+    idx = acc_index === nothing ? nothing : Int32.(collect(acc_index) .- 1)
+    idx === nothing || length(idx) == B || error("tfhe_mi355x: acc_index must have one entry per row")
+    width = out_form == 2 ? p.lwe_size : k * N
+    out = out_form == 0 ? Array{Int32}(undef, N, k + 1, B) : Array{Int32}(undef, width + 1, n_out * B)
+    B == 0 && return out_form == 0 ? out : LweSample[]
+    GC.@preserve acc r idx out @locked gck.ctx check(gck.ctx, ccall((:tfhe_bootstrap_acc_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Int64),
+        gck.ctx, acc, Int64(T), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), r, Int32(n_out), Int32(out_form), out, Int64(B)))
+    out_form == 0 ? out : unflatten(out, LweParams(width))
+end
+
+"""
     tlwe_alloc!(gck, slots)
 
 The device-resident TLWE table of the leveled half (tfhe_tlwe_alloc): `slots` samples of `N x (k+1)` words beside the wire table; 0 frees
@@ -763,6 +793,41 @@ function blind_rotate_level!(gck::GpuCloudKey, acc_slot, term_start, term_wire, 
     GC.@preserve acc start tw tc c s os ow @locked gck.ctx check(gck.ctx, ccall((:tfhe_blind_rotate_level, LIB), Int32,
         (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Int64),
         gck.ctx, acc, start, tw, tc, c === nothing ? Ptr{Int32}(C_NULL) : pointer(c), s === nothing ? Ptr{Int32}(C_NULL) : pointer(s), Int32(n_out),
+        Int32(out_form), os === nothing ? Ptr{Int32}(C_NULL) : pointer(os), ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
+    gck
+end
+
+"""
+    bootstrap_acc_level!(gck, acc_slot, term_start, term_wire, term_coef; cst=nothing, n_out=1, out_form=2, out_slot=nothing, out_wires=nothing)
+
+`bootstrap_acc` between the device-resident tables (tfhe_bootstrap_acc_level): `blind_rotate_level!` on the gates' own kernel and key,
+without a selector set.  Every argument, the 1-based slots and wires and the words are `blind_rotate_level!`'s with `sel = nothing`.
+Synchronous.
+"""
+function bootstrap_acc_level!(gck::GpuCloudKey, acc_slot, term_start, term_wire, term_coef; cst=nothing, n_out::Integer=1, out_form::Integer=2,
+                              out_slot=nothing, out_wires=nothing)
+    p = gck.params
+    N = p.tlwe_polynomial_degree
+    acc = Int32.(collect(acc_slot) .- 1)
+    B = length(acc)
+    start = Int32.(collect(term_start))
+    length(start) == B + 1 && start[1] == 0 && issorted(start) || error("tfhe_mi355x: term_start must be B + 1 non-decreasing entries from 0")
+    T = Int(start[end])
+    tw = Int32.(collect(term_wire) .- 1)
+    tc = Int32.(collect(term_coef))
+    length(tw) >= T && length(tc) >= T || error("tfhe_mi355x: term_wire and term_coef must have term_start[end] entries")
+    c = cst === nothing ? nothing : Int32.(collect(cst))
+    c === nothing || length(c) == B || error("tfhe_mi355x: cst must have one entry per row")
+    out_form == 0 || out_form == 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 into TLWE slots, 2 key-switched into wires)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    os = out_slot === nothing ? nothing : Int32.(collect(out_slot) .- 1)
+    ow = out_wires === nothing ? nothing : Int32.(collect(out_wires) .- 1)
+    out_form != 0 || (os !== nothing && length(os) == B) || error("tfhe_mi355x: out_slot must have one entry per row with out_form 0")
+    out_form != 2 || (ow !== nothing && length(ow) == n_out * B) || error("tfhe_mi355x: out_wires must have n_out * B entries with out_form 2")
+    GC.@preserve acc start tw tc c os ow @locked gck.ctx check(gck.ctx, ccall((:tfhe_bootstrap_acc_level, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Int64),
+        gck.ctx, acc, start, tw, tc, c === nothing ? Ptr{Int32}(C_NULL) : pointer(c), Int32(n_out),
         Int32(out_form), os === nothing ? Ptr{Int32}(C_NULL) : pointer(os), ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
     gck
 end

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "tfhe_mk_blind_rotate_batch", "tfhe_tlwe_alloc", "tfhe_tlwe_upload", "tfhe_tlwe_download", "tfhe_tgsw_update",
     "tfhe_rot_net_level", "tfhe_blind_rotate_level", "tfhe_mk_tlwe_alloc", "tfhe_mk_tlwe_upload", "tfhe_mk_tlwe_download",
     "tfhe_mk_tgsw_update", "tfhe_mk_tgsw_expand_update", "tfhe_mk_rot_net_level", "tfhe_mk_blind_rotate_level",
+    "tfhe_bootstrap_acc_batch", "tfhe_bootstrap_acc_level",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -187,6 +188,9 @@ def load():
         lib.tfhe_mk_tgsw_expand_update.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]
         lib.tfhe_mk_rot_net_level.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, i64, vp, i64]
         lib.tfhe_mk_blind_rotate_level.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64]
+    if hasattr(lib, "tfhe_bootstrap_acc_batch"):
+        lib.tfhe_bootstrap_acc_batch.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, i64]
+        lib.tfhe_bootstrap_acc_level.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -583,6 +587,32 @@ class Engine:
                                                       int(out_form)))
         return out
 
+    def bootstrap_acc(self, acc, rows, acc_index=None, n_out=1, out_form=2):
+        """blind_rotate on the gates' own kernel and key (tfhe_bootstrap_acc_batch): rows are LWE samples int32 [B][n+1], the steps are
+        the context's n under the loaded bootstrapping key, no selector set is read.  acc, acc_index, n_out, out_form and the result
+        are blind_rotate's, and so are the words where the selector set holds the key's n entries in order.  Served where
+        get_option("bootstrap_acc") is 1 (N = 1024, k = 1)."""
+        a = _i32c(acc)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (self.k + 1, self.N):
+            raise ValueError(f"accumulators must be [T][{self.k + 1}][{self.N}], got {a.shape}")
+        r = _i32c(rows)
+        if r.ndim != 2 or r.shape[1] != self.n + 1:
+            raise ValueError(f"rows must be LWE samples [B][{self.n + 1}], got {r.shape}")
+        B = r.shape[0]
+        idx = None
+        if acc_index is not None:
+            idx = _i32c(acc_index).reshape(-1)
+            if idx.size != B:
+                raise ValueError(f"acc_index must have one entry per row ({B}), got {idx.size}")
+        n_out = int(n_out)
+        K = n_out if 1 <= n_out <= 32 else 0
+        shape = {0: (B, self.k + 1, self.N), 1: (B, K, self.k * self.N + 1), 2: (B, K, self.n + 1)}.get(int(out_form), (0,))
+        out = np.empty(shape, np.int32)      # (an out_form or n_out the library refuses: nothing written)
+        self._check(self._lib.tfhe_bootstrap_acc_batch(self._h, _ptr(a), a.shape[0], _ptr(idx), _ptr(r), n_out, int(out_form), _ptr(out), B))
+        return out
+
     # ---- leveled mode on device-resident tables: the TLWE table beside the wire table, levels that read and write both ----
     def tlwe_alloc(self, slots):
         """A device table of TLWE samples int32 [slots][k+1][N] (tfhe_tlwe_alloc); 0 frees it, reallocating discards the contents."""
@@ -649,6 +679,13 @@ class Engine:
         out_wires[g n_out + j].  Synchronous."""
         self._blind_rotate_level(self._lib.tfhe_blind_rotate_level, self.n, acc_slot, term_start, term_wire, term_coef, cst, sel, n_out, out_form,
                                  out_slot, out_wires)
+
+    def bootstrap_acc_level(self, acc_slot, term_start, term_wire, term_coef, cst=None, n_out=1, out_form=2, out_slot=None, out_wires=None):
+        """bootstrap_acc between the tables (tfhe_bootstrap_acc_level): blind_rotate_level on the gates' own kernel and key, without
+        a selector set.  Every argument and the words are blind_rotate_level's with sel None.  Synchronous."""
+        def call(h, acc, start, wire, coef, c, _sel, n_out_, out_form_, os_, ow, B):
+            return self._lib.tfhe_bootstrap_acc_level(h, acc, start, wire, coef, c, n_out_, out_form_, os_, ow, B)
+        self._blind_rotate_level(call, self.n, acc_slot, term_start, term_wire, term_coef, cst, None, n_out, out_form, out_slot, out_wires)
 
     def _blind_rotate_level(self, call, steps, acc_slot, term_start, term_wire, term_coef, cst, sel, n_out, out_form, out_slot, out_wires):
         acc = _i32c(acc_slot).reshape(-1)

@@ -25,6 +25,8 @@
 //                             engine_keys.hip's)                                                                            ("tlwe levels")
 //   engine_mk_tlwe_levels.hip   the rotation under a multi-key cloud key: tfhe_mk_blind_rotate_level (tfhe_mk_rot_net_level is
 //                             engine_mk_rot_net.hip's, tfhe_mk_tgsw_update / _expand_update engine_keys.hip's)              ("mk tlwe levels")
+//   engine_bootstrap_acc.hip    the same rotation on the gates' key and kernel: the ACC form of blind_rotate_kernel_v3, compiled here alone
+//                             (TFHE_ACC_KERNELS), tfhe_bootstrap_acc_batch and tfhe_bootstrap_acc_level                      ("bootstrap acc")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
 //   leveled_run.hpp       host-only: the one runner behind the twelve leveled entry points (workspaces, uploads, level loop, download)
 //   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share
@@ -195,6 +197,9 @@ struct tfhe_ctx {
     }
     // N = 512 with k = 1 (any l) has a tuned kernel of its own (kernels_n512.hpp) and its own key order
     bool n512() const { return !br_anyn && P.parties == 1 && P.N == 512 && P.k == 1; }
+    // the shape blind_rotate_kernel_v3 serves with the key in its layout, on a one-device single-key context: what the ACC form of that
+    // kernel (tfhe_bootstrap_acc_batch / _level, engine_bootstrap_acc.hip) needs; tfhe_get_option "bootstrap_acc"
+    bool bootstrap_acc() const { return kids.empty() && P.parties == 1 && P.N == kN && P.k == 1 && !anyn(); }
 
     // keys (only the layout of the selected keyswitch kernel family stays resident: KsKey)
     cplx *d_bk = nullptr;       size_t bk_polys = 0;
@@ -466,6 +471,7 @@ void mk_tgsw_drop(tfhe_ctx *c);
 struct DiagArgs;
 int32_t prepare_diag(tfhe_ctx *c, size_t R, hipStream_t s, DiagArgs &d);
 void name_kernel(tfhe_ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+int br_inst_l(const tfhe_ctx *c);      // the decomposition-length instantiation of the kernels with a run-time-l form: 2, 3, or 0
 // a TV batch (tfhe_bootstrap_tv_batch): the test polynomials and the table of each rotation of the batch, device pointers
 // A multi-output TV batch (tfhe_bootstrap_tv_multi_batch) adds `bodies`, [R][n_out]: the kernels also write the body coefficients
 // j N / n_out of each rotation there (kernels_common.hpp: store_bodies); NULL for a plain TV batch.
@@ -497,6 +503,7 @@ int32_t run_gates(tfhe_ctx *c, const char *who, const uint8_t *opcodes, int64_t 
                   int32_t *d_out, const int32_t *ia, const int32_t *ib, const int32_t *ic, const int32_t *io, hipStream_t s);
 int32_t launch_linear_prologue(tfhe_ctx *c, bool lut, size_t B, const int32_t *d_start, const int32_t *d_wire, const int32_t *d_coef,
                                const int32_t *d_cst, const int32_t *d_out, hipStream_t s);
+int32_t launch_modswitch(tfhe_ctx *c, size_t B, const int32_t *d_in, hipStream_t s);
 // one level of tfhe_lut_level (tv != NULL; n_out samples per row) or tfhe_linear_level (tv == NULL) as the caller passed it: host arrays,
 // term_start rebased to 0 (engine_circuits.hip validates; run_int_level stages and queues it on a device context)
 struct IntLevel {

@@ -51,7 +51,7 @@ void name_kernel(tfhe_ctx *c, const char *fmt, ...)
 // BASELINE config 4b), with either mask size at N = 1024; the one- and two-waves-per-rotation kernels also exist with the length as a
 // run-time value, taken for every other l and, under option br_rt_l, for l = 2 and 3 too.  (h2, k2 and k2w3 have the tuned lengths only;
 // every other set the reference would accept runs on blind_rotate_kernel_general.)
-static int br_inst_l(const tfhe_ctx *c)
+int br_inst_l(const tfhe_ctx *c)
 {
     return (c->P.bs_l == 2 || c->P.bs_l == 3) && !c->br_rt_l ? c->P.bs_l : 0;
 }

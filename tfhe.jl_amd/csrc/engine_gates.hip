@@ -197,6 +197,15 @@ int32_t launch_prologue(tfhe_ctx *c, size_t R, const int32_t *d_in0, const int32
     return TFHE_OK;
 }
 
+// the modulus switch alone (bootstrap.jl:74-75) of B samples at d_in into the context's bara workspace: tfhe_bootstrap_tv_batch's
+// prologue, for the callers outside this unit (rotate_run.hpp)
+int32_t launch_modswitch(tfhe_ctx *c, size_t B, const int32_t *d_in, hipStream_t s)
+{
+    hipLaunchKernelGGL(modswitch_kernel, dim3((unsigned)B), dim3(256), 0, s, d_in, (int32_t *)c->bara.p, c->P.n, ilog2i(2 * c->P.N));
+    HIP_TRY(c, hipGetLastError());
+    return TFHE_OK;
+}
+
 // integer linear prologue of B rows of a tfhe_lut_level (lut: the modulus-switched combinations into bara) or tfhe_linear_level (the
 // combinations themselves into their output rows of the wire table); device index arrays (kernels_gates.hpp: linear_prologue_kernel)
 int32_t launch_linear_prologue(tfhe_ctx *c, bool lut, size_t B, const int32_t *d_start, const int32_t *d_wire, const int32_t *d_coef,

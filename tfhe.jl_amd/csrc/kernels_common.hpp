@@ -26,14 +26,39 @@ struct WithTv : A {
     int32_t *bodies;          // [R][n_out], or NULL
     int32_t n_out;            // a power of two, 1 <= n_out <= min(32, N / 4) where bodies != NULL
 };
-#ifdef TFHE_TV_KERNELS
+// The ACC form (private-table rotation on a tuned kernel): the translation unit that defines TFHE_ACC_KERNELS
+// (engine_bootstrap_acc.hip) compiles blind_rotate_kernel_v3 a third time, named blind_rotate_kernel_v3_acc, which starts rotation w
+// from X^{-barb} acc[acc_index[w]] on BOTH polynomials of a TLWE sample the caller supplies, and leaves the whole final accumulator
+// and / or its extractions at the coefficients j N / n_out with their masks.  Between the two it is the kernel it was compiled from.
+// WithAcc's `ext` hides the family struct's one-sample rows.
+template <class A>
+struct WithAcc : A {
+    const int32_t *acc;        // [T][2][N] TLWE samples
+    const int32_t *acc_index;  // [R] the accumulator of each rotation, in [0, T); never NULL
+    int32_t *out;              // [.][2][N] the final accumulators, or NULL
+    const int32_t *out_index;  // [R] the row of `out` rotation w writes, or NULL: row w
+    int32_t *ext;              // [R][n_out][N+1] the extractions at coefficients j N / n_out, or NULL
+    int32_t log2_n_out;
+};
+#if defined(TFHE_TV_KERNELS)
 #define TV_KERNEL(name) name##_tv
 #define TV_ARGS(A) WithTv<A>
 constexpr bool kTV = true;
+constexpr bool kACC = false;
+#elif defined(TFHE_ACC_KERNELS)
+#define TV_KERNEL(name) name##_acc
+// (WithAcc<BrArgs> for the kernels on BrArgs, whose ACC form exists; every other family's struct stays itself in that unit — several
+//  have an `acc` of their own — and none of their kernels is instantiated there: AccArgsOf's specialisation follows BrArgs)
+template <class A>
+struct AccArgsOf { using type = A; };
+#define TV_ARGS(A) AccArgsOf<A>::type
+constexpr bool kTV = false;
+constexpr bool kACC = true;
 #else
 #define TV_KERNEL(name) name
 #define TV_ARGS(A) A
 constexpr bool kTV = false;
+constexpr bool kACC = false;
 #endif
 // the test polynomial of rotation w, tv + N tv_index[w] (TV kernels; NULL for the others): the index is read once, by a vector load
 // made wave-uniform
@@ -239,6 +264,10 @@ struct BrArgs {
     int32_t l;            // decomposition length, read by the instantiations with L = 0 (any l at run time)
     int32_t grp_big, grp_q;   // blind_rotate_kernel_k2<.., 7>: workgroups [0, grp_big) hold grp_q + 1 rotations, the others grp_q
 };
+#ifdef TFHE_ACC_KERNELS
+template <>
+struct AccArgsOf<BrArgs> { using type = WithAcc<BrArgs>; };
+#endif
 
 // Issue priority by progress.  The SIMD's arbiter favours the OLDER of its two waves: the first-placed wave of a SIMD runs
 // at nearly the speed of a lone wave (4.7 ms per rotation in blind_rotate_kernel_v3) and the second-placed one takes 7.0 ms,
@@ -349,6 +378,57 @@ __device__ __forceinline__ void extract_mask_poly(int lane, const int32_t *img, 
         const int32_t v = img[kMir + j];
         if (j == 0) ext[0] = v;
         else ext[kN - j] = (int32_t)(0u - (uint32_t)v);
+    }
+}
+// ---- the ACC form's two ends (blind_rotate_kernel_v3_acc; nothing for every other kernel) ------------------------------------------
+// both images of rotation w from the caller's sample: X^{-barb} acc[acc_index[w]] on the mask and the body polynomial alike (tv_coef's
+// rule; store_cur writes the mirror blocks).  The index is read once, by a vector load made wave-uniform, as tv_of reads its own.
+template <class A>
+__device__ __forceinline__ void init_acc(int, int, const A &, size_t, int32_t *) {}
+template <class A>
+__device__ __forceinline__ void init_acc(int lane, int barb, const WithAcc<A> &P, size_t w, int32_t *acc_lds)
+{
+    const int32_t *v = P.acc + (size_t)__builtin_amdgcn_readfirstlane(P.acc_index[w]) * (2 * kN);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        int32_t b[16];
+#pragma unroll
+        for (int m = 0; m < 16; m++) b[m] = tv_coef(v + c * kN, (lane + 64 * m + barb) & (2 * kN - 1), kN);
+        store_cur<16>(lane, b, acc_lds + c * kImg);
+    }
+}
+// the final accumulator of rotation w: both polynomials to out[out_index[w]] (out_index NULL: row w) where `out` is set; where `ext` is
+// set, for j < n_out its extraction at coefficient c = j N / n_out (tlwe.jl:55-59 at c instead of 0): mask word u is coefficient c of
+// X^u a, a[(c - u) mod N] negated when (c - u) mod 2N >= N (leveled::rot_read's rule), and the body is b[c].  One wave, reading its own LDS.
+template <class A>
+__device__ __forceinline__ void store_acc(const A &, size_t, int, const int32_t *) {}
+template <class A>
+__device__ __forceinline__ void store_acc(const WithAcc<A> &P, size_t w, int lane, const int32_t *acc_lds)
+{
+    if (P.out) {
+        const size_t row = P.out_index ? (size_t)__builtin_amdgcn_readfirstlane(P.out_index[w]) : w;
+        int32_t *o = P.out + row * (2 * kN);
+#pragma unroll
+        for (int c = 0; c < 2; c++)
+#pragma unroll
+            for (int m = 0; m < 16; m++) o[c * kN + lane + 64 * m] = acc_lds[c * kImg + kMir + lane + 64 * m];
+    }
+    if (P.ext) {
+        static_assert(kN == 1 << 10, "the shift below");
+        const int n_out = 1 << P.log2_n_out;
+        const int32_t *a = acc_lds + kMir, *b = acc_lds + kImg + kMir;
+#pragma unroll 1
+        for (int j = 0; j < n_out; j++) {
+            const int c = j << (10 - P.log2_n_out);      // (kN = 2^10)
+            int32_t *e = P.ext + (w * n_out + j) * (kN + 1);
+#pragma unroll
+            for (int m = 0; m < 16; m++) {
+                const int u = lane + 64 * m, s = (c - u) & (2 * kN - 1);
+                const int32_t x = a[s & (kN - 1)];
+                e[u] = s < kN ? x : (int32_t)(0u - (uint32_t)x);
+            }
+            if (lane == 0) e[kN] = b[c];
+        }
     }
 }
 

@@ -64,8 +64,12 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
     // registers across the transforms, which have none to spare; the arithmetic is the timed kernel's, instruction for instruction
     double *worst_lds = reinterpret_cast<double *>(xch + kXchElems);        // [64]
     if (MARGIN) worst_lds[lane] = 0.0;
-    init_zero_poly(lane, acc_lds);
-    init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds + kImg);
+    if constexpr (kACC) {
+        init_acc(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds);      // the ACC form: the caller's sample, mask and body
+    } else {
+        init_zero_poly(lane, acc_lds);
+        init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds + kImg);
+    }
     WAVE_LDS_FENCE();
 
     cplx kbuf[16];
@@ -184,10 +188,14 @@ __global__ __launch_bounds__(64 * RW, 2) void TV_KERNEL(blind_rotate_kernel_v3)(
     }
 
     if (padding) return;
-    int32_t *ext = P.ext + w * (kN + 1);
-    extract_mask_poly(lane, acc_lds, ext);
-    if (lane == 0) ext[kN] = acc_lds[kImg + kMir];
-    store_bodies(P, w, lane, acc_lds + kImg + kMir, kN);
+    if constexpr (kACC) {
+        store_acc(P, w, lane, acc_lds);      // the ACC form: the whole accumulator and / or its n_out extractions
+    } else {
+        int32_t *ext = P.ext + w * (kN + 1);
+        extract_mask_poly(lane, acc_lds, ext);
+        if (lane == 0) ext[kN] = acc_lds[kImg + kMir];
+        store_bodies(P, w, lane, acc_lds + kImg + kMir, kN);
+    }
     // (RW = 4: the lane number is not threadIdx.x, which would have to stay alive to the end for diag_end's defaults — one register more than
     //  the tuned DIAG forms have.  The run-time-l DIAG form keeps the defaults and its few spilled bytes: tests/test_resource_usage.py lists it.)
     if constexpr (RW > 1 && L != 0) diag_end<MARGIN>(P.diag, w, MARGIN ? worst_lds[lane] : 0.0, dg_t0, dg_r0, wib == 0 && lane == 0, lane);

@@ -41,8 +41,9 @@ struct LevelKind {
     const char *ks_key;
     const char *no_wires;       // the parenthetical of the "no wire table" refusal
     const char *other_wires;    // what a wire table of the other kind is told
-    bool has_selectors(const tfhe_ctx *c) const { return mk ? c->d_mk_tgsw != nullptr : c->d_tgsw != nullptr; }
-    int64_t selectors(const tfhe_ctx *c) const { return mk ? c->mk_tgsw_count : c->tgsw_count; }
+    bool gate_key = false;      // the selectors are the context's bootstrapping key in the gates' layout, its n entries in order
+    bool has_selectors(const tfhe_ctx *c) const { return gate_key ? c->have_bk : mk ? c->d_mk_tgsw != nullptr : c->d_tgsw != nullptr; }
+    int64_t selectors(const tfhe_ctx *c) const { return gate_key ? c->P.n : mk ? c->mk_tgsw_count : c->tgsw_count; }
     bool has_ks(const tfhe_ctx *c) const { return mk ? c->have_mk_ks() : c->have_ks(); }
 };
 inline const LevelKind SINGLE_KEY = {false, "context is multi-key (leveled operations are single-key)", "TLWE", "tfhe_tlwe_alloc", "tfhe_tgsw_load",
@@ -50,6 +51,9 @@ inline const LevelKind SINGLE_KEY = {false, "context is multi-key (leveled opera
 inline const LevelKind MULTI_KEY = {true, "context is single-key (tfhe_rot_net_level / tfhe_blind_rotate_level are its level calls)", "MK TLWE",
                                     "tfhe_mk_tlwe_alloc", "tfhe_mk_tgsw_load", "the multi-key keyswitch key", "out_form 2 and terms need one",
                                     "the wire table has single-key rows (tfhe_wires_alloc): allocate it with tfhe_mk_wires_alloc"};
+// the single-key calls that rotate on the gates' key and kernel (tfhe_bootstrap_acc_batch / _level): no selector set is read
+inline const LevelKind GATE_KEY = {false, "context is multi-key (leveled operations are single-key)", "TLWE", "tfhe_tlwe_alloc", "tfhe_load_bootstrap_key_i32",
+                                   "the keyswitch key", "out_form 2 and terms need one", "the wire table has multi-key rows (tfhe_mk_wires_alloc)", true};
 
 // what the level calls on the device-resident tables (tfhe_[mk_]rot_net_level, tfhe_[mk_]blind_rotate_level) refuse before they look at
 // their arguments: the state first, then (multi-key) the key that fixes P.  `needs_wires`: the call reads or writes the wire table;
@@ -81,7 +85,7 @@ inline int32_t level_state(tfhe_ctx *c, const char *who, const LevelKind &K, boo
 // the selector set and, for out_form 2, the keyswitch key of a call of kind K: asked for after the call's arguments
 inline int32_t level_keys_check(tfhe_ctx *c, const char *who, const LevelKind &K, int32_t out_form)
 {
-    if (!K.has_selectors(c)) return c->set_err(TFHE_ERR_NO_KEY, "%s: no selector set loaded (%s)", who, K.tgsw_load);
+    if (!K.has_selectors(c)) return c->set_err(TFHE_ERR_NO_KEY, K.gate_key ? "%s: no bootstrapping key loaded (%s)" : "%s: no selector set loaded (%s)", who, K.tgsw_load);
     if (out_form == 2 && !K.has_ks(c)) return c->set_err(TFHE_ERR_NO_KEY, "%s: out_form 2 needs %s", who, K.ks_key);
     // (the keyswitch addresses rows by ITS key's parties, the rotation writes them by the bootstrapping key's: they must agree; level_state
     //  has asked the level calls already)

@@ -483,12 +483,30 @@ def _lwe_rows(lwe):
     return lwe.data if isinstance(lwe, LweSampleArray) else np.asarray(lwe, np.int32)
 
 
-def blind_rotate_lookup(ck, acc, lwe, extra_tgsw=None, acc_index=None, n_out=1, out_form=2, device=0):
+def _tuned_engine(ck, device):
+    """ck's engine where Engine.bootstrap_acc serves its shape and key layout (option "bootstrap_acc"); ValueError elsewhere."""
+    eng = ck.engine(device)
+    if not eng.get_option("bootstrap_acc"):
+        p = ck.params
+        raise ValueError(f"tuned=True: Engine.bootstrap_acc serves N = 1024, k = 1 in the gates' key layout; this context has "
+                         f"N = {p.tlwe_polynomial_degree}, k = {p.tlwe_mask_size} (option bootstrap_acc is 0): use tuned=False")
+    return eng
+
+
+def blind_rotate_lookup(ck, acc, lwe, extra_tgsw=None, acc_index=None, n_out=1, out_form=2, device=0, tuned=False):
     """acc[acc_index[g]] rotated by row g of `lwe` under ck's bootstrapping key (Engine.blind_rotate with in_form 0).  Loads the key's n
     entries as selectors 0 ... n-1 and, behind them, the `extra_tgsw` samples int32 [E][l][k+1][k+1][N] (address bits for a later
     cmux_tree on the same engine: selectors n ... n+E-1), once; then rotates.  acc: int32 [T][k+1][N] (or [k+1][N]); lwe: an
     LweSampleArray or int32 [B][n+1].  out_form 2 (default): an LweSampleArray of B n_out samples under the gate key (row g's output j
-    at g n_out + j); 1: extracted int32 [B][n_out][k N + 1]; 0: the TLWE samples int32 [B][k+1][N]."""
+    at g n_out + j); 1: extracted int32 [B][n_out][k N + 1]; 0: the TLWE samples int32 [B][k+1][N].
+    tuned=True: the same words from Engine.bootstrap_acc, on the gates' own kernel and key; only `extra_tgsw` is loaded as the
+    selector set (selectors 0 ... E-1).  ValueError where get_option("bootstrap_acc") is 0."""
+    if tuned:
+        eng = _tuned_engine(ck, device)
+        if extra_tgsw is not None:
+            eng.tgsw_load(np.asarray(extra_tgsw, np.int32))
+        out = eng.bootstrap_acc(acc, _lwe_rows(lwe), acc_index=acc_index, n_out=n_out, out_form=out_form)
+        return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
     eng = ck.engine(device)
     sels = bootstrap_key_selectors(ck)
     if extra_tgsw is not None:
@@ -502,12 +520,13 @@ def blind_rotate_lookup(ck, acc, lwe, extra_tgsw=None, acc_index=None, n_out=1, 
     return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
 
 
-def two_stage_lookup(ck, tables, high_bits_tgsw, low_lwe, p, out_form=2, device=0):
+def two_stage_lookup(ck, tables, high_bits_tgsw, low_lwe, p, out_form=2, device=0, tuned=False):
     """A table of p 2^d entries addressed by d TGSW-encrypted high bits and one LWE digit of Z_p that gates or lookups computed.
     tables: int32 [2^d][k+1][N], sample h the test polynomial (trivial: tlwe_trivial(make_test_vector(...)); or private_lut_encrypt) of
     the p entries whose high address is h; high_bits_tgsw: int32 [B][d][l][k+1][k+1][N], bit v of row g (bit 0 the lowest); low_lwe: an
     LweSampleArray or int32 [B][n+1] of messages in Z_p (lut_encode).  A CMUX tree with out_form 0 picks row g's sample, the rotation
-    by its low digit reads the entry: 2^d - 1 external products plus one rotation per row.  out_form as blind_rotate_lookup (n_out 1)."""
+    by its low digit reads the entry: 2^d - 1 external products plus one rotation per row.  out_form as blind_rotate_lookup (n_out 1).
+    tuned=True: the rotation by Engine.bootstrap_acc, the selector set holding the address bits alone (blind_rotate_lookup)."""
     a = np.asarray(high_bits_tgsw, np.int32)
     if a.ndim != 6:
         raise ValueError(f"high_bits_tgsw must be [B][depth][l][k+1][k+1][N], got {a.shape}")
@@ -518,6 +537,12 @@ def two_stage_lookup(ck, tables, high_bits_tgsw, low_lwe, p, out_form=2, device=
     if int(p) < 2 or int(p) & (int(p) - 1) or int(p) > a.shape[-1] // 2:
         raise ValueError(f"p = {p} (a power of two, 2 ... N/2)")
     n = ck.params.lwe_size
+    if tuned:
+        eng = _tuned_engine(ck, device)
+        eng.tgsw_load(a.reshape((B * depth,) + a.shape[2:]))
+        picked = eng.cmux_tree(tables, np.arange(B * depth, dtype=np.int32).reshape(B, depth), out_form=0)
+        out = eng.bootstrap_acc(picked, rows, acc_index=np.arange(B, dtype=np.int32), out_form=out_form)
+        return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
     eng = ck.engine(device)
     eng.tgsw_load(np.concatenate([bootstrap_key_selectors(ck), a.reshape((B * depth,) + a.shape[2:])]))
     picked = eng.cmux_tree(tables, n + np.arange(B * depth, dtype=np.int32).reshape(B, depth), out_form=0)
@@ -525,14 +550,14 @@ def two_stage_lookup(ck, tables, high_bits_tgsw, low_lwe, p, out_form=2, device=
     return LweSampleArray(out.reshape(-1, out.shape[-1])) if out_form == 2 else out
 
 
-def pbs_to_tlwe(ck, lwe, f, p, q=None, device=0):
+def pbs_to_tlwe(ck, lwe, f, p, q=None, device=0, tuned=False):
     """f(m) of every sample of m in Z_p as a TLWE sample int32 [B][k+1][N]: the rotation of the trivial accumulator (0, test vector)
     with out_form 0.  The test polynomial is constant over each window, so coefficient 0 carries lut_encode(f(m), q) — where
     cmux_lookup / cmux_net_lookup read their `data` and extract: a gate or lookup output becomes a table entry with no packing key and
-    no keyswitch noise.  f: a callable Z_p -> Z_q or an int32 test polynomial [N]."""
+    no keyswitch noise.  f: a callable Z_p -> Z_q or an int32 test polynomial [N].  tuned: as blind_rotate_lookup."""
     N, k = ck.params.tlwe_polynomial_degree, ck.params.tlwe_mask_size
     tv = make_test_vector(f, p, N, q) if callable(f) else np.asarray(f, np.int32)
-    return blind_rotate_lookup(ck, tlwe_trivial(tv, k), lwe, out_form=0, device=device)
+    return blind_rotate_lookup(ck, tlwe_trivial(tv, k), lwe, out_form=0, device=device, tuned=tuned)
 
 
 # ---- under a multi-key cloud key -------------------------------------------------------------------------------------------------
