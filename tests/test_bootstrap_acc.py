@@ -7,7 +7,12 @@ Engine.bootstrap_tv_multi.  Every comparison is word for word.
 The kernel exists at N = 1024, k = 1 only.  (l, beta) = (2, 10), (3, 8), (4, 6) take the L = 2 and L = 3 instantiations and the run-time-l
 one; n = 5 is an odd step count inside one lockstep period of four steps, n = 9 crosses the barriers at steps 0, 4 and 8.  B = 5 runs as
 five workgroups (v3_rw 1) and as two workgroups of four waves with three padding waves (v3_rw 4).  The schoolbook words of a case are
-computed once and shared by the tests of that case."""
+computed once and shared by the tests of that case.
+
+Section 3b holds the edges that the random programs of tests/test_bootstrap_acc_programs.py cannot reach: the switch of v3_rw 0 to four
+rotations per workgroup at 6 rotations per compute unit (the count read from the HIP runtime), n = 1, 4 and 8 steps, n_out 2, 8, 16 and 32,
+the level form under v3_rw 4 with padding waves and a permuted out_slot, a successful level call on a context without a wire table, and
+workspaces that grow behind a gate level that is still queued; each against the schoolbook alone."""
 import ctypes as C
 import functools
 import inspect
@@ -56,6 +61,12 @@ def _rows(rng, n):
     all-zero row."""
     plant = [0, 1, N, 2 * N - 1]
     x = _words(rng, B_ROWS, n + 1)
+    if n < 4:                                                        # the planted exponents down the rows, at step 0: 1, N, 2N - 1, 0
+        x[0, :n], x[0, n] = _word(1, 2**20 - 1), _word(0)            # (just below a rounding boundary)
+        x[1, :n], x[1, n] = _word(N), _word(N)
+        x[2, :n], x[2, n] = _word(2 * N - 2, 2**20), _word(2 * N - 1)      # (on the boundary: 2N - 2 -> 2N - 1)
+        x[3, :] = 0
+        return x
     x[0, :n] = [_word(plant[i % 4]) for i in range(n)]
     x[0, n] = _word(0)
     x[1, 0], x[1, 1] = _word(3, 2**20 - 1), _word(3, 2**20)          # e 2^21 + 2^20 - 1 -> e, e 2^21 + 2^20 -> e + 1
@@ -84,8 +95,11 @@ def _case(tfhe, l, beta, n):
     x = _rows(rng, n)
     sb = Schoolbook(n, N, K, l, beta, 8, 2, sels)
     exps = np.array([sb.modswitch(r) for r in x], np.int64) % (2 * N)
-    assert list(exps[0, :4]) == [0, 1, N, 2 * N - 1] and exps[0, n] == 0 and list(exps[1, :2]) == [3, 4] and exps[1, n] == N
-    assert exps[2, n] == 2 * N - 1 and list(exps[2, :4]) == [1, N, 2 * N - 1, 0] and not exps[3].any()
+    if n < 4:
+        assert list(exps[:4, 0]) == [1, N, 2 * N - 1, 0] and list(exps[:4, n]) == [0, N, 2 * N - 1, 0] and not exps[3].any()
+    else:
+        assert list(exps[0, :4]) == [0, 1, N, 2 * N - 1] and exps[0, n] == 0 and list(exps[1, :2]) == [3, 4] and exps[1, n] == N
+        assert exps[2, n] == 2 * N - 1 and list(exps[2, :4]) == [1, N, 2 * N - 1, 0] and not exps[3].any()
     ref = Rotation(N, K, l, beta, sels)
     want = np.stack([ref.rotate_lwe(acc[ACC_INDEX[g]], x[g]) for g in range(B_ROWS)])
     return dict(rng=rng, sk=sk, ck=ck, eng=eng, sels=sels, acc=acc, tv=tv, x=x, ref=ref, want=want)
@@ -151,18 +165,19 @@ def test_gpu_trivial_accumulator_equals_bootstrap_tv_multi(tfhe, l, beta):
 
 
 # ---- 3. GPU: the level form ---------------------------------------------------------------------------------------------------------
-def _tables(c, n):
-    """The case's engine with a TLWE table (the three accumulators, then encryptions) and a wire table (arbitrary rows, the case's rows in
-    wires 1 ... 5)."""
+def _tables(c, n, wires=WIRES, eng=None):
+    """The case's engine (or `eng`) with a TLWE table (the three accumulators, then encryptions) and a wire table (arbitrary rows, the
+    case's rows in wires 1 ... 5); wires 0: no wire table."""
     from tfhe_jl_amd import leveled
-    eng, rng = c["eng"], c["rng"]
+    eng, rng = eng or c["eng"], c["rng"]
     full = np.ascontiguousarray(np.concatenate([c["acc"], leveled.tlwe_encrypt(rng, c["sk"], _words(rng, SLOTS - 3, N))]))
-    allw = _words(rng, WIRES, n + 1)
+    allw = _words(rng, max(wires, 1 + B_ROWS), n + 1)
     allw[1:1 + B_ROWS] = c["x"]
     eng.tlwe_alloc(SLOTS)
     eng.tlwe_upload(0, full)
-    eng.wires_alloc(WIRES)
-    eng.wires_upload(0, allw)
+    eng.wires_alloc(wires)
+    if wires:
+        eng.wires_upload(0, allw)
     return full, allw
 
 
@@ -219,6 +234,231 @@ def test_gpu_bootstrap_acc_level_equals_blind_rotate_level(tfhe):
         eng.set_option("v3_rw", 0)
         eng.tlwe_alloc(0)
         eng.wires_alloc(0)
+
+
+# ---- 3b. GPU: the edges random programs do not reach (tests/test_bootstrap_acc_programs.py) -------------------------------------------
+def _cu_count():
+    hip = C.CDLL("libamdhip64.so")
+    count = C.c_int(0)
+    assert hip.hipDeviceGetAttribute(C.byref(count), 63, 0) == 0 and count.value > 0      # hipDeviceAttributeMultiprocessorCount
+    return count.value
+
+
+def _extractions(ref, accs, n_out):
+    """extract_at of every final accumulator at the coefficients j N / n_out: int32 [B][n_out][N+1]."""
+    return np.stack([[ref.extract_at(w, j * (N // n_out)) for j in range(n_out)] for w in accs]).astype(np.int32)
+
+
+def _level_want(c, full, allw, acc_slot, start, wire, coef, cst):
+    """The schoolbook's final accumulators of a level call's rows: int32 [B][2][N]."""
+    rows = form_rows(allw, start, wire, coef, cst)
+    return np.stack([c["ref"].rotate_lwe(full[a], rows[g]) for g, a in enumerate(acc_slot)]).astype(np.int32)
+
+
+@pytest.mark.gpu
+def test_gpu_batch_size_switch_to_four_rotations_per_workgroup(tfhe):
+    """v3_rw 0 chooses by the batch: one wave per workgroup below R0 = 6 compute units' worth of rows, four from R0 up; R0 + 1 is a full set
+    of groups plus one wave and three padding waves.  The case's five rows tiled, against the tiled schoolbook words."""
+    from leveled_ref import ks_ref, ks_schoolbook
+    l, beta, n = 2, 10, 5
+    c = _case(tfhe, l, beta, n)
+    eng, acc, x, ref = c["eng"], c["acc"], c["x"], c["ref"]
+    R0 = 6 * _cu_count()
+    want5 = c["want"].astype(np.int32)
+    assert set(ACC_INDEX.tolist()) == {0, 1, 2}
+    eng.set_option("v3_rw", 0)
+    for R in (R0 - 1, R0, R0 + 1):
+        tile = np.arange(R) % B_ROWS
+        got = eng.bootstrap_acc(acc, x[tile], acc_index=ACC_INDEX[tile], out_form=0)
+        assert eng.last_kernel_name() == _name(l, R >= R0), (R, R0, eng.last_kernel_name())
+        assert eng.last_rotation_count() == R and got.shape == (R, K + 1, N)
+        bad = np.nonzero((got != want5[tile]).reshape(R, -1).any(axis=1))[0]
+        assert bad.size == 0, (R, R0, f"{bad.size} rows differ, the first is row {bad[:1]}")
+    ext4 = _extractions(ref, want5, 4)
+    got1 = eng.bootstrap_acc(acc, x[tile], acc_index=ACC_INDEX[tile], n_out=4, out_form=1)
+    assert eng.last_kernel_name() == _name(l, True) and np.array_equal(got1, ext4[tile]), "R0 + 1, out_form 1, n_out 4"
+    ks1 = ks_ref(ks_schoolbook(c["ck"].params, c["ck"].keyswitch_key), _extractions(ref, want5, 1))
+    got2 = eng.bootstrap_acc(acc, x[tile], acc_index=ACC_INDEX[tile], n_out=1, out_form=2)
+    assert eng.last_kernel_name() == _name(l, True) and np.array_equal(got2, ks1[tile]), "R0 + 1, out_form 2, n_out 1"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 4, 8])
+def test_gpu_step_counts_one_four_eight(tfhe, n):
+    """n = 1: the key prefetch of a one-step loop; 4 and 8: the loop ends exactly at the end of a lockstep period."""
+    l, beta = 2, 10
+    c = _case(tfhe, l, beta, n)
+    eng, acc, x, ref = c["eng"], c["acc"], c["x"], c["ref"]
+    want = c["want"].astype(np.int32)
+    ext4 = _extractions(ref, want, 4)
+    try:
+        for rw in (1, 4):
+            eng.set_option("v3_rw", rw)
+            got0 = eng.bootstrap_acc(acc, x, acc_index=ACC_INDEX, out_form=0)
+            assert eng.last_kernel_name() == _name(l, rw == 4), eng.last_kernel_name()
+            assert np.array_equal(got0, want), ("out_form 0", n, rw)
+            got1 = eng.bootstrap_acc(acc, x, acc_index=ACC_INDEX, n_out=4, out_form=1)
+            assert np.array_equal(got1, ext4), ("out_form 1", n, rw)
+    finally:
+        eng.set_option("v3_rw", 0)
+
+
+@pytest.mark.gpu
+def test_gpu_extractions_of_the_batch_call(tfhe):
+    """n_out 2, 8, 16, 32 (out_form 1) and 2, 8 (out_form 2) against extract_at and ks_ref."""
+    from leveled_ref import ks_ref, ks_schoolbook
+    l, beta, n = 3, 8, 5
+    c = _case(tfhe, l, beta, n)
+    eng, acc, x, ref = c["eng"], c["acc"], c["x"], c["ref"]
+    sbk = ks_schoolbook(c["ck"].params, c["ck"].keyswitch_key)
+    try:
+        for rw in (1, 4):
+            eng.set_option("v3_rw", rw)
+            for n_out in (2, 8, 16, 32):
+                ext = _extractions(ref, c["want"], n_out)
+                got1 = eng.bootstrap_acc(acc, x, acc_index=ACC_INDEX, n_out=n_out, out_form=1)
+                assert got1.shape == (B_ROWS, n_out, N + 1) and np.array_equal(got1, ext), ("out_form 1", n_out, rw)
+                if n_out <= 8:
+                    got2 = eng.bootstrap_acc(acc, x, acc_index=ACC_INDEX, n_out=n_out, out_form=2)
+                    assert got2.shape == (B_ROWS, n_out, n + 1) and np.array_equal(got2, ks_ref(sbk, ext)), ("out_form 2", n_out, rw)
+    finally:
+        eng.set_option("v3_rw", 0)
+
+
+@pytest.mark.gpu
+def test_gpu_extractions_of_the_level_call(tfhe):
+    """n_out 2, 8, 32 with out_form 2 into permuted wires: the wire table after the call, every wire."""
+    from leveled_ref import ks_ref, ks_schoolbook
+    l, beta, n = 3, 8, 5
+    c = _case(tfhe, l, beta, n)
+    eng, rng, ref = c["eng"], c["rng"], c["ref"]
+    W = IN_WIRES + 3 * 32 + 5
+    full, allw = _tables(c, n, W)
+    sbk = ks_schoolbook(c["ck"].params, c["ck"].keyswitch_key)
+    acc_slot, start, wire, coef = np.array([2, 0, 2], np.int32), [0, 1, 1, 3], [1, 2, 3], [1, -3, 2**31 - 1]
+    cst = _words(rng, 3)
+    want = _level_want(c, full, allw, acc_slot, start, wire, coef, cst)
+    try:
+        for n_out in (2, 8, 32):
+            out_wires = (IN_WIRES + rng.permutation(W - IN_WIRES)[:3 * n_out]).astype(np.int32)
+            assert (np.diff(out_wires) < 0).any()
+            eng.bootstrap_acc_level(acc_slot, start, wire, coef, cst=cst, n_out=n_out, out_form=2, out_wires=out_wires)
+            want_w = allw.copy()
+            want_w[out_wires] = ks_ref(sbk, _extractions(ref, want, n_out)).reshape(3 * n_out, n + 1)
+            assert np.array_equal(eng.wires_download(0, W), want_w), n_out
+            assert np.array_equal(eng.tlwe_download(0, SLOTS), full)
+            eng.wires_upload(0, allw)
+    finally:
+        eng.tlwe_alloc(0)
+        eng.wires_alloc(0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [5, 9])
+def test_gpu_level_with_padding_waves_and_permuted_out_slot(tfhe, B):
+    """v3_rw 4 with B = 5 and 9: two and three workgroups, three padding waves each time, which recompute row B - 1 and store nothing;
+    out_form 0 into a permuted out_slot; the slots nobody writes stay as they were (the whole table is compared)."""
+    l, beta, n = 4, 6, 5
+    c = _case(tfhe, l, beta, n)
+    eng, rng = c["eng"], c["rng"]
+    full, allw = _tables(c, n)
+    out_slot = np.random.default_rng(B).permutation(np.arange(3, 3 + B + 2))[:B].astype(np.int32)      # slots 0 ... 2: the accumulators; two of the range stay
+    assert (np.diff(out_slot) < 0).any()
+    acc_slot = np.array([2, 0, 1, 2, 0, 0, 1, 2, 1][:B], np.int32)
+    start = np.arange(B + 1, dtype=np.int32)
+    wire = np.array([1, 2, 3, 4, 5, 6, 7, 8, 9][:B], np.int32)                      # one term per row: the case's rows, then arbitrary ones
+    coef = np.array([1, 1, 1, 1, 1, -3, 2**31 - 1, -2**31, 7][:B], np.int32)
+    cst = _words(rng, B)
+    want = full.copy()
+    want[out_slot] = _level_want(c, full, allw, acc_slot, start, wire, coef, cst)
+    try:
+        eng.set_option("v3_rw", 4)
+        eng.bootstrap_acc_level(acc_slot, start, wire, coef, cst=cst, out_form=0, out_slot=out_slot)
+        assert eng.last_kernel_name() == _name(l, True) and eng.last_rotation_count() == B
+        got = eng.tlwe_download(0, SLOTS)
+        bad = np.nonzero((got != want).reshape(SLOTS, -1).any(axis=1))[0]
+        assert bad.size == 0, (f"slots {bad.tolist()} differ", out_slot.tolist())
+        assert np.array_equal(eng.wires_download(0, WIRES), allw)
+    finally:
+        eng.set_option("v3_rw", 0)
+        eng.tlwe_alloc(0)
+        eng.wires_alloc(0)
+
+
+@pytest.mark.gpu
+def test_gpu_level_without_a_wire_table_runs(tfhe):
+    """A context with the bootstrapping key and a TLWE table, no wire table and no keyswitch key: a call without terms and with out_form 0
+    reads and writes no wire and succeeds; its rows are (0, ..., 0, cst[g]), all zero with cst NULL."""
+    l, beta, n = 2, 10, 5
+    c = _case(tfhe, l, beta, n)
+    ck, rng = c["ck"], c["rng"]
+    raw = tfhe.Engine(ck.params)
+    try:
+        raw.load_bootstrap_key(ck.bootstrap_key)
+        full, _ = _tables(c, n, 0, eng=raw)
+        acc_slot, out_slot, start = np.array([1, 0, 1, 2], np.int32), np.array([9, 4, 12, 5], np.int32), np.zeros(5, np.int32)
+        cst_set = _words(rng, 4)
+        cst_set[0] = _word(N + 3, -7)
+        for cst in (cst_set, None):
+            raw.bootstrap_acc_level(acc_slot, start, [], [], cst=cst, out_form=0, out_slot=out_slot)
+            assert raw.last_kernel_name() == _name(l, False) and raw.last_rotation_count() == 4
+            rows = np.zeros((4, n + 1), np.int32)
+            if cst is not None:
+                rows[:, n] = cst
+            want = full.copy()
+            want[out_slot] = np.stack([c["ref"].rotate_lwe(full[a], rows[g]) for g, a in enumerate(acc_slot)]).astype(np.int32)
+            assert (cst is None) == np.array_equal(want[out_slot], full[acc_slot])                 # (all exponents 0: a copy)
+            assert np.array_equal(raw.tlwe_download(0, SLOTS), want), ("cst NULL" if cst is None else "cst set")
+            raw.tlwe_upload(0, full)
+    finally:
+        raw.close()
+
+
+@pytest.mark.gpu
+def test_gpu_workspaces_grow_behind_a_queued_gate_level(tfhe, orc):
+    """A fresh context: an asynchronous gates_level of 8 gates sizes bara, ext and map for 8 rotations; the bootstrap_acc_level right behind
+    it needs 20 rows and 40 extractions, so all three are replaced while the gate level may still be running.  The gates' wires are
+    wire_table_model's arithmetic, the rotation's the schoolbook's; its rows read the gates' outputs."""
+    import wire_table_model as M
+    from leveled_ref import ks_ref, ks_schoolbook
+    l, beta, n = 2, 10, 9
+    c = _case(tfhe, l, beta, n)
+    ck, rng, ref = c["ck"], c["rng"], c["ref"]
+    p = ck.params
+    oracle = orc.Oracle(p.lwe_size, N, K, l, beta, p.ks_decomp_length, p.ks_log2_base)
+    oracle.load_bootstrap_key(ck.bootstrap_key)
+    oracle.load_keyswitch_key(ck.keyswitch_key)
+    arith = M.single_key_arith(oracle, None)
+    B, n_out, W = 20, 2, 72
+    raw = tfhe.Engine(p)
+    try:
+        raw.load_bootstrap_key(ck.bootstrap_key)
+        raw.load_keyswitch_key(ck.keyswitch_key)
+        full, allw = _tables(c, n, W, eng=raw)
+        ops = np.array([M.OPS[nm] for nm in ("NAND", "XOR", "MUX", "OR", "ANDNY", "NOT", "XNOR", "AND")], np.uint8)      # 8 rotations (a MUX is two)
+        a, b, z = np.arange(1, 9, dtype=np.int32), np.arange(2, 10, dtype=np.int32), np.arange(3, 11, dtype=np.int32)
+        gate_out = np.arange(12, 20, dtype=np.int32)
+        assert M.rotations(ops) == 8
+        acc_slot = (np.arange(B) % 3).astype(np.int32)
+        start = np.arange(B + 1, dtype=np.int32)
+        wire = np.concatenate([gate_out, gate_out, np.arange(1, 5)]).astype(np.int32)                # every row reads a wire, 16 of them a gate's output
+        coef = np.where(np.arange(B) % 3 == 0, 1, _words(rng, B)).astype(np.int32)
+        cst = _words(rng, B)
+        out_wires = (20 + rng.permutation(W - 20)[:B * n_out]).astype(np.int32)
+        raw.gates_level(ops, a, b, z, gate_out)
+        raw.bootstrap_acc_level(acc_slot, start, wire, coef, cst=cst, n_out=n_out, out_form=2, out_wires=out_wires)
+        assert raw.last_kernel_name() == _name(l, False) and raw.last_rotation_count() == B
+        got = raw.wires_download(0, W)
+        want = allw.copy()
+        want[gate_out] = arith.gates(ops, allw[a], allw[b], allw[z])
+        assert np.array_equal(got[gate_out], want[gate_out]), "the gate level's outputs"
+        accs = _level_want(c, full, want, acc_slot, start, wire, coef, cst)
+        want[out_wires] = ks_ref(ks_schoolbook(p, ck.keyswitch_key), _extractions(ref, accs, n_out)).reshape(B * n_out, n + 1)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, f"wires {bad.tolist()} differ"
+        assert np.array_equal(raw.tlwe_download(0, SLOTS), full)
+    finally:
+        raw.close()
 
 
 # ---- 4. GPU: refusals ---------------------------------------------------------------------------------------------------------------

@@ -35,20 +35,25 @@ CASES = [pytest.param(name, i, id=f"{name}-seed{seed}") for name in SETS for i, 
 GATES2 = ("NAND", "OR", "AND", "XOR", "XNOR", "NOR", "ANDNY", "ANDYN", "ORNY", "ORYN")
 
 
-def build_set(tfhe, orc, name, programs=None):
-    """Keys, reference arithmetic, the programs and the model's result of each (one Model: its memo and event counters span them)."""
+AB_STEPS_SHA1 = "4a3638943731efac19672a05bb27bc83f35a80ce"        # tlwe_table_model.steps_digest of the eight programs, taken before the generator learnt acc=True
+
+
+def build_set(tfhe, orc, name, programs=None, shape=None, acc=False):
+    """Keys, reference arithmetic, the programs and the model's result of each (one Model: its memo and event counters span them).
+    shape: (n, N, k, l, beta) of a set that is not in SETS; acc: programs with acc_rotate / acc_batch steps (tests/test_bootstrap_acc_programs.py)."""
     import leveled_ref
     from test_any_params import _setup
     from test_independent import Schoolbook
-    n, N, k, l, beta = SETS[name]
-    S = SimpleNamespace(name=name, p=SimpleNamespace(n=n, N=N, k=k, l=l, beta=beta))
+    from tfhe_jl_amd import leveled
+    n, N, k, l, beta = shape or SETS[name]
+    S = SimpleNamespace(name=name, p=SimpleNamespace(n=n, N=N, k=k, l=l, beta=beta), acc=acc)
     S.K = _setup(tfhe, orc, n, N, k, l, beta)
     S.arbitrary = S.K.params.exactness()[0] == 2
     sb = Schoolbook(n, N, k, l, beta, 8, 2, S.K.ck.bootstrap_key, S.K.ck.keyswitch_key)
     S.arith = M.single_key_arith(S.K.oracle, sb)
-    S.model = T.Model(S.p, S.arith, leveled_ref.ks_schoolbook(S.K.params, S.K.ck.keyswitch_key))
+    S.model = T.Model(S.p, S.arith, leveled_ref.ks_schoolbook(S.K.params, S.K.ck.keyswitch_key), leveled.bootstrap_key_selectors(S.K.ck) if acc else None)
     S.seeds = PROGRAMS[name] if programs is None else programs
-    S.progs = [T.make_program(seed, steps, S.p, S.K.sk, S.arbitrary) for seed, steps in S.seeds]
+    S.progs = [T.make_program(seed, steps, S.p, S.K.sk, S.arbitrary, acc) for seed, steps in S.seeds]
     S.results = [S.model.run(p) for p in S.progs]
     return S
 
@@ -65,6 +70,13 @@ def sets(tfhe, orc):
 
 
 # ---- CPU: the programs ---------------------------------------------------------------------------------------------------------------------
+def test_committed_programs_are_the_steps_they_were(sets):
+    """The generator's acc=True steps changed no draw of acc=False: the eight programs, every kind and every array's bytes, in order."""
+    assert T.steps_digest([p for name in SETS for p in sets[name].progs]) == AB_STEPS_SHA1
+    assert not any(s.kind in ("acc_rotate", "acc_batch") or "v3_rw" in s or (s.kind == "refused" and s.why in T.ACC_REFUSALS)
+                   for name in SETS for p in sets[name].progs for s in p)
+
+
 def test_committed_programs_have_the_promised_steps(sets):
     for name, S in sets.items():
         n, N = S.p.n, S.p.N
@@ -206,6 +218,9 @@ def _level_call(eng, lv):
     if lv.kind == "rotate":
         return eng.blind_rotate_level(lv.acc_slot, lv.start, lv.wire, lv.coef, cst=lv.cst, sel=lv.sel, n_out=lv.n_out, out_form=lv.out_form,
                                       out_slot=lv.out_slot, out_wires=lv.out_wires)
+    if lv.kind == "acc_rotate":
+        return eng.bootstrap_acc_level(lv.acc_slot, lv.start, lv.wire, lv.coef, cst=lv.cst, n_out=lv.n_out, out_form=lv.out_form, out_slot=lv.out_slot,
+                                       out_wires=lv.out_wires)
     if lv.kind == "net":
         return eng.rot_net_level(lv.net, lv.sel, table_first=lv.table_first, out_form=lv.out_form, out_first=lv.out_first, out_wires=lv.out_wires)
     return _call(eng, lv, lv.kind)
@@ -224,9 +239,10 @@ def _replay(tfhe, eng, S, which, checked):
     """Runs the program on the engine; every read against the model; checked: both whole tables after every step as well."""
     p = S.p
     tag = f"set {S.name}, seed {S.seeds[which][0]}, {'checked' if checked else 'free-running'},"
-    slots = W = 0
+    slots = W = rw = 0
     spec = -1
     eng.set_option("anyn_spec", -1)
+    eng.set_option("v3_rw", 0)
     try:
         for i, (s, (want, tlwe, wires)) in enumerate(zip(S.progs[which], S.results[which])):
             what = f"{tag} step {i} ({s.kind})"
@@ -244,13 +260,22 @@ def _replay(tfhe, eng, S, which, checked):
                 eng.tgsw_load(s.data)
             elif s.kind == "tgsw_update":
                 eng.tgsw_update(s.first, s.data)
+            elif s.kind == "option" and "v3_rw" in s:
+                eng.set_option("v3_rw", s.v3_rw)
+                rw = s.v3_rw
             elif s.kind == "option":
                 eng.set_option("anyn_spec", s.anyn_spec)
                 spec = s.anyn_spec
+            elif s.kind == "acc_batch":
+                got = eng.bootstrap_acc(s.acc, s.rows, acc_index=s.acc_index, n_out=s.n_out, out_form=s.out_form)
+                assert eng.last_kernel_name() == _acc_name(p.l, rw == 4), (what, eng.last_kernel_name())
+                _assert_rows(got, want, 0, "row", what)
             elif s.kind in T.LEVELS:
                 _level_call(eng, s)
                 if s.kind == "rotate":
                     assert eng.last_kernel_name() == f"tlwe_rotate_level_kernel(N={p.N},k={p.k},l={p.l},steps={p.n}{',spec=global' if spec == 1 else ''})", what
+                elif s.kind == "acc_rotate":
+                    assert eng.last_kernel_name() == _acc_name(p.l, rw == 4), (what, eng.last_kernel_name())
                 elif s.kind == "net":
                     assert eng.last_kernel_name().startswith("rot_net_level_kernel("), (what, eng.last_kernel_name())
             elif s.kind == "refused":
@@ -271,6 +296,12 @@ def _replay(tfhe, eng, S, which, checked):
                     _assert_rows(eng.wires_download(0, W), wires, 0, "wire", what + ", the wire table after it")
     finally:
         eng.set_option("anyn_spec", -1)
+        eng.set_option("v3_rw", 0)
+
+
+def _acc_name(l, rw4):
+    from test_bootstrap_acc import _name
+    return _name(l, rw4)
 
 
 def _engine(S):

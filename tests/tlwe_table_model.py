@@ -20,6 +20,18 @@ A program is a seeded list of steps over a TLWE table of 12 ... 24 slots and a w
     option                              anyn_spec in {-1, 1}
     refused                             a call the library must refuse (REFUSALS), both tables as they were
 
+With acc=True (N = 1024, k = 1, where blind_rotate_kernel_v3_acc exists; acc=False draws exactly what it drew before: steps_digest) also:
+
+    acc_rotate                          tfhe_bootstrap_acc_level: `rotate` without sel, B = 1 ... 9, n_out 1, 2, 8 with B n_out at most half the
+                                        wires and the outputs apart from every read; the special rows take turns on their own
+    acc_batch                           Engine.bootstrap_acc on host buffers between the levels, a read: T = 1 ... 3 arbitrary accumulators,
+                                        B = 1 ... 6 rows of arbitrary words, acc_index or None, out_form 0, 1 or 2 (n_out 1, 4, 32)
+    option                              also v3_rw in turn 1, 4, 0, 4 (the model ignores it: no word depends on it)
+    refused                             REFUSALS and ACC_REFUSALS in turn
+
+Both rotate with a second Rotation over leveled.bootstrap_key_selectors(ck), selector i at step i, whatever set is loaded (ACC_EVENTS,
+ACC_FAULTS).
+
 `Model` holds one wire table [W][n+1], one TLWE table [slots][k+1][N] and the selector set [S][l][k+1][k+1][N] and applies each step in
 exact integer arithmetic: test_tlwe_levels.form_rows then test_blind_rotate.Rotation.rotate_lwe for a rotation row, Rotation.extract_at
 for the extractions, leveled_ref.rot_net_ref over a Tree for the networks, leveled_ref.ks_ref for the keyswitch, wire_table_model's
@@ -40,8 +52,13 @@ REFUSALS = ("out_is_acc", "slot_twice", "out_meets_read", "term_is_out", "out_fo
 UPDATES = ("first_0", "last", "straddles_n", "whole")
 SPECIALS = (None, "copy", "mask_zero", "skip_last")
 TLWE_LEVELS = ("rotate", "net")
-LEVELS = TLWE_LEVELS + M.LEVELS
-READS = ("tlwe_download", "wires_download", "wires_gather")
+ACC_LEVELS = ("acc_rotate",)
+LEVELS = TLWE_LEVELS + M.LEVELS + ACC_LEVELS
+READS = ("tlwe_download", "wires_download", "wires_gather", "acc_batch")
+# with acc=True (the programs of tests/test_bootstrap_acc_programs.py at N = 1024, k = 1; never in a program made with acc=False):
+ACC_B = (1, 4, 5, 8, 9)                                                            # half of the acc_rotate steps draw B here, the others 1 ... 9
+ACC_N_OUTS, BATCH_N_OUTS, V3_RWS = (1, 2, 8), (1, 4, 32), (4, 1, 4, 0)
+ACC_REFUSALS = ("acc_out_is_acc", "acc_slot_twice", "acc_term_is_out", "acc_out_form_1")
 
 EVENTS = ("slot_rewritten_then_read", "upload_over_level_written_slot", "net_reads_slot_written_by_rotate", "rotate_reads_slot_written_by_net",
           "rotate_term_wire_written_by_net", "rotate_term_is_gate_output", "gate_reads_wire_written_by_tlwe_level",
@@ -50,6 +67,13 @@ EVENTS = ("slot_rewritten_then_read", "upload_over_level_written_slot", "net_rea
           "outputs_below_read_ranges", "level_under_spec_global", "read_after_refused")
 FAULTS = ("stale_selectors", "update_offset", "first_ignored", "net_out_stride", "out_slot_order", "dst_order", "sel_ignored", "cst_dropped",
           "other_sample", "extract_stride", "realloc_clobbers", "refused_writes_first", "stale_slot")
+ACC_EVENTS = ("acc_rotate_reads_slot_written_by_rotate", "acc_rotate_reads_slot_written_by_net", "rotate_or_net_reads_slot_written_by_acc_rotate",
+              "acc_rotate_term_is_gate_output", "gate_reads_wire_written_by_acc_rotate", "acc_rotate_directly_after_wire_level",
+              "wire_level_directly_after_acc_rotate", "acc_batch_between_two_levels", "acc_rotate_after_selector_change",
+              "acc_rotate_rw4_with_padding", "acc_rotate_rw4_out_form_0", "acc_rotate_shared_acc_slot", "acc_rotate_copy_row",
+              "acc_rotate_last_step_skipped", "acc_rotate_larger_than_every_level_before")
+ACC_FAULTS = ("acc_uses_loaded_selectors", "acc_out_index_ignored", "acc_first_rows_slot", "acc_mask_from_zero", "acc_barb_dropped",
+              "acc_extract_stride", "acc_batch_stale_rows", "acc_clobbers_wire_level")
 
 
 def _words(rng, *shape):
@@ -88,8 +112,8 @@ class Generator:
     wire_table_model.Generator (self.g), which shares the generator's rng and table size.  What was written by a level lately is
     preferred as an operand (hot_slots, hot_wires), so that levels read what levels wrote."""
 
-    def __init__(self, rng, p, sk, arbitrary):
-        self.rng, self.p, self.sk, self.arbitrary = rng, p, sk, arbitrary
+    def __init__(self, rng, p, sk, arbitrary, acc=False):
+        self.rng, self.p, self.sk, self.arbitrary, self.acc = rng, p, sk, arbitrary, acc
         self.g = M.Generator(rng, p.n + 1)
         self.nets = make_nets(p.N)
         self.slots = self.S = self.S_seen = 0
@@ -97,6 +121,10 @@ class Generator:
         self.refusal_at, self.update_at, self.special_at = (int(rng.integers(0, m)) for m in (len(REFUSALS), len(UPDATES), len(SPECIALS)))
         self.hot_slots, self.hot_wires = [], []
         self.tables = _words(rng, M.N_TV, p.N)
+        self.refusals = REFUSALS
+        if acc:                                                                   # (nothing is drawn for it otherwise: acc=False draws what it drew)
+            self.refusals = tuple(w for pair in zip(ACC_REFUSALS + ACC_REFUSALS[:2], REFUSALS[::-1]) for w in pair)      # in turn: one of each
+            self.acc_special_at, self.rw_at = int(rng.integers(0, len(SPECIALS))), int(rng.integers(0, len(V3_RWS)))
 
     W = property(lambda self: self.g.W)
 
@@ -162,11 +190,24 @@ class Generator:
 
     def rotate(self, form=None, min_B=1, special="turn"):
         """[steps]: the rotation, behind an upload of the planted wire when the row `skip_last` is due."""
-        rng, n, N = self.rng, self.p.n, self.p.N
         if special == "turn":
             special = SPECIALS[self.special_at % len(SPECIALS)]
             self.special_at += 1
-        B = int(rng.integers(min_B, 5))
+        B = int(self.rng.integers(min_B, 5))
+        return self._rotation("rotate", B, form, N_OUTS, special)
+
+    def acc_rotate(self, form=None, min_B=1, special="turn"):
+        """[steps]: `rotate` without sel, B up to 9, n_out 1, 2 or 8 with B n_out at most half the wires."""
+        rng = self.rng
+        if special == "turn":
+            special = SPECIALS[self.acc_special_at % len(SPECIALS)]
+            self.acc_special_at += 1
+        B = max(int(rng.choice(ACC_B)) if rng.random() < 0.5 else int(rng.integers(1, 10)), min_B)
+        return self._rotation("acc_rotate", B, form, [v for v in ACC_N_OUTS if B * v <= self.W // 2], special)
+
+    def _rotation(self, kind, B, form, n_outs, special):
+        """A rotation level of B rows; only `rotate` has a sel."""
+        rng, n, N = self.rng, self.p.n, self.p.N
         form = int(rng.choice((0, 2))) if form is None else form
         every_slot, every_wire = np.arange(self.slots, dtype=np.int32), np.arange(self.W, dtype=np.int32)
         n_out, out_slot, out_wires = 1, None, None
@@ -175,7 +216,7 @@ class Generator:
             acc = self._prefer(np.setdiff1d(every_slot, out_slot), self.hot_slots, B)
             pool = every_wire
         else:
-            n_out = int(rng.choice(N_OUTS))
+            n_out = int(rng.choice(n_outs))
             out_wires = rng.choice(self.W, B * n_out, replace=False).astype(np.int32)
             acc = self._prefer(every_slot, self.hot_slots, B)
             pool = np.setdiff1d(every_wire, out_wires)
@@ -206,10 +247,25 @@ class Generator:
             w = int(rng.choice(pool))
             wire[start[row]], coef[start[row]] = w, 1
             before = [Step(kind="wires_upload", first=w, data=planted)]
-        sel = None if rng.random() < 0.4 else rng.permutation(self.S)[:n].astype(np.int32)
-        s = Step(kind="rotate", B=B, special=special, acc_slot=acc, start=start, wire=wire, coef=coef, cst=cst, sel=sel, n_out=n_out, out_form=form,
+        sel = None if kind != "rotate" or rng.random() < 0.4 else rng.permutation(self.S)[:n].astype(np.int32)
+        s = Step(kind=kind, B=B, special=special, acc_slot=acc, start=start, wire=wire, coef=coef, cst=cst, sel=sel, n_out=n_out, out_form=form,
                  out_slot=out_slot, out_wires=out_wires)
         return before + [s]
+
+    def acc_batch(self):
+        """Engine.bootstrap_acc on host buffers: arbitrary accumulators and LWE words; a read."""
+        rng, p = self.rng, self.p
+        T, B, form = int(rng.integers(1, 4)), int(rng.integers(1, 7)), int(rng.integers(0, 3))
+        index = None if rng.random() < 0.3 else rng.integers(0, T, B).astype(np.int32)
+        return Step(kind="acc_batch", B=B, acc=_words(rng, T, p.k + 1, p.N), rows=_words(rng, B, p.n + 1), acc_index=index, out_form=form,
+                    n_out=int(rng.choice(BATCH_N_OUTS)) if form else 1)
+
+    def option(self):
+        if self.acc and self.rng.random() < 0.7:
+            self.rw_at += 1
+            return Step(kind="option", v3_rw=V3_RWS[self.rw_at % len(V3_RWS)])
+        self.spec = -self.spec
+        return Step(kind="option", anyn_spec=self.spec)
 
     def net(self, form=None, name=None):
         rng, slots = self.rng, self.slots
@@ -249,12 +305,26 @@ class Generator:
     def refused(self):
         """[steps]: the refused call (otherwise a valid one), behind a smaller tgsw_load where `sel_beyond` needs one."""
         rng = self.rng
-        why = REFUSALS[self.refusal_at % len(REFUSALS)]
+        why = self.refusals[self.refusal_at % len(self.refusals)]
         self.refusal_at += 1
         before = []
         if why == "out_is_acc":
             lv = self.rotate(0, special=None)[0]
             lv.out_slot[-1] = lv.acc_slot[0]
+        elif why == "acc_out_is_acc":
+            lv = self.acc_rotate(0, special=None)[0]
+            lv.out_slot[-1] = lv.acc_slot[0]
+        elif why == "acc_slot_twice":
+            lv = self.acc_rotate(0, min_B=2, special=None)[0]
+            lv.out_slot[-1] = lv.out_slot[0]
+        elif why == "acc_term_is_out":
+            lv = self.acc_rotate(2, special=None)[0]
+            while len(lv.wire) == 0:
+                lv = self.acc_rotate(2, special=None)[0]
+            lv.wire[-1] = lv.out_wires[0]
+        elif why == "acc_out_form_1":
+            lv = self.acc_rotate(special=None)[0]
+            lv["out_form"] = 1
         elif why == "slot_twice":
             lv = self.rotate(0, min_B=2, special=None)[0]
             lv.out_slot[-1] = lv.out_slot[0]
@@ -284,7 +354,7 @@ class Generator:
 
     def note(self, s):
         """What the step wrote, for the preferences of later steps."""
-        if s.kind == "rotate":
+        if s.kind in ("rotate", "acc_rotate"):
             if s.out_form == 0:
                 self.hot_slots += s.out_slot.tolist()
             else:
@@ -302,7 +372,7 @@ def level_code(lv, slots, W, N, S):
     """The code of a TLWE level call on tables of `slots` slots and W wires with S selectors loaded: model_blind_rotate_level /
     model_rot_net_level of tests/test_tlwe_levels.py; those take the state and the keys as in order, so a selector index beyond the
     loaded count is refused here, behind them, as the library does."""
-    if lv.kind == "rotate":
+    if lv.kind in ("rotate", "acc_rotate"):
         code, sel = model_blind_rotate_level(slots, W, N, lv.acc_slot, lv.start, lv.wire, lv.n_out, lv.out_form, lv.out_slot, lv.out_wires), lv.sel
     else:
         code, sel = model_rot_net_level(slots, W, lv.E, lv.F, lv.B, lv.table_first, lv.out_form, lv.out_first, lv.out_wires), lv.sel
@@ -311,17 +381,53 @@ def level_code(lv, slots, W, N, S):
     return code
 
 
-def make_program(seed, steps, p, sk, arbitrary):
-    """`steps` steps; the last two download both whole tables."""
+def level_size(s):
+    """The rows a level's (or an acc_batch's) workspaces are sized for: rotations of a gate level, B F of a network, B n_out otherwise."""
+    if s.kind == "gates":
+        return M.rotations(s.ops)
+    return s.B * (s.F if s.kind == "net" else s.get("n_out", 1))
+
+
+def steps_digest(progs):
+    """SHA-1 over the steps of the programs in order: each step's kind, then every field in order (an array's dtype, shape and bytes, a
+    nested level likewise, numbers, strings and None by value)."""
+    h = hashlib.sha1()
+
+    def feed(s):
+        h.update(b"<" + str(s["kind"]).encode())
+        for key, v in s.items():
+            if isinstance(v, np.ndarray):
+                h.update(f"|{key}:{v.dtype.str}{v.shape}".encode())
+                h.update(np.ascontiguousarray(v).tobytes())
+            elif isinstance(v, dict):
+                h.update(f"|{key}:".encode())
+                feed(v)
+            elif v is None or isinstance(v, (bool, int, str, np.integer)):
+                h.update(f"|{key}={v}".encode())
+        h.update(b">")
+
+    for prog in progs:
+        h.update(b"[")
+        for s in prog:
+            feed(s)
+        h.update(b"]")
+    return h.hexdigest()
+
+
+def make_program(seed, steps, p, sk, arbitrary, acc=False):
+    """`steps` steps; the last two download both whole tables.  acc: acc_rotate and acc_batch steps, v3_rw options and the acc_ refusals
+    as well (without it the draws are those of the programs committed before these existed: steps_digest)."""
     rng = np.random.default_rng(seed)
-    g = Generator(rng, p, sk, arbitrary)
+    g = Generator(rng, p, sk, arbitrary, acc)
     prog = g.wires_alloc() + g.tlwe_alloc() + [g.tgsw_load(int(rng.integers(p.n + 3, p.n + 5)), plant=True)]
     kinds = ["rotate", "net", "gates", "linear", "lut", "tlwe_upload", "wires_upload", "tgsw_load", "tgsw_update", "tlwe_download", "wires_download",
              "wires_gather", "option", "refused", "tlwe_alloc", "wires_alloc"]
     weight = np.array([0.21, 0.19, 0.09, 0.03, 0.05, 0.06, 0.03, 0.03, 0.07, 0.05, 0.02, 0.03, 0.04, 0.07, 0.015, 0.015])
+    if acc:
+        kinds, weight = kinds + ["acc_rotate", "acc_batch"], np.array([0.10, 0.10, 0.10, 0.02, 0.04, 0.04, 0.02, 0.02, 0.05, 0.03, 0.01, 0.02, 0.09, 0.10, 0.015, 0.015, 0.26, 0.08])
     while len(prog) < steps - 2:
         kind = kinds[int(rng.choice(len(kinds), p=weight / weight.sum()))]
-        if len(prog) == steps - 3 and kind in ("rotate", "refused", "tlwe_alloc", "wires_alloc"):      # room for one step: these may take two
+        if len(prog) == steps - 3 and kind in ("rotate", "acc_rotate", "refused", "tlwe_alloc", "wires_alloc"):      # room for one step: these may take two
             continue
         if kind == "rotate":
             new = g.rotate()
@@ -350,8 +456,11 @@ def make_program(seed, steps, p, sk, arbitrary):
         elif kind == "wires_gather":
             new = [Step(kind="wires_gather", wires=rng.integers(0, g.W, int(rng.integers(1, 2 * g.W))).astype(np.int32))]
         elif kind == "option":
-            g.spec = -g.spec
-            new = [Step(kind="option", anyn_spec=g.spec)]
+            new = [g.option()]
+        elif kind == "acc_rotate":
+            new = g.acc_rotate()
+        elif kind == "acc_batch":
+            new = [g.acc_batch()]
         elif kind == "refused":
             new = g.refused()
         elif kind == "tlwe_alloc":
@@ -378,11 +487,16 @@ class Model:
     Rotations, network rows and keyswitches are memoised by their operand words and the selector set's digest: a run under an emulated
     fault computes only what the fault changed."""
 
-    def __init__(self, p, arith, ks_sb):
+    def __init__(self, p, arith, ks_sb, key_selectors=None):
+        """key_selectors: leveled.bootstrap_key_selectors(ck), for programs with acc_rotate / acc_batch steps: those rotate with a second
+        Rotation over it, built once, selector i at step i whatever set is loaded."""
         self.p, self.arith, self.ks_sb = p, arith, ks_sb
         self.memo, self.refs = {}, {}
-        self.ref = self.set_id = self.tgsw = None
+        self.ref = self.set_id = self.tgsw = self.acc_ref = None
         self.events = collections.Counter()
+        if key_selectors is not None:
+            from test_blind_rotate import Rotation
+            self.acc_ref = Rotation(p.N, p.k, p.l, p.beta, np.ascontiguousarray(key_selectors, np.int32))
 
     # -- arithmetic
     def load(self, tgsw):
@@ -412,6 +526,20 @@ class Model:
             else:
                 out = self.ref.rotate_lwe(acc, x, sel)
             self.memo[key] = out.astype(np.int32)
+        return self.memo[key]
+
+    def acc_rotation(self, acc, x, fault=None):
+        """The same with the bootstrapping key's entries as the selectors, entry i at step i (memo keys tagged "acc": never `rotation`'s)."""
+        how = fault if fault in ("acc_uses_loaded_selectors", "acc_mask_from_zero", "acc_barb_dropped") else None
+        if how == "acc_uses_loaded_selectors":
+            return self.rotation(acc, x, None)
+        key = ("acc", acc.tobytes(), x.tobytes(), how)
+        if key not in self.memo:
+            w = self.acc_ref.sb.modswitch(x)
+            if how == "acc_mask_from_zero":
+                acc = acc.copy()
+                acc[:self.p.k] = 0
+            self.memo[key] = self.acc_ref.rotate(acc, w[:-1], 0 if how == "acc_barb_dropped" else w[-1]).astype(np.int32)
         return self.memo[key]
 
     def net_row(self, name, net, table, sels):
@@ -453,6 +581,40 @@ class Model:
         ext = np.stack([[self.extract(r, j * stride) for j in range(s.n_out)] for r in res])
         rows = self.keyswitch(ext).reshape(s.B * s.n_out, p.n + 1)
         return "wires", (np.sort(s.out_wires) if fault == "dst_order" else s.out_wires), rows
+
+    def acc_rotate_level(self, s, tlwe, wires, fault=None, count=False):
+        """tfhe_bootstrap_acc_level: rotate_level with sel None over the key's own selectors."""
+        p, ev = self.p, self.events
+        x = form_rows(wires, s.start, s.wire, s.coef, s.cst)
+        if count:
+            for g in range(s.B):
+                e = self.exponents(x[g])
+                ev["acc_rotate_copy_row"] += int(not any(e))
+                ev["acc_rotate_last_step_skipped"] += int(e[p.n - 1] == 0 and e[p.n - 2] != 0)
+        slots = [s.acc_slot[0]] * s.B if fault == "acc_first_rows_slot" else s.acc_slot
+        res = np.stack([self.acc_rotation(tlwe[a], x[g], fault) for g, a in enumerate(slots)])
+        if s.out_form == 0:
+            return "tlwe", (np.arange(s.B) if fault == "acc_out_index_ignored" else s.out_slot), res
+        rows = self.keyswitch(self.extractions(res, s.n_out, fault)).reshape(s.B * s.n_out, p.n + 1)
+        return "wires", s.out_wires, rows
+
+    def extractions(self, res, n_out, fault=None):
+        stride = 1 if fault == "acc_extract_stride" else self.p.N // n_out
+        return np.stack([[self.extract(r, j * stride) for j in range(n_out)] for r in res])
+
+    def acc_batch(self, s, fault=None, stale_rows=None):
+        """Engine.bootstrap_acc: the words it must return, by out_form [B][k+1][N], [B][n_out][kN+1] or [B][n_out][n+1]."""
+        x = s.rows
+        if fault == "acc_batch_stale_rows" and stale_rows is not None:
+            x = stale_rows[np.arange(s.B) % len(stale_rows)]
+        index = np.zeros(s.B, np.int32) if s.acc_index is None else s.acc_index
+        if fault == "acc_first_rows_slot":
+            index = np.full(s.B, index[0])
+        res = np.stack([self.acc_rotation(s.acc[a], x[g], fault) for g, a in enumerate(index)])
+        if s.out_form == 0:
+            return res
+        ext = self.extractions(res, s.n_out, fault)
+        return ext if s.out_form == 1 else self.keyswitch(ext)
 
     def net_level(self, s, tlwe, fault=None):
         p = self.p
@@ -512,6 +674,42 @@ class Model:
         elif s.kind == "refused" and s.why == "sel_beyond":
             ev["sel_beyond_smaller_load_refused"] += int(len(self.tgsw) <= int(np.max(s.level.sel)) < st.S_seen)
 
+    def _count_acc(self, s, st):
+        """ACC_EVENTS, likewise.  st: rw (option v3_rw), before / before2 (the kinds of the two steps in front), selectors_changed (since the
+        last acc_rotate), largest (level_size over the levels so far)."""
+        ev = self.events
+        if s.kind == "acc_rotate":
+            slots_read = [int(a) for a in s.acc_slot]
+            terms = [int(w) for w in s.wire[:s.start[-1]]]
+            ev["acc_rotate_reads_slot_written_by_rotate"] += int(any(st.slot_by[a] == "rotate" for a in slots_read))
+            ev["acc_rotate_reads_slot_written_by_net"] += int(any(st.slot_by[a] == "net" for a in slots_read))
+            ev["acc_rotate_term_is_gate_output"] += int(any(st.wire_by[w] == "gates" for w in terms))
+            ev["acc_rotate_directly_after_wire_level"] += int(st.before in M.LEVELS)
+            ev["acc_rotate_after_selector_change"] += int(st.selectors_changed is True)
+            ev["acc_rotate_rw4_with_padding"] += int(st.rw == 4 and s.B % 4 != 0)
+            ev["acc_rotate_rw4_out_form_0"] += int(st.rw == 4 and s.out_form == 0)
+            ev["acc_rotate_shared_acc_slot"] += int(len(set(slots_read)) < len(slots_read))
+            ev["acc_rotate_larger_than_every_level_before"] += int(0 < st.largest < level_size(s))
+            st.selectors_changed = False
+        elif s.kind == "rotate":
+            ev["rotate_or_net_reads_slot_written_by_acc_rotate"] += int(any(st.slot_by[int(a)] == "acc_rotate" for a in s.acc_slot))
+        elif s.kind == "net":
+            first = [0] * s.B if s.table_first is None else [int(f) for f in s.table_first]
+            ev["rotate_or_net_reads_slot_written_by_acc_rotate"] += int(any(st.slot_by[f + e] == "acc_rotate" for f in first for e in range(s.E)))
+        elif s.kind == "gates":
+            ev["gate_reads_wire_written_by_acc_rotate"] += int(any(st.wire_by[w] == "acc_rotate" for w in M.reads_of(s, 0, s.B)))
+        elif s.kind in ("tgsw_load", "tgsw_update") and st.selectors_changed is False:
+            st.selectors_changed = True
+        elif s.kind == "option" and "v3_rw" in s:
+            st.rw = s.v3_rw
+        if s.kind in M.LEVELS:
+            ev["wire_level_directly_after_acc_rotate"] += int(st.before == "acc_rotate")
+        if s.kind in LEVELS:
+            ev["acc_batch_between_two_levels"] += int(st.before == "acc_batch" and st.before2 in LEVELS)
+        if s.kind in LEVELS + ("acc_batch",):
+            st.largest = max(st.largest, level_size(s))
+        st.before2, st.before = st.before, s.kind
+
     def _wrote(self, s, st, what, dst):
         if what == "tlwe":
             for a in dst:
@@ -525,14 +723,17 @@ class Model:
     def run(self, prog, fault=None, want=None):
         """Fault-free: the list of (read, TLWE table, wire table) per step, the events counted.  With `fault` and `want` (the fault-free
         reads): the index of the first read that differs, or None."""
-        assert fault is None or (fault in FAULTS and want is not None)
-        tlwe = wires = prev_tlwe = None
-        st = Step(slot_by=None, wire_by=None, slot_writes=None, used=set(), renewed=set(), S_seen=0, spec=-1)
+        assert fault is None or (fault in FAULTS + ACC_FAULTS and want is not None)
+        tlwe = wires = prev_tlwe = stale_rows = wire_level = None
+        st = Step(slot_by=None, wire_by=None, slot_writes=None, used=set(), renewed=set(), S_seen=0, spec=-1,
+                  rw=0, before=None, before2=None, selectors_changed=None, largest=0)
         res, refused = [], False
         for i, s in enumerate(prog):
             read, before = None, tlwe
+            in_front, wire_level = wire_level, None                               # (what a gates, linear or lut step directly in front wrote over)
             if fault is None:
                 self._count(s, st)
+                self._count_acc(s, st)
             if s.kind == "tlwe_alloc":
                 self.events["tlwe_realloc_with_live_wires"] += int(fault is None and tlwe is not None and wires is not None)
                 tlwe = np.zeros((s.slots, self.p.k + 1, self.p.N), np.int32)
@@ -564,17 +765,29 @@ class Model:
                     t[first:first + len(s.data)] = s.data
                     self.load(t)
             elif s.kind == "option":
-                st.spec = s.anyn_spec
-            elif s.kind in LEVELS or (s.kind == "refused" and fault == "refused_writes_first" and s.why in REFUSALS[:4]):
+                if "anyn_spec" in s:                                              # (v3_rw changes no word: the model ignores it)
+                    st.spec = s.anyn_spec
+            elif s.kind == "acc_batch":
+                read = self.acc_batch(s, fault, stale_rows)
+                stale_rows = s.rows
+                if fault is not None and not np.array_equal(read, want[i]):
+                    return i
+            elif s.kind in LEVELS or (s.kind == "refused" and fault == "refused_writes_first" and s.why in REFUSALS[:4] + ACC_REFUSALS[:3]):
                 lv = s.level if s.kind == "refused" else s
                 stale = fault == "stale_slot" and prev_tlwe is not None and prev_tlwe.shape == tlwe.shape
                 if lv.kind == "rotate":
                     what, dst, rows = self.rotate_level(lv, prev_tlwe if stale else tlwe, wires, fault, count=fault is None)
+                elif lv.kind == "acc_rotate":
+                    if fault == "acc_clobbers_wire_level" and s is lv and in_front is not None:      # that level's rows as they were before it
+                        wires = wires.copy()
+                        wires[in_front[0]] = in_front[1]
+                    what, dst, rows = self.acc_rotate_level(lv, tlwe, wires, fault, count=fault is None)
                 elif lv.kind == "net":
                     what, dst, rows = self.net_level(lv, prev_tlwe if stale else tlwe, fault)
                 else:
                     what = "wires"
                     dst, rows = M.run_level(self.arith, wires, lv, 0, lv.B)
+                    wire_level = (dst, wires[dst].copy()) if s is lv else None
                 if what == "tlwe":
                     tlwe = tlwe.copy()
                     tlwe[dst] = rows
