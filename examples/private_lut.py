@@ -14,11 +14,13 @@ rotations per address, and the answer comes as three bits.  (Masking the eight l
 lookup in Z_16 needs 17 rotations, but its +-1/64 window does not hold a bootstrap's output noise at this parameter set: it was tried
 and fails to decrypt.)
 
-    python examples/private_lut.py [--tuned]
+    python examples/private_lut.py [--tuned [--by-size]]
 
 --tuned: the two-stage lookup is also run with its rotation on the gates' own kernel and key (two_stage_lookup(..., tuned=True);
 tfhe_bootstrap_acc_batch: the accumulator stays in LDS, the bootstrapping key is not loaded a second time as selectors), the same program
 both ways: equal words, both times.
+--by-size (with --tuned): the engine's option acc_dispatch is set to 1 for that run, so the rotation of these 32 rows takes the kernel a
+gate batch of 32 rotations takes (every transform split over two waves) instead of one wave per row.
 """
 import argparse
 import os
@@ -71,7 +73,7 @@ def timed(call):
     return out, (time.perf_counter() - t0) * 1e3
 
 
-def main(tuned=False):
+def main(tuned=False, by_size=False):
     rng = np.random.default_rng(2026)
     params = tfhe.tfhe_parameters_80()
     sk, ck = tfhe.make_key_pair(rng, params)
@@ -102,7 +104,13 @@ def main(tuned=False):
             low = digit_circuit(P).run_batch(ck, digits)[:, 0]
             return tfhe.two_stage_lookup(ck, enc_table, tgsw, low, P, tuned=True)
 
-        out_tuned, ms_tuned = timed(tuned_way)
+        eng = ck.engine(0)
+        eng.set_option("acc_dispatch", 1 if by_size else 0)
+        try:
+            out_tuned, ms_tuned = timed(tuned_way)
+            tuned_kernel = eng.last_kernel_name()
+        finally:
+            eng.set_option("acc_dispatch", 0)
         assert np.array_equal(out_tuned.data, out_new.data), "the tuned rotation's words differ"
 
     hlwe = tfhe.encrypt(rng, sk, hbits.reshape(-1)).data.reshape(ADDRESSES, DEPTH, -1)                                 # [B][3][n+1]
@@ -116,7 +124,7 @@ def main(tuned=False):
     print(f"{ADDRESSES} addresses into a {P << DEPTH}-entry table, all answers correct both ways")
     print(f"  private table, TGSW high bits, computed LWE digit : {ms_new:8.2f} ms  (2 rotations + {(1 << DEPTH) - 1} external products per address)")
     if tuned:
-        print(f"  the same with the rotation on the gates' kernel   : {ms_tuned:8.2f} ms  (equal words)")
+        print(f"  the same with the rotation on the gates' kernel   : {ms_tuned:8.2f} ms  (equal words; {tuned_kernel})")
     print(f"  public table, LWE high bits, lookups and MUX gates: {ms_old:8.2f} ms  ({1 + 3 * ((1 << DEPTH) + 2 * ((1 << DEPTH) - 1))} rotations per address)")
     ck.close()
     return ms_new, ms_old
@@ -125,4 +133,6 @@ def main(tuned=False):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--tuned", action="store_true", help="also run the lookup with its rotation on the gates' kernel (tfhe_bootstrap_acc_batch)")
-    main(ap.parse_args().tuned)
+    ap.add_argument("--by-size", action="store_true", help="with --tuned: option acc_dispatch 1, the rotation's kernel chosen by batch size as a gate batch's is")
+    args = ap.parse_args()
+    main(args.tuned, args.by_size)

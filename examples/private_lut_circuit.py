@@ -11,8 +11,13 @@ only its three address selectors (Engine.tgsw_update).
 The host path (two_stage_lookup around a digit circuit: three downloads and three uploads per request, the whole key re-uploaded as
 selectors) computes the same words; the example checks the circuit's answer against it word for word and both by decryption.
 
-    python examples/private_lut_circuit.py
+    python examples/private_lut_circuit.py [--tuned]
+
+--tuned: the circuit is also run with its rotation node on the gates' own key and kernels (Circuit.blind_rotate(..., tuned=True):
+tfhe_bootstrap_acc_level) and the engine's option acc_dispatch at 1, so that the one row of a request takes the kernel a single gate
+takes; the selector set then holds the three address selectors alone.  Equal words, both times printed.
 """
+import argparse
 import os
 import sys
 import time
@@ -40,15 +45,16 @@ def digit_circuit():
     return c
 
 
-def lookup_circuit(n, N):
-    """The whole request: outputs (the table entry as a message of Z_8, the parity of its three bits as a gate bit)."""
+def lookup_circuit(n, N, tuned=False):
+    """The whole request: outputs (the table entry as a message of Z_8, the parity of its three bits as a gate bit).  `n` is where the
+    three address selectors sit in the loaded set; tuned: the rotation on the gates' key, which reads no selector."""
     c = tfhe.Circuit()
     a, b = c.inputs(2)
     table = c.tlwe_inputs(1 << DEPTH)
     s = c.linear([a, b], const=-(1 << 27))
     low = c.lut(digit_of, [s], P)                                       # the digit, computed from the wires
     picked = c.rot_net(leveled.tree_net(DEPTH), table, [n + v for v in range(DEPTH)], out="tlwe")[0]
-    answer = c.blind_rotate(picked, [low])                              # steps 0 ... n-1 on the key's selectors (sel None)
+    answer = c.blind_rotate(picked, [low], tuned=tuned)                 # steps 0 ... n-1 on the key's selectors (sel None), or on the gates' key
     bits = [c.lut(tfhe.make_gate_test_vector(lambda m, t=t: (m >> t) & 1, P, N), [answer], P) for t in range(3)]
     c.set_outputs([answer, c.xor(c.xor(bits[0], bits[1]), bits[2])])
     return c
@@ -73,17 +79,22 @@ def host_path(ck, enc_table, tgsw, digits):
     return tfhe.two_stage_lookup(ck, enc_table, tgsw, low, P).data
 
 
-def circuit_path(ck, enc_table, tgsw, digits):
-    """One Circuit.run per request; the key's selectors are loaded once, the request's three address selectors swapped behind them."""
-    n = ck.params.lwe_size
+def circuit_path(ck, enc_table, tgsw, digits, tuned=False):
+    """One Circuit.run per request; the key's selectors are loaded once, the request's three address selectors swapped behind them.
+    tuned: the rotation node on the gates' key (option acc_dispatch 1 while it runs), the selector set the address selectors alone."""
+    first = 0 if tuned else ck.params.lwe_size
     eng = ck.engine(0)
-    eng.tgsw_load(np.concatenate([leveled.bootstrap_key_selectors(ck), tgsw[0]]))
-    circuit = lookup_circuit(n, ck.params.tlwe_polynomial_degree)
+    eng.tgsw_load(tgsw[0] if tuned else np.concatenate([leveled.bootstrap_key_selectors(ck), tgsw[0]]))
+    circuit = lookup_circuit(first, ck.params.tlwe_polynomial_degree, tuned)
     out = []
-    for g in range(digits.shape[0]):
-        if g:
-            eng.tgsw_update(n, tgsw[g])
-        out.append(circuit.run(ck, digits[g], tlwe_inputs=enc_table).data)
+    eng.set_option("acc_dispatch", 1 if tuned else 0)
+    try:
+        for g in range(digits.shape[0]):
+            if g:
+                eng.tgsw_update(first, tgsw[g])
+            out.append(circuit.run(ck, digits[g], tlwe_inputs=enc_table).data)
+    finally:
+        eng.set_option("acc_dispatch", 0)
     return np.stack(out)                                                 # [B][2][n+1]: the answer, the parity bit
 
 
@@ -94,8 +105,9 @@ def timed(call):
     return out, (time.perf_counter() - t0) * 1e3
 
 
-def lookup_both_ways(rng, sk, ck, addresses):
-    """`addresses` random requests through both paths; returns (circuit ms, host ms) after checking the words and the decryptions."""
+def lookup_both_ways(rng, sk, ck, addresses, tuned=False):
+    """`addresses` random requests through both paths; returns (circuit ms, host ms) after checking the words and the decryptions —
+    and, with tuned, (circuit ms, host ms, tuned circuit ms) after checking the tuned circuit's words against the circuit's."""
     table = [int(v) for v in rng.integers(0, P, P << DEPTH)]
     high = rng.integers(0, 1 << DEPTH, addresses)
     da, db = rng.integers(0, 4, addresses), rng.integers(0, 4, addresses)
@@ -108,20 +120,28 @@ def lookup_both_ways(rng, sk, ck, addresses):
     assert np.array_equal(got, want), "the circuit's lookup decrypts wrongly"
     parity = tfhe.decrypt(sk, tfhe.LweSampleArray(np.ascontiguousarray(out_circ[:, 1])))
     assert np.array_equal(parity, [bin(int(v)).count("1") & 1 == 1 for v in want]), "the gates on the answer decrypt wrongly"
+    if tuned:
+        out_tuned, ms_tuned = timed(lambda: circuit_path(ck, enc_table, tgsw, digits, tuned=True))
+        assert np.array_equal(out_tuned, out_circ), "the tuned rotation node's words differ"
+        return ms_circ, ms_host, ms_tuned
     return ms_circ, ms_host
 
 
-def main():
+def main(tuned=False):
     rng = np.random.default_rng(2026)
     params = tfhe.tfhe_parameters_80()
     sk, ck = tfhe.make_key_pair(rng, params)
-    ms_circ, ms_host = lookup_both_ways(rng, sk, ck, ADDRESSES)
+    ms_circ, ms_host, *ms_tuned = lookup_both_ways(rng, sk, ck, ADDRESSES, tuned)
     print(f"{ADDRESSES} addresses into a private {P << DEPTH}-entry table, the same words both ways, all answers correct")
     print(f"  one Circuit per request on the device-resident tables : {ms_circ:8.2f} ms")
+    if tuned:
+        print(f"  the same, its rotation node on the gates' key (tuned)  : {ms_tuned[0]:8.2f} ms  (equal words)")
     print(f"  digit circuit, then two_stage_lookup through the host : {ms_host:8.2f} ms  (all requests in one batch)")
     ck.close()
     return ms_circ, ms_host
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tuned", action="store_true", help="also run the circuit with its rotation node on the gates' key (tfhe_bootstrap_acc_level, acc_dispatch 1)")
+    main(ap.parse_args().tuned)

@@ -590,8 +590,15 @@ int32_t tfhe_blind_rotate_level(tfhe_ctx *ctx, const int32_t *acc_slot, const in
  * "br_anyn") — the message names the shape and points to tfhe_blind_rotate_batch; TFHE_ERR_INVALID_ARG: as the two calls above;
  * TFHE_ERR_NO_KEY: no bootstrapping key, or out_form 2 without the keyswitch key; TFHE_ERR_NOMEM: the workspaces compared with the
  * device's free memory before anything is allocated.  B = 0 returns TFHE_OK.  tfhe_get_option(ctx, "bootstrap_acc") answers 1
- * where the context's shape and key layout are served, 0 otherwise.  Out of scope: the multi-wave families (h2, w2) for small
- * batches, k = 2, N = 512 and N = 2048, Circuit, and the multi-key forms (tfhe_mk_blind_rotate_batch / _level keep the any-N kernel). */
+ * where the context's shape and key layout are served, 0 otherwise.
+ * Option "acc_dispatch" (tfhe_set_option; 0 or 1, anything else TFHE_ERR_INVALID_ARG; default 0 = everything above): with 1 both calls
+ * choose kernel and geometry by batch size as a gate batch of B rotations does, under the same options ("br_tiny", "br_small",
+ * "br_rt_l", "w2_rw", "v3_rw", "br_split"): up to br_tiny rows (one per CU; l = 2, 3) the ACC form of the 4 l-wave kernel,
+ * "blind_rotate_kernel_h2_acc<L>"; up to br_small rows (four per CU) that of the two-wave kernel,
+ * "blind_rotate_kernel_w2_acc<L[,rw2]>"; above, the one-wave form; and a batch above 8 rows per CU whose last round is at most
+ * br_small rows is two launches on the context's stream, "blind_rotate_kernel_v3_acc<..> + blind_rotate_kernel_w2_acc<..>" (or
+ * h2_acc).  The words, the checks, the refusals and the timing slots do not depend on the option (csrc/engine_bootstrap_acc_small.hip).
+ * Out of scope: k = 2, N = 512 and N = 2048, and the multi-key forms (tfhe_mk_blind_rotate_batch / _level keep the any-N kernel). */
 int32_t tfhe_bootstrap_acc_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t n_out,
                                  int32_t out_form, int32_t *out, int64_t B);
 int32_t tfhe_bootstrap_acc_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,

@@ -637,7 +637,9 @@ end
 `blind_rotate` on the gates' own kernel and key (tfhe_bootstrap_acc_batch): `rows` is `(n+1) x B`, LWE samples, which pass unchanged;
 the steps are the context's `n` under the loaded bootstrapping key and no selector set is read.  `acc`, the 1-based `acc_index`,
 `n_out`, `out_form` and the result are `blind_rotate`'s, and so are the words where the selector set holds the key's `n` entries in
-order.  Served at `N = 1024`, `k = 1` (option "bootstrap_acc").
+order.  Served at `N = 1024`, `k = 1` (option "bootstrap_acc").  With the context's option "acc_dispatch" set to 1 (tfhe_set_option;
+default 0: one wave per row at every `B`) the kernel is chosen by `B` as a gate batch's is — the multi-wave kernels for small batches,
+a second launch for the last round of a large one; the words are the same.
 """
 function bootstrap_acc(gck::GpuCloudKey, acc::Array{Int32,3}, rows::AbstractMatrix, acc_index=nothing; n_out::Integer=1, out_form::Integer=2)
     p = gck.params
@@ -802,7 +804,7 @@ end
 
 `bootstrap_acc` between the device-resident tables (tfhe_bootstrap_acc_level): `blind_rotate_level!` on the gates' own kernel and key,
 without a selector set.  Every argument, the 1-based slots and wires and the words are `blind_rotate_level!`'s with `sel = nothing`.
-Synchronous.
+Synchronous.  The context's option "acc_dispatch" (see `bootstrap_acc`) chooses the kernel by the number of rows; the words are the same.
 """
 function bootstrap_acc_level!(gck::GpuCloudKey, acc_slot, term_start, term_wire, term_coef; cst=nothing, n_out::Integer=1, out_form::Integer=2,
                               out_slot=nothing, out_wires=nothing)

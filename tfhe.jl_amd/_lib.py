@@ -591,7 +591,11 @@ class Engine:
         """blind_rotate on the gates' own kernel and key (tfhe_bootstrap_acc_batch): rows are LWE samples int32 [B][n+1], the steps are
         the context's n under the loaded bootstrapping key, no selector set is read.  acc, acc_index, n_out, out_form and the result
         are blind_rotate's, and so are the words where the selector set holds the key's n entries in order.  Served where
-        get_option("bootstrap_acc") is 1 (N = 1024, k = 1)."""
+        get_option("bootstrap_acc") is 1 (N = 1024, k = 1).
+        set_option("acc_dispatch", 1) (default 0: blind_rotate_kernel_v3_acc, one wave per row, at every B) lets the call choose its
+        kernel by B as a gate batch does, under the same options (br_tiny, br_small, br_rt_l, w2_rw, v3_rw, br_split): the 4 l-wave
+        kernel's ACC form up to one row per compute unit, the two-wave kernel's up to four, the one-wave form above, and a second launch
+        for the last round of a batch above eight.  The words are the same; last_kernel_name() tells which ran."""
         a = _i32c(acc)
         if a.ndim == 2:
             a = a[None]
@@ -682,7 +686,8 @@ class Engine:
 
     def bootstrap_acc_level(self, acc_slot, term_start, term_wire, term_coef, cst=None, n_out=1, out_form=2, out_slot=None, out_wires=None):
         """bootstrap_acc between the tables (tfhe_bootstrap_acc_level): blind_rotate_level on the gates' own kernel and key, without
-        a selector set.  Every argument and the words are blind_rotate_level's with sel None.  Synchronous."""
+        a selector set.  Every argument and the words are blind_rotate_level's with sel None.  Synchronous.
+        Option acc_dispatch (see bootstrap_acc) chooses the kernel by the number of rows; the words are the same."""
         def call(h, acc, start, wire, coef, c, _sel, n_out_, out_form_, os_, ow, B):
             return self._lib.tfhe_bootstrap_acc_level(h, acc, start, wire, coef, c, n_out_, out_form_, os_, ow, B)
         self._blind_rotate_level(call, self.n, acc_slot, term_start, term_wire, term_coef, cst, None, n_out, out_form, out_slot, out_wires)

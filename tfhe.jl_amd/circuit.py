@@ -19,7 +19,8 @@ supplies to run(..., tlwe_inputs=...), `rot_net(net, entries, selectors)` a CMUX
 rotation-0 case) over E TLWE nodes, `blind_rotate(acc, terms)` the blind rotation of a TLWE node by the integer combination of wires that
 a LUT would rotate its table by.  Either leaves TLWE nodes (out="tlwe") or, extracted and keyswitched, ordinary wires (out="lwe").  The
 planner gives TLWE nodes slots of the engine's TLWE table as wires get rows of the wire table and levels them with the gate, LUT and
-linear nodes; a level issues one tfhe_blind_rotate_level per (n_out, out, sel) and one tfhe_rot_net_level per network node.  The
+linear nodes; a level issues one tfhe_blind_rotate_level per (n_out, out, sel), one tfhe_bootstrap_acc_level per (n_out, out) of its
+tuned=True rotations (the gates' own key and kernels: no selector set) and one tfhe_rot_net_level per network node.  The
 selectors are indices into the engine's loaded set: loading it (Engine.tgsw_load: the bootstrapping key's n selectors for the rotations'
 sel=None, address-bit selectors behind them; Engine.tgsw_update swaps those per request) stays the caller's job."""
 import numbers
@@ -60,6 +61,7 @@ class Circuit:
         self._n_tlwe_inputs = 0
         self._rot_nets = []       # (level, E, widths, nodes [..][5] with absolute level-0 sources, selectors [V], out_form, first out slot, [output wires])
         self._rotations = []      # (level, acc slot, terms, constant, n_out, out_form, sel tuple or None, out slot, [output wires])
+        self._rotation_tuned = []  # per rotation: True = on the gates' own key and kernels (Engine.bootstrap_acc_level)
 
     # ---- building -----------------------------------------------------------------------------------
     def input(self):
@@ -196,10 +198,16 @@ class Circuit:
         self._rot_nets.append((level, max(slots) + 1, np.asarray(net.widths, np.int32), nodes, sel, form, first, wires, getattr(net, "degree", None)))
         return wires if form == 2 else [TlweNode(first + i) for i in range(F)]
 
-    def blind_rotate(self, acc, terms, const=0, n_out=1, out="lwe", sel=None):
+    def blind_rotate(self, acc, terms, const=0, n_out=1, out="lwe", sel=None, tuned=False):
         """The TLWE node `acc` rotated by the combination of `terms` + const (as lut's; the context's n steps, selector sel[i] — None: i
         — of the engine's loaded set for step i): one TLWE node (out="tlwe", n_out 1) or the n_out extractions at the coefficients
-        j N / n_out, keyswitched, as wires (out="lwe"; n_out = 1: one wire, else a list)."""
+        j N / n_out, keyswitched, as wires (out="lwe"; n_out = 1: one wire, else a list).
+        tuned=True rotates on the gates' own key and kernels instead (Engine.bootstrap_acc_level: the same words where
+        get_option("bootstrap_acc") is 1, that is N = 1024, k = 1; run raises ValueError elsewhere): the steps are the bootstrapping key's,
+        so sel must be None, and the node needs no loaded selector set.  With the engine's option acc_dispatch 1 a level's one or few
+        tuned rows take the multi-wave kernels a gate batch of that size takes."""
+        if tuned and sel is not None:
+            raise ValueError("tuned=True rotates by the gates' key, the bootstrapping key in step order: sel must be None")
         form = self._out_form(out)
         slot = self._check_tlwe(acc)
         n_out = int(n_out)
@@ -211,6 +219,7 @@ class Circuit:
         first = self._new_tlwe(level, 1) if form == 0 else -1
         wires = [self._new_wire(level) for _ in range(n_out)] if form == 2 else []
         self._rotations.append((level, slot, folded, cst, n_out, form, key, first, wires))
+        self._rotation_tuned.append(bool(tuned))
         if form == 0:
             return TlweNode(first)
         return wires[0] if n_out == 1 else wires
@@ -347,20 +356,24 @@ class Circuit:
             if self._tlwe_level:
                 if M != 1:
                     raise ValueError("a circuit with TLWE nodes runs one instance at a time (run, not run_batch)")
+                # one call per (n_out, out, sel), the tuned rotations (sel None) grouped apart from the others: "bootstrap_acc"
                 groups = {}
-                for r in self._rotations:
+                for r, tuned in zip(self._rotations, self._rotation_tuned):
                     if r[0] == level:
-                        groups.setdefault((r[4], r[5], r[6]), []).append(r)
-                rot = []
-                for (n_out, form, sel), rs in groups.items():
+                        groups.setdefault((tuned, r[4], r[5], r[6]), []).append(r)
+                rot, rot_tuned = [], []
+                for (tuned, n_out, form, sel), rs in groups.items():
                     start, wire, coef, cst, _ = rows([(r[2], r[3], [0]) for r in rs], 1)
-                    rot.append((np.array([r[1] for r in rs], np.int32), start, wire, coef, cst, None if sel is None else np.array(sel, np.int32), n_out, form,
-                                np.array([r[7] for r in rs], np.int32) if form == 0 else None,
-                                np.array([w for r in rs for w in r[8]], np.int32) if form == 2 else None))
+                    (rot_tuned if tuned else rot).append(
+                        (np.array([r[1] for r in rs], np.int32), start, wire, coef, cst, None if sel is None else np.array(sel, np.int32), n_out, form,
+                         np.array([r[7] for r in rs], np.int32) if form == 0 else None,
+                         np.array([w for r in rs for w in r[8]], np.int32) if form == 2 else None))
                 nets = [(SimpleNamespace(entries=E, widths=widths, levels=int(widths.size), nodes=nodes, variables=len(sel), degree=N if degree is None else degree),
                          np.array([sel], np.int32), form, max(first, 0), np.array(wires, np.int32) if form == 2 else None)
                         for (lv, E, widths, nodes, sel, form, first, wires, degree) in self._rot_nets if lv == level]
                 plan[-1]["blind_rotate"], plan[-1]["rot_net"] = rot, nets
+                if rot_tuned:
+                    plan[-1]["bootstrap_acc"] = rot_tuned
         return plan
 
     def _run_plan(self, eng, plan, mk):
@@ -376,6 +389,8 @@ class Circuit:
                 linear_level(*lv["linear"])
             for acc, start, wire, coef, cst, sel, n_out, form, out_slot, out_wires in lv.get("blind_rotate", ()):
                 eng.blind_rotate_level(acc, start, wire, coef, cst=cst, sel=sel, n_out=n_out, out_form=form, out_slot=out_slot, out_wires=out_wires)
+            for acc, start, wire, coef, cst, _, n_out, form, out_slot, out_wires in lv.get("bootstrap_acc", ()):
+                eng.bootstrap_acc_level(acc, start, wire, coef, cst=cst, n_out=n_out, out_form=form, out_slot=out_slot, out_wires=out_wires)
             for net, sel, form, out_first, out_wires in lv.get("rot_net", ()):
                 eng.rot_net_level(net, sel, out_form=form, out_first=out_first, out_wires=out_wires)
 
@@ -410,6 +425,9 @@ class Circuit:
         if self._n_inputs:
             eng.wires_upload(0, m)
         plan = self.level_plan(eng.N)
+        if any(self._rotation_tuned) and eng.get_option("bootstrap_acc") != 1:
+            raise ValueError(f"tuned=True: Engine.bootstrap_acc serves N = 1024, k = 1 in the gates' key layout; this context has "
+                             f"N = {eng.N}, k = {eng.k} (option bootstrap_acc is 0): use tuned=False")
         if self._tlwe_level:
             eng.tlwe_alloc(self.num_tlwe)
             if self._n_tlwe_inputs:

@@ -27,6 +27,8 @@
 //                             engine_mk_rot_net.hip's, tfhe_mk_tgsw_update / _expand_update engine_keys.hip's)              ("mk tlwe levels")
 //   engine_bootstrap_acc.hip    the same rotation on the gates' key and kernel: the ACC form of blind_rotate_kernel_v3, compiled here alone
 //                             (TFHE_ACC_KERNELS), tfhe_bootstrap_acc_batch and tfhe_bootstrap_acc_level                      ("bootstrap acc")
+//   engine_bootstrap_acc_small.hip   the ACC forms of blind_rotate_kernel_w2 and blind_rotate_kernel_h2, compiled here alone: what the two
+//                             calls launch for small batches under option acc_dispatch                                       ("bootstrap acc small")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
 //   leveled_run.hpp       host-only: the one runner behind the twelve leveled entry points (workspaces, uploads, level loop, download)
 //   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share
@@ -282,6 +284,8 @@ struct tfhe_ctx {
     int k2_w3 = -1;              // tfhe_set_option("k2_w3", -1 | 0 | 1): the three-waves-per-rotation k = 2 kernel for batches of up to two rotations per CU and for the last round of a larger one (-1: by size), never (0), for every batch (1)
     int k2_rw = 0;               // tfhe_set_option("k2_rw", 0 | 1 | 7): rotations per workgroup of the k = 2 kernel; 0 = equally full rounds of up to seven per CU
     int v3_rw = 0;               // tfhe_set_option("v3_rw", 0 | 1 | 4): rotations per workgroup of the default kernel; 0 = 4 from 1536 rotations up
+    int acc_dispatch = 0;        // tfhe_set_option("acc_dispatch", 0 | 1): tfhe_bootstrap_acc_batch / _level on blind_rotate_kernel_v3_acc at every batch size (0), or on
+                                 //  the family a gate batch of that size takes — h2_acc, w2_acc, v3_acc, split — by launch_blind_rotate's rules (1)
     int64_t pipeline_min = 4096;   // tfhe_set_option("pipeline_min", n); < 0: never
     bool last_call_two_streams = false;   // the last batch call ran as two halves: timings span both streams
     // Pinned staging for the index maps of a call, a ring of kMapStages blocks: the H2D copy of a call's maps sits in the stream
@@ -544,6 +548,21 @@ int32_t br_launch_k2(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hi
 int32_t br_launch_h2(tfhe_ctx *c, const WithTv<BrArgs> &a, const H2Tables &ht, const BrLaunch &g, hipStream_t s);
 int32_t br_launch_w2(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
 int32_t br_launch_v3(tfhe_ctx *c, const WithTv<BrArgs> &a, const BrLaunch &g, hipStream_t s);
+// engine_dispatch.hip: which of the three families of N = 1024, k = 1 a batch of R rotations takes (h2 first, then w2, else v3), each
+// family's geometry, the tail of a split launch (0: one launch) and the families' kernel names — shared by launch_blind_rotate_part and
+// the ACC rotation under option acc_dispatch (engine_bootstrap_acc.hip)
+bool br_takes_h2(const tfhe_ctx *c, size_t R);
+bool br_takes_w2(const tfhe_ctx *c, size_t R);
+H2Tables br_h2_tables(const tfhe_ctx *c);
+BrLaunch br_geo_h2(const tfhe_ctx *c, size_t R, bool dg);
+BrLaunch br_geo_w2(const tfhe_ctx *c, size_t R, bool dg);
+BrLaunch br_geo_v3(const tfhe_ctx *c, size_t R, bool dg);
+size_t br_split_tail(const tfhe_ctx *c, size_t R);
+void name_br(tfhe_ctx *c, const char *family, int L, const char *rest = "");
+// engine_bootstrap_acc_small.hip: the ACC forms of the multi-wave gate kernels as launch handles — blind_rotate_kernel_w2_acc<L, false, rw>
+// for L = 2 | 3 | 0 and rw = 1 | 2, blind_rotate_kernel_h2_acc<L, false> for L = 2 | 3; NULL for anything else
+const void *acc_kernel_w2(int L, int rw);
+const void *acc_kernel_h2(int L);
 // engine_leveled.hip: grows the workspaces of one leveled call, all or none, after comparing what they would grow by with the device's
 // free memory (TFHE_ERR_NOMEM before anything is allocated)
 struct LvlWant { DevBuf *buf; size_t bytes; };

@@ -238,7 +238,7 @@ int32_t tfhe_get_option(tfhe_ctx *c, const char *name, int64_t *value) try
         {"level_split_min", c->level_split_min}, {"level_exchange", c->level_exchange}, {"br_prio_pct", c->br_prio_pct}, {"ks_slices", c->ks_slices_large},
         {"measure_margin", c->measure_margin ? 1 : 0}, {"pipeline_min", c->pipeline_min}, {"w2_rw", c->w2_rw}, {"k2_rw", c->k2_rw}, {"k2_w3", c->k2_w3}, {"n512_rw", c->n512_rw}, {"n512_w2", c->n512_w2},
         {"v3_rw", c->v3_rw}, {"mk_general", c->mk_force_general ? 1 : 0}, {"n2048_rw", c->n2048_rw}, {"mkg_acc", c->mkg_acc},
-        {"mkg_variant", c->mkg_variant}, {"mkg_rw", c->mkg_rw}, {"mk_rw", c->mk_rw}, {"ks_variant", c->ks_variant},
+        {"mkg_variant", c->mkg_variant}, {"mkg_rw", c->mkg_rw}, {"mk_rw", c->mk_rw}, {"ks_variant", c->ks_variant}, {"acc_dispatch", c->acc_dispatch},
     };
     for (const auto &e : table)
         if (!strcmp(name, e.n)) { *value = e.v; return TFHE_OK; }
@@ -330,6 +330,11 @@ int32_t tfhe_set_option(tfhe_ctx *c, const char *name, int64_t value) try
     if (!strcmp(name, "v3_rw")) {
         if (value != 0 && value != 1 && value != 4) return c->set_err(TFHE_ERR_INVALID_ARG, "set_option: v3_rw must be 0 (by batch size), 1 or 4");
         c->v3_rw = (int)value;
+        return TFHE_OK;
+    }
+    if (!strcmp(name, "acc_dispatch")) {
+        if (value != 0 && value != 1) return c->set_err(TFHE_ERR_INVALID_ARG, "set_option: acc_dispatch must be 0 (blind_rotate_kernel_v3_acc at every batch size) or 1 (by batch size, as a gate batch)");
+        c->acc_dispatch = (int)value;
         return TFHE_OK;
     }
     if (!strcmp(name, "mk_general")) { c->mk_force_general = value != 0; return TFHE_OK; }

@@ -57,10 +57,67 @@ int br_inst_l(const tfhe_ctx *c)
 }
 
 // "blind_rotate_kernel_<family><L<rest>>"; the run-time-l instantiation also names the context's l: "...<0<rest>>(l=<l>)"
-static void name_br(tfhe_ctx *c, const char *family, int L, const char *rest = "")
+void name_br(tfhe_ctx *c, const char *family, int L, const char *rest)
 {
     if (L) name_kernel(c, "blind_rotate_kernel_%s<%d%s>", family, L, rest);
     else name_kernel(c, "blind_rotate_kernel_%s<0%s>(l=%d)", family, rest, c->P.bs_l);
+}
+
+// ---- the three families of N = 1024, k = 1: which one a batch of R rotations takes and its geometry ----------------------------------
+// Written once for the two dispatchers that choose among them: launch_blind_rotate_part below (the mu / DIAG / TV kernels) and the
+// ACC rotation under option acc_dispatch (engine_bootstrap_acc.hip), which launches the families' ACC forms with the same geometry.
+// every transform split over two waves (4 l waves per rotation: instantiated for the shipped l only), up to br_tiny rotations
+bool br_takes_h2(const tfhe_ctx *c, size_t R)
+{
+    const int L = c->P.bs_l;
+    const int64_t tiny = c->br_tiny == -2 ? (int64_t)c->cu_count : c->br_tiny;
+    return tiny >= 0 && (int64_t)R <= tiny && (L == 2 || L == 3) && !c->br_rt_l;
+}
+// two waves per rotation, up to br_small rotations
+bool br_takes_w2(const tfhe_ctx *c, size_t R)
+{
+    return c->br_small >= 0 && (int64_t)R <= c->br_small;
+}
+H2Tables br_h2_tables(const tfhe_ctx *c)
+{
+    H2Tables ht;
+    ht.tw1h = c->d_tables + kH2TableOffset; ht.tw2q = ht.tw1h + 512; ht.tw3q = ht.tw2q + 64;
+    return ht;
+}
+BrLaunch br_geo_h2(const tfhe_ctx *c, size_t R, bool dg)
+{
+    const int L = c->P.bs_l;
+    // acc[2][N] | transposition buffers [4L][320] | extra slots [4L][256] | rotated differences [2 (step parity)][2][N]
+    const size_t ldsh = 2 * kImg * 4 + (size_t)4 * L * (kH2Buf + 256) * sizeof(cplx) + 2 * 2 * kN * 4;
+    return BrLaunch{L, 1, dg, dim3((unsigned)R), dim3(256 * L), ldsh};
+}
+BrLaunch br_geo_w2(const tfhe_ctx *c, size_t R, bool dg)
+{
+    // 27.4 KB of LDS and < 256 registers per wave: four workgroups per CU, 1024 rotations resident at two waves per SIMD.
+    // Two rotations per workgroup (lockstep through the step barrier, key reads shared in L1) when that fills the CUs evenly: from
+    // more than one rotation up to one pair per CU (300 rotations 2.26 vs 2.58 ms, 512: 2.29 vs 2.57; 128-bit set 3.64 vs 4.10) and at (nearly) two
+    // pairs per CU (1024: 3.35 vs 3.41; 128-bit 5.36 vs 5.57); in between single rotations spread better (700: 2.95 vs 3.29)
+    const size_t cus2 = 2 * (size_t)c->cu_count;
+    const bool pairs = !dg && (c->w2_rw == 2 || (c->w2_rw == 0 && ((R > cus2 / 2 && R <= cus2) || R > 2 * cus2 - cus2 / 8)));
+    const int rw = pairs ? 2 : 1;
+    return BrLaunch{br_inst_l(c), rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(128 * rw), (size_t)rw * kW2LdsBytes};
+}
+BrLaunch br_geo_v3(const tfhe_ctx *c, size_t R, bool dg)
+{
+    // one wave per rotation: half of a transform's key chunk requested a transform ahead, pass-B twiddles in registers
+    // (round 3's <l, 16> / <l, 8, tw2 in LDS> variants were A/B scaffolding and are gone); four rotations per workgroup in
+    // lockstep once the batch puts two waves on most SIMDs (option v3_rw: 0 = by batch size, 1, 4)
+    const bool group = c->v3_rw == 4 || (c->v3_rw == 0 && R >= 6 * (size_t)c->cu_count);      // 1536 on 256 CUs (1400 rotations: 5.47 vs 5.40 ms, 1700: 5.50 vs 5.66, 2000: 5.69 vs 5.93)
+    const int rw = group ? 4 : 1;
+    return BrLaunch{br_inst_l(c), rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(64 * rw), (size_t)rw * kV3LdsBytes};
+}
+// the last, partly filled round of a batch above what the chip holds on the one-wave kernel (8 per CU), where launch_blind_rotate's
+// rule sends it to the multi-wave kernels in a second launch (see there); 0: one launch
+size_t br_split_tail(const tfhe_ctx *c, size_t R)
+{
+    if (!c->br_split || c->br_small <= 0) return 0;
+    const size_t resident = 8 * (size_t)c->cu_count;      // rotations of blind_rotate_kernel_v3 on the chip
+    return R > resident && R % resident > 0 && R % resident <= (size_t)c->br_small ? R % resident : 0;
 }
 
 // Blind rotation of rotations [first, first + R) of the batch (rows of the bara / ext workspaces): picks the kernel and geometry for
@@ -207,42 +264,26 @@ static int32_t launch_blind_rotate_part(tfhe_ctx *c, size_t first, size_t R, int
         name_br(c, "k2", L, grouped ? ",rw7" : "");
         return TFHE_OK;
     }
-    const int64_t tiny = c->br_tiny == -2 ? (int64_t)c->cu_count : c->br_tiny;
-    if (tiny >= 0 && (int64_t)R <= tiny && (L == 2 || L == 3) && !c->br_rt_l) {      // (4 l waves per rotation: instantiated for the shipped l only)
-        // every transform split over two waves
-        H2Tables ht;
-        ht.tw1h = c->d_tables + kH2TableOffset; ht.tw2q = ht.tw1h + 512; ht.tw3q = ht.tw2q + 64;
-        // acc[2][N] | transposition buffers [4L][320] | extra slots [4L][256] | rotated differences [2 (step parity)][2][N]
-        const size_t ldsh = 2 * kImg * 4 + (size_t)4 * L * (kH2Buf + 256) * sizeof(cplx) + 2 * 2 * kN * 4;
-        const BrLaunch geo{L, 1, dg, dim3((unsigned)R), dim3(256 * L), ldsh};
+    // (the three families' rules and geometries: br_takes_* / br_geo_* above)
+    if (br_takes_h2(c, R)) {
+        const H2Tables ht = br_h2_tables(c);
+        const BrLaunch geo = br_geo_h2(c, R, dg);
         const int32_t rc = tv_all ? br_launch_h2(c, with_tv(a, tv), ht, geo, s) : br_launch_h2(c, a, ht, geo, s);
         if (rc) return rc;
         name_br(c, "h2", L);
         return TFHE_OK;
     }
-    if (c->br_small >= 0 && (int64_t)R <= c->br_small) {
-        // 27.4 KB of LDS and < 256 registers per wave: four workgroups per CU, 1024 rotations resident at two waves per SIMD.
-        // Two rotations per workgroup (lockstep through the step barrier, key reads shared in L1) when that fills the CUs evenly: from
-        // more than one rotation up to one pair per CU (300 rotations 2.26 vs 2.58 ms, 512: 2.29 vs 2.57; 128-bit set 3.64 vs 4.10) and at (nearly) two
-        // pairs per CU (1024: 3.35 vs 3.41; 128-bit 5.36 vs 5.57); in between single rotations spread better (700: 2.95 vs 3.29)
-        const size_t cus2 = 2 * (size_t)c->cu_count;
-        const bool pairs = !dg && (c->w2_rw == 2 || (c->w2_rw == 0 && ((R > cus2 / 2 && R <= cus2) || R > 2 * cus2 - cus2 / 8)));
-        const int rw = pairs ? 2 : 1;
-        const BrLaunch geo{br_inst_l(c), rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(128 * rw), (size_t)rw * kW2LdsBytes};
+    if (br_takes_w2(c, R)) {
+        const BrLaunch geo = br_geo_w2(c, R, dg);
         const int32_t rc = tv_all ? br_launch_w2(c, with_tv(a, tv), geo, s) : br_launch_w2(c, a, geo, s);
         if (rc) return rc;
-        name_br(c, "w2", geo.L, pairs ? ",rw2" : "");
+        name_br(c, "w2", geo.L, geo.rw == 2 ? ",rw2" : "");
         return TFHE_OK;
     }
-    // one wave per rotation: half of a transform's key chunk requested a transform ahead, pass-B twiddles in registers
-    // (round 3's <l, 16> / <l, 8, tw2 in LDS> variants were A/B scaffolding and are gone); four rotations per workgroup in
-    // lockstep once the batch puts two waves on most SIMDs (option v3_rw: 0 = by batch size, 1, 4)
-    const bool group = c->v3_rw == 4 || (c->v3_rw == 0 && R >= 6 * (size_t)c->cu_count);      // 1536 on 256 CUs (1400 rotations: 5.47 vs 5.40 ms, 1700: 5.50 vs 5.66, 2000: 5.69 vs 5.93)
-    const int rw = group ? 4 : 1;
-    const BrLaunch geo{br_inst_l(c), rw, dg, dim3((unsigned)((R + rw - 1) / rw)), dim3(64 * rw), (size_t)rw * kV3LdsBytes};
+    const BrLaunch geo = br_geo_v3(c, R, dg);
     const int32_t rc = tv_all ? br_launch_v3(c, with_tv(a, tv), geo, s) : br_launch_v3(c, a, geo, s);
     if (rc) return rc;
-    name_br(c, "v3", geo.L, group ? ",8,tw2reg,rw4" : ",8,tw2reg");
+    name_br(c, "v3", geo.L, geo.rw == 4 ? ",8,tw2reg,rw4" : ",8,tw2reg");
     return TFHE_OK;
 }
 
@@ -324,9 +365,9 @@ int32_t launch_blind_rotate(tfhe_ctx *c, size_t R, int32_t mu, hipStream_t s, co
         // one launch
     } else if (c->br_split && !c->br_general && !c->measure_margin && c->P.N == kN && c->P.k == 2 && tuned_l && (c->k2_rw == 0 || c->k2_rw == 7) && c->k2_w3 != 1) {
         seg = k2_partition(R, (size_t)c->cu_count, c->k2_w3 < 0);
-    } else if (c->br_split && !c->br_general && c->P.N == kN && c->P.k == 1 && c->br_small > 0) {      // (any l: the run-time-l instantiations)
-        const size_t resident = 8 * (size_t)c->cu_count;      // rotations of blind_rotate_kernel_v3 on the chip
-        if (R > resident && R % resident > 0 && R % resident <= (size_t)c->br_small) seg = {{R - R % resident, -1}, {R % resident, -1}};
+    } else if (!c->br_general && c->P.N == kN && c->P.k == 1) {      // (any l: the run-time-l instantiations)
+        const size_t tail = br_split_tail(c, R);
+        if (tail) seg = {{R - tail, -1}, {tail, -1}};
     }
     // (a TV batch's kernels carry "+tv" in tfhe_last_kernel_name)
     auto part = [&](size_t first, size_t count, int kind) {

@@ -219,8 +219,12 @@ __global__ __launch_bounds__(256 * L, 1) void TV_KERNEL(blind_rotate_kernel_h2)(
         tw.tw2[q] = HT.tw2q[q * 16 + (lane & 15)];
         tw.tw3[q] = HT.tw3q[q * 4 + (lane & 3)];
     }
-    if (wv == 0) init_zero_poly(lane, acc_all);
-    else if (wv == 1) init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_all + kImg);
+    if constexpr (kACC) {
+        if (wv == 0) init_acc(lane, bara[P.n] & (2 * kN - 1), P, w, acc_all);      // the ACC form: the caller's sample, both images by one wave
+    } else {
+        if (wv == 0) init_zero_poly(lane, acc_all);
+        else if (wv == 1) init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_all + kImg);
+    }
     __syncthreads();
 
     // this lane's four frequencies f = 2 k' + h, k' = q + 4 q2 + 16 q3 + 64 q4: in the key's (v3) order frequency f sits
@@ -363,8 +367,12 @@ __global__ __launch_bounds__(256 * L, 1) void TV_KERNEL(blind_rotate_kernel_h2)(
         __syncthreads();
     }
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0);
-    int32_t *ext = P.ext + w * (kN + 1);
-    if (wv == 0) extract_mask_poly(lane, acc_all, ext);
-    else if (tid == 64) ext[kN] = acc_all[kImg + kMir];
-    if (wv == 1) store_bodies(P, w, lane, acc_all + kImg + kMir, kN);
+    if constexpr (kACC) {
+        if (wv == 0) store_acc(P, w, lane, acc_all);      // the ACC form: the whole accumulator and / or its n_out extractions, by one wave
+    } else {
+        int32_t *ext = P.ext + w * (kN + 1);
+        if (wv == 0) extract_mask_poly(lane, acc_all, ext);
+        else if (tid == 64) ext[kN] = acc_all[kImg + kMir];
+        if (wv == 1) store_bodies(P, w, lane, acc_all + kImg + kMir, kN);
+    }
 }

@@ -46,8 +46,12 @@ __global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(blind_rotate_kernel_w2)
 #pragma unroll
     for (int q = 0; q < 8; q++) tw1f[q] = P.T.tw1f[q * 64 + lane];
     if (tid < 64) tw2_lds[tid] = P.T.tw2[tid];
-    if (wv) init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds);
-    else init_zero_poly(lane, acc_lds);
+    if constexpr (kACC) {
+        if (wv == 0) init_acc(lane, bara[P.n] & (2 * kN - 1), P, w, acc_all);      // the ACC form: the caller's sample, both images by one wave
+    } else {
+        if (wv) init_body(lane, bara[P.n] & (2 * kN - 1), P, w, acc_lds);
+        else init_zero_poly(lane, acc_lds);
+    }
     __syncthreads();
     STAMP_DECL;
 
@@ -114,8 +118,12 @@ __global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(blind_rotate_kernel_w2)
     __syncthreads();
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0);
     if (padding) return;
-    int32_t *ext = P.ext + w * (kN + 1);
-    if (wv == 0) extract_mask_poly(lane, acc_all, ext);
-    else if (lane == 0) ext[kN] = acc_all[kImg + kMir];
-    if (wv == 1) store_bodies(P, w, lane, acc_all + kImg + kMir, kN);
+    if constexpr (kACC) {
+        if (wv == 0) store_acc(P, w, lane, acc_all);      // the ACC form: the whole accumulator and / or its n_out extractions, by one wave
+    } else {
+        int32_t *ext = P.ext + w * (kN + 1);
+        if (wv == 0) extract_mask_poly(lane, acc_all, ext);
+        else if (lane == 0) ext[kN] = acc_all[kImg + kMir];
+        if (wv == 1) store_bodies(P, w, lane, acc_all + kImg + kMir, kN);
+    }
 }

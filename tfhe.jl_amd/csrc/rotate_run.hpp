@@ -4,7 +4,8 @@
 // engine_bootstrap_acc.hip).  An entry point validates its arguments (leveled_checks.hpp), describes the
 // call in a RotatePlan and names its kernel; the workspace protocol, the map, the uploads, the prologue, the launch, the keyswitch, the
 // download and the timing are here and nowhere else: leveled_run.hpp's protocol for a call that is one launch and not a level loop.
-// The launch itself is the caller's (run_rotation_on's launcher): AnyNRotation below for the four, V3AccRotation for the two.
+// The launch itself is the caller's (run_rotation_on's launcher): AnyNRotation below for the four, V3AccRotation or, under option
+// acc_dispatch, AccDispatchRotation for the two.
 #pragma once
 #include "engine.hpp"
 #include "leveled_run.hpp"
@@ -54,8 +55,8 @@ struct RotateDev {
 //   L.kGateRows       true: the kernel reads rows already switched to Z_2N, as the gates' kernels do: the batch calls' rows go through the
 //                     modulus switch of tfhe_bootstrap_tv_batch (launch_modswitch) between events 0 and 1, and there are no per-row
 //                     ping-pong samples and no global spectrum accumulators; false: the any-N rotation kernels, which switch themselves
-//   L.prepare(c, d)   the kernel's arguments from d, its LDS grant; before the timing slot is taken
-//   L.launch(c, s)    the one launch
+//   L.prepare(c, d)   the kernel's arguments from d, the LDS grant of each kernel it will launch; before the timing slot is taken
+//   L.launch(c, s)    the rotation's launch on s: one, or (AccDispatchRotation's split call) two over disjoint rows, one after the other
 //   L.name(c, d)      tfhe_last_kernel_name
 // Timing events as the gate entry points: what stages the rows between events 0 and 1 (outside slot 0), the rotation in slot 0, the
 // keyswitch in slot 1.
