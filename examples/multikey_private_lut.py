@@ -15,8 +15,13 @@ looked up at the digit (16 rotations) and a tree of 15 MUX gates (two rotations 
 Every multi-key rotation at this parameter set adds noise with a standard deviation near 0.06 of the torus to a +-1/8 window (DESIGN
 4.11), so neither way decrypts every answer; the number that does is printed for both.
 
-    python examples/multikey_private_lut.py
+    python examples/multikey_private_lut.py [--tuned]
+
+--tuned: the two-stage lookup is also run with its rotation on the multi-key gates' own kernel and key (mk_two_stage_lookup(...,
+tuned=True); tfhe_mk_bootstrap_acc_batch): the bootstrapping key is not expanded and loaded a second time as P n selectors, the selector
+set holds the address bits alone.  The words are the same; the time and the kernel are printed.
 """
+import argparse
 import os
 import sys
 import time
@@ -45,7 +50,7 @@ def timed(call):
     return out, (time.perf_counter() - t0) * 1e3
 
 
-def main():
+def main(tuned=False):
     rng, params, sks, shared, parts, ck = rom.setup(2027)
     eng = ck.engine(0)
     N = params.tlwe_polynomial_degree
@@ -69,6 +74,16 @@ def main():
     out_new, ms_new = timed(new_way)
     right_new = int(np.sum(tfhe.mk_decrypt(sks, out_new) == want))
 
+    ms_tuned = None
+    if tuned:
+        def tuned_way():
+            low = eng.mk_bootstrap_tv(digit_tv, digits)
+            return tfhe.mk_two_stage_lookup(ck, enc_table, uni, OWNER, low, P, tuned=True)
+
+        out_tuned, ms_tuned = timed(tuned_way)
+        tuned_kernel = eng.last_kernel_name()
+        assert np.array_equal(out_tuned, out_new), "the tuned rotation's words differ"
+
     hlwe = tfhe.mk_encrypt(rng, sks, hbits.reshape(-1)).reshape(ADDRESSES, DEPTH, -1)
     idx = np.tile(np.arange(1 << DEPTH, dtype=np.int32), ADDRESSES)
 
@@ -87,6 +102,8 @@ def main():
     print(f"{ADDRESSES} jointly encrypted addresses into party 0's {P << DEPTH}-entry table")
     print(f"  private table, uni-encrypted high bits, computed digit : {ms_new:8.2f} ms  {right_new} of {ADDRESSES} decrypt  "
           f"(2 rotations + {(1 << DEPTH) - 1} multi-key external products per address)")
+    if tuned:
+        print(f"  the same with the rotation on the gates' kernel         : {ms_tuned:8.2f} ms  (equal words; {tuned_kernel})")
     print(f"  public table, LWE high bits, lookups and MUX gates     : {ms_old:8.2f} ms  {right_old} of {ADDRESSES} decrypt  "
           f"({1 + (1 << DEPTH) + 2 * ((1 << DEPTH) - 1)} rotations per address)")
     ck.close()
@@ -94,4 +111,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tuned", action="store_true", help="also run the lookup with its rotation on the multi-key gates' kernel (tfhe_mk_bootstrap_acc_batch)")
+    main(ap.parse_args().tuned)

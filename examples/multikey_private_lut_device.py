@@ -20,8 +20,13 @@ tfhe_mk_blind_rotate_level):
 Both paths compute the same words.  Every multi-key rotation at this parameter set adds noise with a standard deviation near 0.06 of the
 torus to a +-1/8 window, so neither path decrypts every answer; the number that does is printed for both.
 
-    python examples/multikey_private_lut_device.py
+    python examples/multikey_private_lut_device.py [--tuned]
+
+--tuned: the device-resident path is also run with its rotation on the multi-key gates' own kernel and key
+(mk_two_stage_lookup_device(..., tuned=True); tfhe_mk_bootstrap_acc_level): the key's P n selectors are never loaded, the selector set
+holds a request's address bits alone.  The words are the same; the time is printed.
 """
+import argparse
 import os
 import sys
 import time
@@ -71,8 +76,9 @@ def host_path(ck, enc_table, uni, digits, masks, digit_tv):
     return np.concatenate(out)
 
 
-def device_path(ck, enc_table, uni, digits, masks, digit_tv):
-    """The same requests between the device-resident tables: per request one upload of its wires, four level calls and one gather."""
+def device_path(ck, enc_table, uni, digits, masks, digit_tv, tuned=False):
+    """The same requests between the device-resident tables: per request one upload of its wires, four level calls and one gather.
+    tuned: the rotation by tfhe_mk_bootstrap_acc_level, on the gates' kernel and key."""
     eng = ck.engine(0)
     eng.mk_tlwe_alloc(SLOTS)
     eng.mk_tlwe_upload(S_TABLE, enc_table)
@@ -84,7 +90,7 @@ def device_path(ck, enc_table, uni, digits, masks, digit_tv):
         eng.wires_upload(W_DIGIT, digits[rows])
         eng.wires_upload(W_MASK, masks[rows])
         eng.mk_lut_level(digit_tv, np.arange(ROWS + 1, dtype=np.int32), W_DIGIT + every, one, None, W_LOW + every)
-        leveled.mk_two_stage_lookup_device(ck, S_TABLE, [a[rows] for a in uni], OWNER, W_LOW + every, W_ANS + every, work_slot=S_WORK)
+        leveled.mk_two_stage_lookup_device(ck, S_TABLE, [a[rows] for a in uni], OWNER, W_LOW + every, W_ANS + every, work_slot=S_WORK, tuned=tuned)
         eng.mk_gates_level(np.full(ROWS, NAND, np.uint8), W_ANS + every, W_MASK + every, None, W_OUT + every)
         out.append(eng.wires_gather(W_OUT + every))
     return np.concatenate(out)
@@ -102,7 +108,7 @@ def timed(call):
     return out, (time.perf_counter() - t0) * 1e3
 
 
-def main():
+def main(tuned=False):
     rng, params, sks, shared, parts, ck = rom.setup(2028)
     N = params.tlwe_polynomial_degree
     A = REQUESTS * ROWS
@@ -115,6 +121,10 @@ def main():
     out_host, ms_host = timed(lambda: host_path(ck, enc_table, uni, digits, masks, digit_tv))
     out_dev, ms_dev = timed(lambda: device_path(ck, enc_table, uni, digits, masks, digit_tv))
     equal = bool(np.array_equal(out_host, out_dev))
+    ms_tuned = None
+    if tuned:
+        out_tuned, ms_tuned = timed(lambda: device_path(ck, enc_table, uni, digits, masks, digit_tv, tuned=True))
+        assert np.array_equal(out_tuned, out_dev), "the tuned rotation's words differ"
     right_host = int(np.sum(tfhe.mk_decrypt(sks, out_host) == want))
     right_dev = int(np.sum(tfhe.mk_decrypt(sks, out_dev) == want))
     moved = selectors_moved(params)
@@ -124,10 +134,14 @@ def main():
     print(f"{REQUESTS} requests of {ROWS} jointly encrypted addresses into party 0's {P << DEPTH}-entry table, each answer into a NAND gate")
     print(f"  host path   : {ms_host:8.2f} ms  {right_host} of {A} decrypt  ({moved['host']} selectors expanded and uploaded per request, 5 host round trips)")
     print(f"  device path : {ms_dev:8.2f} ms  {right_dev} of {A} decrypt  ({moved['device']} selectors expanded and uploaded per request, 1 upload and 1 gather)")
+    if tuned:
+        print(f"  device path, rotation on the gates' kernel : {ms_tuned:8.2f} ms  (equal words; no key selectors loaded, {moved['device']} per request)")
     print(f"  the two paths' words are equal: {equal}")
     ck.close()
     return ms_host, ms_dev, right_host, right_dev, equal
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tuned", action="store_true", help="also run the device path with its rotation on the multi-key gates' kernel (tfhe_mk_bootstrap_acc_level)")
+    main(ap.parse_args().tuned)

@@ -598,7 +598,7 @@ int32_t tfhe_blind_rotate_level(tfhe_ctx *ctx, const int32_t *acc_slot, const in
  * "blind_rotate_kernel_w2_acc<L[,rw2]>"; above, the one-wave form; and a batch above 8 rows per CU whose last round is at most
  * br_small rows is two launches on the context's stream, "blind_rotate_kernel_v3_acc<..> + blind_rotate_kernel_w2_acc<..>" (or
  * h2_acc).  The words, the checks, the refusals and the timing slots do not depend on the option (csrc/engine_bootstrap_acc_small.hip).
- * Out of scope: k = 2, N = 512 and N = 2048, and the multi-key forms (tfhe_mk_blind_rotate_batch / _level keep the any-N kernel). */
+ * Out of scope: k = 2, N = 512 and N = 2048.  The multi-key forms are tfhe_mk_bootstrap_acc_batch / _level, further down. */
 int32_t tfhe_bootstrap_acc_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows, int32_t n_out,
                                  int32_t out_form, int32_t *out, int64_t B);
 int32_t tfhe_bootstrap_acc_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,
@@ -786,6 +786,38 @@ int32_t tfhe_mk_rot_net_level(tfhe_ctx *ctx, const int32_t *table_first, int32_t
 int32_t tfhe_mk_blind_rotate_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,
                                    const int32_t *term_coef, const int32_t *cst, const int32_t *sel, int32_t n_out, int32_t out_form,
                                    const int32_t *out_slot, const int32_t *out_wires, int64_t B);
+
+/* The same two multi-key rotations on the multi-key gates' own kernel and key (additions within ABI v7): tfhe_mk_blind_rotate_batch and
+ * tfhe_mk_blind_rotate_level with steps = P n, in_form 0 and sel NULL, run by the ACC form of the two-waves-per-rotation kernel of the
+ * 2-party gates (mk_blind_rotate_kernel_w2 in csrc/kernels_multikey.hpp, compiled once more in csrc/engine_mk_bootstrap_acc.hip): the
+ * three polynomials of the accumulator stay in LDS for all P n steps.  The calls read the multi-key bootstrapping key in the layout the
+ * gates read (tfhe_mk_load_bootstrap_key_*, tfhe_mk_expand_load_bootstrap_key); they need no selector set — the key need not be
+ * expanded and loaded a second time as P n selectors — and leave a loaded one alone.  The result equals, word for word, that of
+ * tfhe_mk_blind_rotate_batch(acc, T, acc_index, rows, steps = P n, in_form 0, sel NULL, n_out, out, B, out_form), respectively
+ * tfhe_mk_blind_rotate_level(..., sel NULL, ...), where the selector set holds the loaded bootstrapping key's P n entries in order.
+ * Served: 2 parties (those of the loaded key), N = 1024, l = 4, the tuned key layout — mktfhe_parameters_2party.  Option "mk_general" is
+ * ignored: there is one ACC family, and the tuned and the any-party kernel read the same key layout.
+ * Buffer shapes (acc [T][P+1][N], acc_index, out), the n_out rule, the out_forms 0 / 1 / 2 and, for the level call, the terms, the slot,
+ * wire and overlap rules are those of tfhe_mk_blind_rotate_batch and tfhe_mk_blind_rotate_level above.  rows: host int32 [B][P n + 1],
+ * multi-key LWE samples, staged by tfhe_mk_bootstrap_tv_batch's modulus switch; the level call's rows by tfhe_mk_lut_level's prologue
+ * (a call without terms stages its rows on the host and needs no wire table), as tfhe_mk_blind_rotate_level's.
+ * Geometry: the gates' — option "mk_rw": 0 = one rotation per workgroup up to one row per CU and pairs in lockstep beyond, 1, 2 (an odd
+ * count in pairs gets a padding rotation that stores nothing).  tfhe_last_kernel_name reports "mk_blind_rotate_kernel_w2_acc<4[,rw2]>";
+ * tfhe_last_rotation_count = B; tfhe_last_timing_ms: 0 = the rotation, 1 = the keyswitch, 2 = both.
+ * Everything is validated on the host before anything is uploaded, and a refused call changes no slot and no wire.  TFHE_ERR_STATE:
+ * a single-key context, a multi-device context, measure_margin on (the level call: and a missing or unfit table, as
+ * tfhe_mk_blind_rotate_level), then a shape the kernel does not serve (parties != 2, l != 4, N != 1024) or a key that is not in its
+ * layout (the any-N kernels' layout) — the message names the shape and points to tfhe_mk_blind_rotate_batch; TFHE_ERR_INVALID_ARG: as
+ * the two calls above; TFHE_ERR_NO_KEY: no multi-key bootstrapping key, or out_form 2 without the multi-key keyswitch key;
+ * TFHE_ERR_NOMEM: the workspaces compared with the device's free memory before anything is allocated.  B = 0 returns TFHE_OK.
+ * tfhe_get_option(ctx, "mk_bootstrap_acc") answers 1 where the context's shape, its key's parties and its key layout are served, 0
+ * otherwise.  The single-key tfhe_bootstrap_acc_batch / _level keep refusing a multi-key context.
+ * Out of scope: the 4- and 8-party sets (mk_g2 and the any-party kernel have no ACC form), dispatch by batch size beyond "mk_rw". */
+int32_t tfhe_mk_bootstrap_acc_batch(tfhe_ctx *ctx, const int32_t *acc, int64_t T, const int32_t *acc_index, const int32_t *rows,
+                                    int32_t n_out, int32_t out_form, int32_t *out, int64_t B);
+int32_t tfhe_mk_bootstrap_acc_level(tfhe_ctx *ctx, const int32_t *acc_slot, const int32_t *term_start, const int32_t *term_wire,
+                                    const int32_t *term_coef, const int32_t *cst, int32_t n_out, int32_t out_form, const int32_t *out_slot,
+                                    const int32_t *out_wires, int64_t B);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

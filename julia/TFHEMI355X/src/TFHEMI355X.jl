@@ -39,7 +39,7 @@ using TFHE: LweSample, LweParams, CloudKey, SecretKey, SchemeParameters, MKCloud
 using Random: AbstractRNG, RandomDevice
 import Base.Broadcast: broadcastable, broadcasted
 
-export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate, tlwe_alloc!, tlwe_upload!, tlwe_download, tgsw_update!, rot_net_level!, blind_rotate_level!, mk_tlwe_alloc!, mk_tlwe_upload!, mk_tlwe_download, mk_tgsw_update!, mk_tgsw_expand_update!, mk_rot_net_level!, mk_blind_rotate_level!, bootstrap_acc, bootstrap_acc_level!
+export GpuCloudKey, GpuMKCloudKey, GpuLweArray, gates_batch, gates_batch_async, PendingGates, upload, download, tgsw_load!, extern_mul, cmux_tree, cmux_net, rot_net, blind_rotate, mk_tgsw_load!, mk_extern_mul, mk_cmux_tree, mk_cmux_net, mk_rot_net, mk_blind_rotate, tlwe_alloc!, tlwe_upload!, tlwe_download, tgsw_update!, rot_net_level!, blind_rotate_level!, mk_tlwe_alloc!, mk_tlwe_upload!, mk_tlwe_download, mk_tgsw_update!, mk_tgsw_expand_update!, mk_rot_net_level!, mk_blind_rotate_level!, bootstrap_acc, bootstrap_acc_level!, mk_bootstrap_acc, mk_bootstrap_acc_level!
 
 # the shared library as this repository builds it (make -C tfhe.jl_amd/csrc), or wherever TFHE_MI355X_LIB points
 const LIB = get(ENV, "TFHE_MI355X_LIB", joinpath(@__DIR__, "..", "..", "..", "tfhe.jl_amd", "lib", "libtfhe_mi355x.so"))
@@ -1408,6 +1408,75 @@ function mk_blind_rotate_level!(mck::GpuMKCloudKey, acc_slot, term_start, term_w
         (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Int64),
         mck.ctx, acc, start, tw, tc, c === nothing ? Ptr{Int32}(C_NULL) : pointer(c), s === nothing ? Ptr{Int32}(C_NULL) : pointer(s), Int32(n_out),
         Int32(out_form), os === nothing ? Ptr{Int32}(C_NULL) : pointer(os), ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
+    mck
+end
+
+"""
+    mk_bootstrap_acc(mck, acc::Array{Int32,3}, rows::AbstractMatrix, acc_index=nothing; n_out=1, out_form=2)
+
+`mk_blind_rotate` on the multi-key gates' own kernel and key (tfhe_mk_bootstrap_acc_batch): `rows` is `(P n + 1) x B`, multi-key LWE
+samples, which pass unchanged; the steps are the `P n` entries of the loaded multi-key bootstrapping key, read in the layout the gates
+read, and no selector set is needed (the key is not loaded a second time as selectors).  `acc`, `acc_index` (1-based; `nothing`:
+accumulator 1 for every row), `n_out`, `out_form` and the result are `mk_blind_rotate`'s, and so are the words where the selector set
+holds the key's entries in order.  Served for 2 parties, `N = 1024`, `l = 4` (option "mk_bootstrap_acc"); the context's option "mk_rw"
+(tfhe_set_option; 0 = by the number of rows, 1, 2) sets the rotations per workgroup as for the gates.
+"""
+function mk_bootstrap_acc(mck::GpuMKCloudKey, acc::Array{Int32,3}, rows::AbstractMatrix, acc_index=nothing; n_out::Integer=1, out_form::Integer=2)
+    p, P = mck.params, mck.parties
+    N, n = p.tlwe_polynomial_degree, p.lwe_size
+    T = size(acc, 3)
+    size(acc)[1:2] == (N, P + 1) && T >= 1 || error("tfhe_mi355x: accumulators must be N x (P+1) x T")
+    words, B = size(rows)
+    words == P * n + 1 || error("tfhe_mi355x: rows must be multi-key LWE samples, (P n + 1) x B")
+    0 <= out_form <= 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 TLWE, 1 extracted, 2 key-switched)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    r = Matrix{Int32}(rows)
+    idx = acc_index === nothing ? nothing : Int32.(collect(acc_index) .- 1)
+    idx === nothing || length(idx) == B || error("tfhe_mi355x: acc_index must have one entry per row")
+    width = out_form == 2 ? P * n : P * N
+    out = out_form == 0 ? Array{Int32}(undef, N, P + 1, B) : Array{Int32}(undef, width + 1, n_out * B)
+    B == 0 && return out_form == 2 ? MKLweSample[] : out
+    GC.@preserve acc r idx out @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_bootstrap_acc_batch, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Int64),
+        mck.ctx, acc, Int64(T), idx === nothing ? Ptr{Int32}(C_NULL) : pointer(idx), r, Int32(n_out), Int32(out_form), out, Int64(B)))
+    out_form == 2 || return out
+    params = LweParams(n)
+    [MKLweSample(params, reshape(out[1:n*P, r], n, P), out[n * P + 1, r], 0.) for r in 1:n_out*B]
+end
+
+"""
+    mk_bootstrap_acc_level!(mck, acc_slot, term_start, term_wire, term_coef; cst=nothing, n_out=1, out_form=2, out_slot=nothing, out_wires=nothing)
+
+`mk_bootstrap_acc` between the device-resident tables (tfhe_mk_bootstrap_acc_level): `mk_blind_rotate_level!` on the multi-key gates' own
+kernel and key, without a selector set.  Every argument and the words are `mk_blind_rotate_level!`'s with `sel = nothing`: slots and wires
+are 1-based, `term_start`, the coefficients and the constants pass unchanged.  Synchronous.
+"""
+function mk_bootstrap_acc_level!(mck::GpuMKCloudKey, acc_slot, term_start, term_wire, term_coef; cst=nothing, n_out::Integer=1, out_form::Integer=2,
+                                 out_slot=nothing, out_wires=nothing)
+    p = mck.params
+    N = p.tlwe_polynomial_degree
+    acc = Int32.(collect(acc_slot) .- 1)
+    B = length(acc)
+    start = Int32.(collect(term_start))
+    length(start) == B + 1 && start[1] == 0 && issorted(start) || error("tfhe_mi355x: term_start must be B + 1 non-decreasing entries from 0")
+    T = Int(start[end])
+    tw = Int32.(collect(term_wire) .- 1)
+    tc = Int32.(collect(term_coef))
+    length(tw) >= T && length(tc) >= T || error("tfhe_mi355x: term_wire and term_coef must have term_start[end] entries")
+    c = cst === nothing ? nothing : Int32.(collect(cst))
+    c === nothing || length(c) == B || error("tfhe_mi355x: cst must have one entry per row")
+    out_form == 0 || out_form == 2 || error("tfhe_mi355x: out_form = ", out_form, " (0 into MK TLWE slots, 2 key-switched into wires)")
+    ispow2(n_out) && n_out <= 32 && (n_out == 1 || n_out <= N ÷ 4) || error("tfhe_mi355x: n_out = ", n_out, " (a power of two <= 32, and 1 or <= N / 4)")
+    out_form != 0 || n_out == 1 || error("tfhe_mi355x: n_out must be 1 with out_form 0")
+    os = out_slot === nothing ? nothing : Int32.(collect(out_slot) .- 1)
+    ow = out_wires === nothing ? nothing : Int32.(collect(out_wires) .- 1)
+    out_form != 0 || (os !== nothing && length(os) == B) || error("tfhe_mi355x: out_slot must have one entry per row with out_form 0")
+    out_form != 2 || (ow !== nothing && length(ow) == n_out * B) || error("tfhe_mi355x: out_wires must have n_out * B entries with out_form 2")
+    GC.@preserve acc start tw tc c os ow @locked mck.ctx check(mck.ctx, ccall((:tfhe_mk_bootstrap_acc_level, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Int64),
+        mck.ctx, acc, start, tw, tc, c === nothing ? Ptr{Int32}(C_NULL) : pointer(c), Int32(n_out), Int32(out_form),
+        os === nothing ? Ptr{Int32}(C_NULL) : pointer(os), ow === nothing ? Ptr{Int32}(C_NULL) : pointer(ow), Int64(B)))
     mck
 end
 

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "tfhe_mk_blind_rotate_batch", "tfhe_tlwe_alloc", "tfhe_tlwe_upload", "tfhe_tlwe_download", "tfhe_tgsw_update",
     "tfhe_rot_net_level", "tfhe_blind_rotate_level", "tfhe_mk_tlwe_alloc", "tfhe_mk_tlwe_upload", "tfhe_mk_tlwe_download",
     "tfhe_mk_tgsw_update", "tfhe_mk_tgsw_expand_update", "tfhe_mk_rot_net_level", "tfhe_mk_blind_rotate_level",
-    "tfhe_bootstrap_acc_batch", "tfhe_bootstrap_acc_level",
+    "tfhe_bootstrap_acc_batch", "tfhe_bootstrap_acc_level", "tfhe_mk_bootstrap_acc_batch", "tfhe_mk_bootstrap_acc_level",
 ]
 ABI_VERSION = 7
 ERR_NOMEM = 6
@@ -191,6 +191,9 @@ def load():
     if hasattr(lib, "tfhe_bootstrap_acc_batch"):
         lib.tfhe_bootstrap_acc_batch.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, i64]
         lib.tfhe_bootstrap_acc_level.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64]
+    if hasattr(lib, "tfhe_mk_bootstrap_acc_batch"):
+        lib.tfhe_mk_bootstrap_acc_batch.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, i64]
+        lib.tfhe_mk_bootstrap_acc_level.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64]
     lib.tfhe_ctx_create_multi.argtypes = [C.POINTER(TfheParams), vp, i32, C.POINTER(vp)]
     lib.tfhe_ctx_device_count.argtypes = [vp]
     lib.tfhe_ctx_device_count.restype = i32
@@ -853,6 +856,34 @@ class Engine:
                                                          B, int(out_form)))
         return out
 
+    def mk_bootstrap_acc(self, acc, rows, acc_index=None, n_out=1, out_form=2):
+        """mk_blind_rotate on the multi-key gates' own kernel and key (tfhe_mk_bootstrap_acc_batch): rows are multi-key LWE samples int32
+        [B][P*n+1], the steps are the P n entries of the loaded multi-key bootstrapping key, no selector set is read (the key need not
+        be loaded a second time as selectors).  acc, acc_index, n_out, out_form and the result are mk_blind_rotate's, and so are the
+        words where the selector set is mk_bootstrap_key_selectors(ck).  Served where get_option("mk_bootstrap_acc") is 1 (2 parties,
+        N = 1024, l = 4); option mk_rw (0 = by B, 1, 2) sets the rotations per workgroup as for the gates."""
+        P = self._mk_width("mk_bootstrap_acc")
+        a = _i32c(acc)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (P + 1, self.N):
+            raise ValueError(f"accumulators must be [T][{P + 1}][{self.N}], got {a.shape}")
+        r = _i32c(rows)
+        if r.ndim != 2 or r.shape[1] != P * self.n + 1:
+            raise ValueError(f"rows must be multi-key LWE samples [B][{P * self.n + 1}], got {r.shape}")
+        B = r.shape[0]
+        idx = None
+        if acc_index is not None:
+            idx = _i32c(acc_index).reshape(-1)
+            if idx.size != B:
+                raise ValueError(f"acc_index must have one entry per row ({B}), got {idx.size}")
+        n_out = int(n_out)
+        K = n_out if 1 <= n_out <= 32 else 0
+        shape = {0: (B, P + 1, self.N), 1: (B, K, P * self.N + 1), 2: (B, K, P * self.n + 1)}.get(int(out_form), (0,))
+        out = np.empty(shape, np.int32)      # (an out_form or n_out the library refuses: nothing written)
+        self._check(self._lib.tfhe_mk_bootstrap_acc_batch(self._h, _ptr(a), a.shape[0], _ptr(idx), _ptr(r), n_out, int(out_form), _ptr(out), B))
+        return out
+
     # ---- multi-key leveled mode on device-resident tables: the MK TLWE table beside the multi-key wire table ----
     def mk_tlwe_alloc(self, slots):
         """A device table of MK TLWE samples int32 [slots][P+1][N] for the parties of the loaded multi-key bootstrapping key
@@ -915,6 +946,15 @@ class Engine:
         P = self._mk_width("mk_blind_rotate_level")
         self._blind_rotate_level(self._lib.tfhe_mk_blind_rotate_level, P * self.n, acc_slot, term_start, term_wire, term_coef, cst, sel, n_out,
                                  out_form, out_slot, out_wires)
+
+    def mk_bootstrap_acc_level(self, acc_slot, term_start, term_wire, term_coef, cst=None, n_out=1, out_form=2, out_slot=None, out_wires=None):
+        """mk_bootstrap_acc between the tables (tfhe_mk_bootstrap_acc_level): mk_blind_rotate_level on the multi-key gates' own kernel and
+        key, without a selector set.  Every argument and the words are mk_blind_rotate_level's with sel None.  Synchronous."""
+        P = self._mk_width("mk_bootstrap_acc_level")
+
+        def call(h, acc, start, wire, coef, c, _sel, n_out_, out_form_, os_, ow, B):
+            return self._lib.tfhe_mk_bootstrap_acc_level(h, acc, start, wire, coef, c, n_out_, out_form_, os_, ow, B)
+        self._blind_rotate_level(call, P * self.n, acc_slot, term_start, term_wire, term_coef, cst, None, n_out, out_form, out_slot, out_wires)
 
     # ---- levelised circuits on the device-resident wire table ----
     def wires_alloc(self, num_wires):

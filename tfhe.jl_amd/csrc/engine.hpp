@@ -29,6 +29,8 @@
 //                             (TFHE_ACC_KERNELS), tfhe_bootstrap_acc_batch and tfhe_bootstrap_acc_level                      ("bootstrap acc")
 //   engine_bootstrap_acc_small.hip   the ACC forms of blind_rotate_kernel_w2 and blind_rotate_kernel_h2, compiled here alone: what the two
 //                             calls launch for small batches under option acc_dispatch                                       ("bootstrap acc small")
+//   engine_mk_bootstrap_acc.hip   the same rotation under a multi-key cloud key on the 2-party gates' key and kernel: the ACC form of
+//                             mk_blind_rotate_kernel_w2, compiled here alone, tfhe_mk_bootstrap_acc_batch and tfhe_mk_bootstrap_acc_level  ("mk bootstrap acc")
 //   leveled_checks.hpp    host-only: the state and netlist checks that the leveled units share
 //   leveled_run.hpp       host-only: the one runner behind the twelve leveled entry points (workspaces, uploads, level loop, download)
 //   kernels_leveled_core.hpp  device-only: the CMUX level body the six level kernels share
@@ -213,6 +215,12 @@ struct tfhe_ctx {
     int mk_parties = 0;            // parties of the loaded multi-key bootstrapping key (the keyswitch key's: ks.parties; the gates need them equal)
     bool have_mk_bk = false;
     bool have_mk_ks() const { return ks.mode != 0 && ks.parties > 1; }
+    // the shape mk_blind_rotate_kernel_w2 serves with the key in its layout, on a one-device multi-key context: what the ACC form of that
+    // kernel (tfhe_mk_bootstrap_acc_batch / _level, engine_mk_bootstrap_acc.hip) needs; tfhe_get_option "mk_bootstrap_acc".  The parties
+    // are the loaded bootstrapping key's (a context may hold a key for fewer parties than it was created for), the context's before one is
+    // loaded.  Option mk_general does not matter: the tuned and the any-party kernel read the same key layout.
+    int mk_acc_parties() const { return have_mk_bk ? mk_parties : P.parties; }
+    bool mk_bootstrap_acc() const { return kids.empty() && P.parties >= 2 && mk_acc_parties() == 2 && P.bs_l == 4 && P.N == kN && !anyn(); }
 
     // device-resident wire table for levelised circuits: int32 [num_wires][n+1], or [num_wires][P n+1] for a multi-key table
     // (tfhe_mk_wires_alloc: wires_parties = P, fixed when the table is allocated; 0 = single-key rows)
@@ -563,6 +571,7 @@ void name_br(tfhe_ctx *c, const char *family, int L, const char *rest = "");
 // for L = 2 | 3 | 0 and rw = 1 | 2, blind_rotate_kernel_h2_acc<L, false> for L = 2 | 3; NULL for anything else
 const void *acc_kernel_w2(int L, int rw);
 const void *acc_kernel_h2(int L);
+// (engine_mk_bootstrap_acc.hip — the ACC form of mk_blind_rotate_kernel_w2 and the two entry points on it — exports nothing to the other units)
 // engine_leveled.hip: grows the workspaces of one leveled call, all or none, after comparing what they would grow by with the device's
 // free memory (TFHE_ERR_NOMEM before anything is allocated)
 struct LvlWant { DevBuf *buf; size_t bytes; };

@@ -219,6 +219,8 @@ int32_t tfhe_get_option(tfhe_ctx *c, const char *name, int64_t *value) try
     if (!strcmp(name, "debug_fail_alloc_after")) { *value = g_fail_alloc_countdown.load(); return TFHE_OK; }
     // read-only: tfhe_bootstrap_acc_batch / _level serve this context's shape and key layout
     if (!strcmp(name, "bootstrap_acc")) { *value = c->bootstrap_acc() ? 1 : 0; return TFHE_OK; }
+    // read-only: tfhe_mk_bootstrap_acc_batch / _level serve this context's shape, its key's parties and its key layout
+    if (!strcmp(name, "mk_bootstrap_acc")) { *value = c->mk_bootstrap_acc() ? 1 : 0; return TFHE_OK; }
     if (c->multi() && !strcmp(name, "peer_pairs")) {     // read-only: ordered pairs of DIFFERENT device contexts of this context that copy device to device
         int64_t n = 0;
         const size_t nk = c->kids.size();

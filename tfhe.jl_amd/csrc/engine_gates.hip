@@ -198,10 +198,12 @@ int32_t launch_prologue(tfhe_ctx *c, size_t R, const int32_t *d_in0, const int32
 }
 
 // the modulus switch alone (bootstrap.jl:74-75) of B samples at d_in into the context's bara workspace: tfhe_bootstrap_tv_batch's
-// prologue, for the callers outside this unit (rotate_run.hpp)
+// prologue, for the callers outside this unit (rotate_run.hpp).  Rows of n + 1 words, or of P n + 1 on a multi-key context (P: the parties
+// of its bootstrapping key), as bootstrap_rows switches them for tfhe_mk_bootstrap_tv_batch.
 int32_t launch_modswitch(tfhe_ctx *c, size_t B, const int32_t *d_in, hipStream_t s)
 {
-    hipLaunchKernelGGL(modswitch_kernel, dim3((unsigned)B), dim3(256), 0, s, d_in, (int32_t *)c->bara.p, c->P.n, ilog2i(2 * c->P.N));
+    const int n = c->P.parties != 1 ? c->mk_parties * c->P.n : c->P.n;      // (mask words of a sample)
+    hipLaunchKernelGGL(modswitch_kernel, dim3((unsigned)B), dim3(256), 0, s, d_in, (int32_t *)c->bara.p, n, ilog2i(2 * c->P.N));
     HIP_TRY(c, hipGetLastError());
     return TFHE_OK;
 }

@@ -22,6 +22,70 @@ struct MkBrArgs {
     int32_t mu;
     int32_t prio_steps;   // of the P * n steps of a rotation; see wave_priority_begin
 };
+// The ACC form of mk_blind_rotate_kernel_w2 (engine_mk_bootstrap_acc.hip: tfhe_mk_bootstrap_acc_batch / _level): WithAcc on the 2-party
+// struct, with MK TLWE samples of three polynomials — acc [T][3][N], out [.][3][N], ext [R][n_out][2 N + 1].  WithAcc's `ext` hides
+// MkBrArgs::ext as it hides BrArgs's.  The other multi-key families keep their structs (MkGenArgs has an `acc` of its own) and have no
+// ACC form.
+#ifdef TFHE_ACC_KERNELS
+template <>
+struct AccArgsOf<MkBrArgs> { using type = WithAcc<MkBrArgs>; };
+#endif
+// ---- the ACC form's two ends (mk_blind_rotate_kernel_w2_acc; nothing for every other kernel) ----------------------------------------
+// The three images of rotation w from the caller's sample: X^{-barb} acc[acc_index[w]] on both masks and the body (tv_coef's rule;
+// store_cur writes the mirror blocks).  Wave 0 fills polynomials 0 and 1, wave 1 the body: the split of the mu form's zeros and body.
+template <class A>
+__device__ __forceinline__ void mk_init_acc(int, int, int, const A &, size_t, int32_t *) {}
+__device__ __forceinline__ void mk_init_acc(int lane, int wv, int barb, const WithAcc<MkBrArgs> &P, size_t w, int32_t *acc_lds)
+{
+    constexpr int NP = 2;
+    const int32_t *v = P.acc + (size_t)__builtin_amdgcn_readfirstlane(P.acc_index[w]) * ((NP + 1) * kN);
+    const int c_begin = wv == 0 ? 0 : NP, c_end = wv == 0 ? NP : NP + 1;
+#pragma unroll 1
+    for (int c = c_begin; c < c_end; c++) {
+        int32_t b[16];
+#pragma unroll
+        for (int m = 0; m < 16; m++) b[m] = tv_coef(v + c * kN, (lane + 64 * m + barb) & (2 * kN - 1), kN);
+        store_cur<16>(lane, b, acc_lds + c * kImg);
+    }
+}
+// The final accumulator of rotation w, after the last hand-off of the pair (all three images are then visible to both waves).  Where
+// `out` is set the three polynomials go to out[out_index[w]] (out_index NULL: row w): wave c stores mask c, wave 1 also the body.
+// Where `ext` is set, for j < n_out the extraction at coefficient c = j N / n_out (mk_tlwe_extract_sample, mk_internals.jl:88-95, at c
+// instead of 0): word u of mask column p is coefficient c of X^u a_p — a_p[(c - u) mod N], negated when (c - u) mod 2N >= N, the
+// single-key store_acc's rule — written by wave p; the body word b[c] by one lane of wave 0.
+template <class A>
+__device__ __forceinline__ void mk_store_acc(const A &, size_t, int, int, const int32_t *) {}
+__device__ __forceinline__ void mk_store_acc(const WithAcc<MkBrArgs> &P, size_t w, int lane, int wv, const int32_t *acc_lds)
+{
+    constexpr int NP = 2;
+    if (P.out) {
+        const size_t row = P.out_index ? (size_t)__builtin_amdgcn_readfirstlane(P.out_index[w]) : w;
+        int32_t *o = P.out + row * ((NP + 1) * kN);
+#pragma unroll
+        for (int m = 0; m < 16; m++) o[wv * kN + lane + 64 * m] = acc_lds[wv * kImg + kMir + lane + 64 * m];
+        if (wv == 1) {
+#pragma unroll
+            for (int m = 0; m < 16; m++) o[NP * kN + lane + 64 * m] = acc_lds[NP * kImg + kMir + lane + 64 * m];
+        }
+    }
+    if (P.ext) {
+        static_assert(kN == 1 << 10, "the shift below");
+        const int n_out = 1 << P.log2_n_out;
+        const int32_t *a = acc_lds + wv * kImg + kMir, *b = acc_lds + NP * kImg + kMir;
+#pragma unroll 1
+        for (int j = 0; j < n_out; j++) {
+            const int c = j << (10 - P.log2_n_out);      // (kN = 2^10)
+            int32_t *e = P.ext + (w * n_out + j) * (NP * kN + 1);
+#pragma unroll
+            for (int m = 0; m < 16; m++) {
+                const int u = lane + 64 * m, s = (c - u) & (2 * kN - 1);
+                const int32_t x = a[s & (kN - 1)];
+                e[wv * kN + u] = s < kN ? x : (int32_t)(0u - (uint32_t)x);
+            }
+            if (wv == 0 && lane == 0) e[NP * kN] = b[c];
+        }
+    }
+}
 
 // ---- multi-key blind rotation, 2 parties, TWO waves per rotation ------------------------------------------------
 // BASELINE config 5 is 1024 rotations: with one wave per rotation that is ONE wave per SIMD (a lone wave issues FP64 at
@@ -213,8 +277,12 @@ __global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(mk_blind_rotate_kernel_
     if (wib == 0) tw2_lds[lane] = P.T.tw2[lane];
     if (lane == 0) pair_flags[wv] = 0;
     // acc = (0, ..., 0, X^{-barb} * mu)       mk_internals.jl:491-492, 72-79
-    if (wv == 0) { init_zero_poly(lane, acc_lds); init_zero_poly(lane, acc_lds + kImg); }
-    else init_body(lane, bara[NP * P.n] & (2 * kN - 1), P, w, acc_lds + 2 * kImg);
+    if constexpr (kACC) {
+        mk_init_acc(lane, wv, bara[NP * P.n] & (2 * kN - 1), P, w, acc_lds);      // the ACC form: the caller's sample, masks and body
+    } else {
+        if (wv == 0) { init_zero_poly(lane, acc_lds); init_zero_poly(lane, acc_lds + kImg); }
+        else init_body(lane, bara[NP * P.n] & (2 * kN - 1), P, w, acc_lds + 2 * kImg);
+    }
     __syncthreads();
     wave_priority_begin(P.prio_steps);
     Tan16 tk;
@@ -230,11 +298,15 @@ __global__ __launch_bounds__(128 * RW, 2) void TV_KERNEL(mk_blind_rotate_kernel_
     if (!live) return;
     const int lane_e = lane_id_fresh();
     diag_end<MARGIN>(P.diag, w, worst, dg_t0, dg_r0, wv == 0 && lane_e == 0);
-    // mk_tlwe_extract_sample (mk_internals.jl:88-95): one extracted mask column per party, b = body[0]
-    int32_t *ext = P.ext + w * (NP * kN + 1);
-    extract_mask_poly(lane_e, acc_lds + wv * kImg, ext + wv * kN);                // wave c extracts mask column c
-    if (wv == 0 && lane_e == 0) ext[NP * kN] = acc_lds[NP * kImg + kMir];
-    if (wv == 0) store_bodies(P, w, lane_e, acc_lds + NP * kImg + kMir, kN);
+    if constexpr (kACC) {
+        mk_store_acc(P, w, lane_e, wv, acc_lds);      // the ACC form: the whole accumulator and / or its n_out extractions
+    } else {
+        // mk_tlwe_extract_sample (mk_internals.jl:88-95): one extracted mask column per party, b = body[0]
+        int32_t *ext = P.ext + w * (NP * kN + 1);
+        extract_mask_poly(lane_e, acc_lds + wv * kImg, ext + wv * kN);                // wave c extracts mask column c
+        if (wv == 0 && lane_e == 0) ext[NP * kN] = acc_lds[NP * kImg + kMir];
+        if (wv == 0) store_bodies(P, w, lane_e, acc_lds + NP * kImg + kMir, kN);
+    }
 }
 
 // ---- multi-key blind rotation, any number of parties (2..8) and any decomposition length (<= 8) ------------

@@ -42,8 +42,8 @@ struct LevelKind {
     const char *no_wires;       // the parenthetical of the "no wire table" refusal
     const char *other_wires;    // what a wire table of the other kind is told
     bool gate_key = false;      // the selectors are the context's bootstrapping key in the gates' layout, its n entries in order
-    bool has_selectors(const tfhe_ctx *c) const { return gate_key ? c->have_bk : mk ? c->d_mk_tgsw != nullptr : c->d_tgsw != nullptr; }
-    int64_t selectors(const tfhe_ctx *c) const { return gate_key ? c->P.n : mk ? c->mk_tgsw_count : c->tgsw_count; }
+    bool has_selectors(const tfhe_ctx *c) const { return gate_key ? (mk ? c->have_mk_bk : c->have_bk) : mk ? c->d_mk_tgsw != nullptr : c->d_tgsw != nullptr; }
+    int64_t selectors(const tfhe_ctx *c) const { return gate_key ? (mk ? (int64_t)c->mk_parties * c->P.n : c->P.n) : mk ? c->mk_tgsw_count : c->tgsw_count; }
     bool has_ks(const tfhe_ctx *c) const { return mk ? c->have_mk_ks() : c->have_ks(); }
 };
 inline const LevelKind SINGLE_KEY = {false, "context is multi-key (leveled operations are single-key)", "TLWE", "tfhe_tlwe_alloc", "tfhe_tgsw_load",
@@ -54,6 +54,11 @@ inline const LevelKind MULTI_KEY = {true, "context is single-key (tfhe_rot_net_l
 // the single-key calls that rotate on the gates' key and kernel (tfhe_bootstrap_acc_batch / _level): no selector set is read
 inline const LevelKind GATE_KEY = {false, "context is multi-key (leveled operations are single-key)", "TLWE", "tfhe_tlwe_alloc", "tfhe_load_bootstrap_key_i32",
                                    "the keyswitch key", "out_form 2 and terms need one", "the wire table has multi-key rows (tfhe_mk_wires_alloc)", true};
+// the multi-key calls that rotate on the multi-key gates' key and kernel (tfhe_mk_bootstrap_acc_batch / _level): the selectors are the
+// multi-key bootstrapping key's P n entries in order, no selector set is read
+inline const LevelKind MK_GATE_KEY = {true, "context is single-key (tfhe_bootstrap_acc_batch / tfhe_bootstrap_acc_level are its calls)", "MK TLWE",
+                                      "tfhe_mk_tlwe_alloc", "tfhe_mk_load_bootstrap_key_i32", "the multi-key keyswitch key", "out_form 2 and terms need one",
+                                      "the wire table has single-key rows (tfhe_wires_alloc): allocate it with tfhe_mk_wires_alloc", true};
 
 // what the level calls on the device-resident tables (tfhe_[mk_]rot_net_level, tfhe_[mk_]blind_rotate_level) refuse before they look at
 // their arguments: the state first, then (multi-key) the key that fixes P.  `needs_wires`: the call reads or writes the wire table;

@@ -5,7 +5,8 @@
 // call in a RotatePlan and names its kernel; the workspace protocol, the map, the uploads, the prologue, the launch, the keyswitch, the
 // download and the timing are here and nowhere else: leveled_run.hpp's protocol for a call that is one launch and not a level loop.
 // The launch itself is the caller's (run_rotation_on's launcher): AnyNRotation below for the four, V3AccRotation or, under option
-// acc_dispatch, AccDispatchRotation for the two.
+// acc_dispatch, AccDispatchRotation for the two; MkW2AccRotation for their multi-key twins (tfhe_mk_bootstrap_acc_batch, tfhe_mk_bootstrap_acc_level:
+// engine_mk_bootstrap_acc.hip).
 #pragma once
 #include "engine.hpp"
 #include "leveled_run.hpp"

@@ -741,28 +741,75 @@ def _mk_load_key_selectors(ck, extra_uni_bits, extra_party_of, expand, device):
     return eng
 
 
-def mk_blind_rotate_lookup(ck, acc, lwe, extra_uni_bits=None, extra_party_of=None, acc_index=None, n_out=1, out_form=2, expand="device", device=0):
+def _mk_tuned_engine(ck, device):
+    """ck's engine where Engine.mk_bootstrap_acc serves its shape and key layout (option "mk_bootstrap_acc"); ValueError elsewhere."""
+    eng = ck.engine(device)
+    if not eng.get_option("mk_bootstrap_acc"):
+        p = ck.params
+        raise ValueError(f"tuned=True: Engine.mk_bootstrap_acc serves 2 parties, N = 1024, l = 4 in the gates' key layout; this context has "
+                         f"{ck.parties} parties, N = {p.tlwe_polynomial_degree}, l = {p.bs_decomp_length} (option mk_bootstrap_acc is 0): use tuned=False")
+    return eng
+
+
+def _mk_load_extra_selectors(ck, extra_uni_bits, extra_party_of, expand, device):
+    """The tuned rotation's selector set: the E samples of extra_uni_bits alone, as selectors 0 ... E - 1 of ck's engine on `device` (the
+    bootstrapping key is read in the gates' layout and is not loaded as selectors); nothing is loaded without extra bits.  Returns the
+    engine."""
+    assert expand in ("device", "host")
+    eng = _mk_tuned_engine(ck, device)
+    if extra_uni_bits is None:
+        return eng
+    extra = [np.asarray(a, np.int32) for a in extra_uni_bits]
+    if len(extra) != 6 or extra[0].ndim != 3 or any(a.shape != extra[0].shape for a in extra):
+        raise ValueError("extra_uni_bits must be six arrays [E][l][N]")
+    who = np.ascontiguousarray(np.asarray(extra_party_of, np.int32).reshape(-1))
+    if who.size != extra[0].shape[0]:
+        raise ValueError(f"extra_party_of must have one entry per extra sample ({extra[0].shape[0]}), got {who.size}")
+    pub = np.stack([part.public_b for part in ck._parts])
+    if expand == "device":
+        eng.mk_tgsw_expand_load(pub, who, *extra)
+    else:
+        l, N = extra[0].shape[1:]
+        tg = np.zeros((who.size, 2 * l * ck.parties + 2 * l, N), np.int32)
+        for i in range(ck.parties):
+            mine = np.nonzero(who == i)[0]
+            if mine.size:
+                tg[mine] = mk_tgsw_expand(ck.params, pub, i, *[a[mine] for a in extra])
+        eng.mk_tgsw_load(tg, who)
+    eng._mk_key_extra = ("tuned", int(who.size))      # (mk_two_stage_lookup_device: this many selectors are resident, without the key)
+    return eng
+
+
+def mk_blind_rotate_lookup(ck, acc, lwe, extra_uni_bits=None, extra_party_of=None, acc_index=None, n_out=1, out_form=2, expand="device", device=0,
+                           tuned=False):
     """acc[acc_index[g]] rotated by row g of `lwe` under the MKCloudKey ck's bootstrapping key (Engine.mk_blind_rotate with in_form 0).
     Loads the key's P n entries as selectors 0 ... P n - 1 and, behind them, the extra address bits (six arrays [E][l][N] of
     mk_tgsw_uni_encrypt_bits, sample e by party extra_party_of[e]: selectors P n ... P n + E - 1, for a later mk_cmux_tree on the same
     engine), once; then rotates.  expand "device": RGSW.Expand on the GPU (tfhe_mk_tgsw_expand_load) of the parts' uni-encryptions,
     "host": the host expansion then mk_tgsw_load.  acc: int32 [T][P+1][N] (or [P+1][N]); lwe: int32 [B][P n + 1].  out_form 2
     (default): multi-key LWE samples int32 [B n_out][P*n+1] for mk_decrypt / mk_gate_* (row g's output j at g n_out + j); 1: extracted
-    int32 [B][n_out][P*N+1]; 0: the MK TLWE samples int32 [B][P+1][N]."""
+    int32 [B][n_out][P*N+1]; 0: the MK TLWE samples int32 [B][P+1][N].
+    tuned=True: the same words from Engine.mk_bootstrap_acc, on the multi-key gates' own kernel and key; the key is not loaded as
+    selectors, only the extra address bits are (selectors 0 ... E-1).  ValueError where get_option("mk_bootstrap_acc") is 0."""
+    if tuned:
+        eng = _mk_load_extra_selectors(ck, extra_uni_bits, extra_party_of, expand, device)
+        out = eng.mk_bootstrap_acc(acc, np.asarray(lwe, np.int32), acc_index=acc_index, n_out=n_out, out_form=out_form)
+        return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
     eng = _mk_load_key_selectors(ck, extra_uni_bits, extra_party_of, expand, device)
     sel = None if extra_uni_bits is None else np.arange(ck.parties * ck.params.lwe_size, dtype=np.int32)
     out = eng.mk_blind_rotate(acc, np.asarray(lwe, np.int32), sel=sel, acc_index=acc_index, in_form=0, n_out=n_out, out_form=out_form)
     return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
 
 
-def mk_two_stage_lookup(ck, tables, high_uni_bits, party_of, low_lwe, p, out_form=2, expand="device", device=0):
+def mk_two_stage_lookup(ck, tables, high_uni_bits, party_of, low_lwe, p, out_form=2, expand="device", device=0, tuned=False):
     """A table of p 2^d entries addressed by d jointly encrypted high bits and one multi-key LWE digit of Z_p that gates or lookups
     computed.  tables: int32 [2^d][P+1][N], sample h the test polynomial (trivial: mk_tlwe_trivial(make_test_vector(...), P); or
     mk_private_lut_encrypt) of the p entries whose high address is h; high_uni_bits: the six arrays of mk_tgsw_uni_encrypt_bits, each
     [B][d][l][N], bit v of row g (bit 0 the lowest) uni-encrypted by party party_of[g][v] (party_of: [B][d], or [d] for every row);
     low_lwe: int32 [B][P n + 1] of messages in Z_p (mk_lut_encrypt).  An MK CMUX tree with out_form 0 picks row g's sample, the
     rotation by its low digit reads the entry: 2^d - 1 MK external products plus one MK rotation per row.  out_form as
-    mk_blind_rotate_lookup (n_out 1)."""
+    mk_blind_rotate_lookup (n_out 1).
+    tuned=True: the rotation by Engine.mk_bootstrap_acc, the selector set holding the address bits alone (mk_blind_rotate_lookup)."""
     arrs = [np.asarray(a, np.int32) for a in high_uni_bits]
     if len(arrs) != 6 or arrs[0].ndim != 4 or any(a.shape != arrs[0].shape for a in arrs):
         raise ValueError("high_uni_bits must be six arrays [B][depth][l][N]")
@@ -774,23 +821,29 @@ def mk_two_stage_lookup(ck, tables, high_uni_bits, party_of, low_lwe, p, out_for
         raise ValueError(f"p = {p} (a power of two, 2 ... N/2)")
     who = np.broadcast_to(np.asarray(party_of, np.int32), (B, depth)).reshape(-1)
     Pn = ck.parties * ck.params.lwe_size
+    if tuned:
+        eng = _mk_load_extra_selectors(ck, [a.reshape((B * depth,) + a.shape[2:]) for a in arrs], who, expand, device)
+        picked = eng.mk_cmux_tree(tables, np.arange(B * depth, dtype=np.int32).reshape(B, depth), out_form=0)
+        out = eng.mk_bootstrap_acc(picked, rows, acc_index=np.arange(B, dtype=np.int32), out_form=out_form)
+        return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
     eng = _mk_load_key_selectors(ck, [a.reshape((B * depth,) + a.shape[2:]) for a in arrs], who, expand, device)
     picked = eng.mk_cmux_tree(tables, Pn + np.arange(B * depth, dtype=np.int32).reshape(B, depth), out_form=0)
     out = eng.mk_blind_rotate(picked, rows, sel=np.arange(Pn, dtype=np.int32), acc_index=np.arange(B, dtype=np.int32), in_form=0, out_form=out_form)
     return out.reshape(-1, out.shape[-1]) if out_form == 2 else out
 
 
-def mk_pbs_to_tlwe(ck, lwe, f, p, q=None, device=0):
+def mk_pbs_to_tlwe(ck, lwe, f, p, q=None, device=0, tuned=False):
     """f(m) of every multi-key sample of m in Z_p as an MK TLWE sample int32 [B][P+1][N]: the rotation of the trivial accumulator
     (0, ..., 0, test vector) with out_form 0.  The test polynomial is constant over each window, so coefficient 0 carries
     lut_encode(f(m), q) — where mk_cmux_lookup / mk_cmux_net_lookup read their `data` and extract: a multi-key gate or lookup output
-    becomes a table entry with no packing key and no keyswitch noise.  f: a callable Z_p -> Z_q or an int32 test polynomial [N]."""
+    becomes a table entry with no packing key and no keyswitch noise.  f: a callable Z_p -> Z_q or an int32 test polynomial [N].
+    tuned: as mk_blind_rotate_lookup."""
     N = ck.params.tlwe_polynomial_degree
     tv = make_test_vector(f, p, N, q) if callable(f) else np.asarray(f, np.int32)
-    return mk_blind_rotate_lookup(ck, mk_tlwe_trivial(tv, ck.parties), lwe, out_form=0, device=device)
+    return mk_blind_rotate_lookup(ck, mk_tlwe_trivial(tv, ck.parties), lwe, out_form=0, device=device, tuned=tuned)
 
 
-def mk_two_stage_lookup_device(ck, table_slot, high_uni_bits, party_of, low_wires, out_wires, work_slot, device=0):
+def mk_two_stage_lookup_device(ck, table_slot, high_uni_bits, party_of, low_wires, out_wires, work_slot, device=0, tuned=False):
     """mk_two_stage_lookup between the device-resident tables of ck's engine: the 2^d test polynomials are in MK TLWE slots
     [table_slot, table_slot + 2^d) (Engine.mk_tlwe_upload), row g's low digit is multi-key wire low_wires[g] (what mk_lut_level or
     mk_gates_level left there) and its answer goes, keyswitched, to wire out_wires[g]; slots [work_slot, work_slot + B) receive the
@@ -798,7 +851,10 @@ def mk_two_stage_lookup_device(ck, table_slot, high_uni_bits, party_of, low_wire
     (tfhe_mk_tgsw_expand_load); every later request of the same shape swaps only its B d address bits in (Engine.mk_tgsw_expand_update)
     instead of re-expanding the key.  Then Engine.mk_rot_net_level (the tree, into slots) and Engine.mk_blind_rotate_level (into wires):
     nothing but the uni-encryptions and the index maps crosses PCIe.  The words in out_wires equal mk_two_stage_lookup's on the same
-    samples.  Returns the engine."""
+    samples.  Returns the engine.
+    tuned=True: the rotation by Engine.mk_bootstrap_acc_level on the multi-key gates' own kernel and key: the key is never loaded as
+    selectors, the set holds the B d address bits alone (selectors 0 ... B d - 1), swapped in place by later requests of the same shape.
+    The same words; ValueError where get_option("mk_bootstrap_acc") is 0."""
     arrs = [np.asarray(a, np.int32) for a in high_uni_bits]
     if len(arrs) != 6 or arrs[0].ndim != 4 or any(a.shape != arrs[0].shape for a in arrs):
         raise ValueError("high_uni_bits must be six arrays [B][depth][l][N]")
@@ -809,6 +865,17 @@ def mk_two_stage_lookup_device(ck, table_slot, high_uni_bits, party_of, low_wire
     who = np.ascontiguousarray(np.broadcast_to(np.asarray(party_of, np.int32), (B, depth)).reshape(-1))
     flat = [a.reshape((B * depth,) + a.shape[2:]) for a in arrs]
     Pn = ck.parties * ck.params.lwe_size
+    if tuned:
+        eng = _mk_tuned_engine(ck, device)
+        if getattr(eng, "_mk_key_extra", None) == ("tuned", B * depth):
+            eng.mk_tgsw_expand_update(0, np.stack([part.public_b for part in ck._parts]), who, *flat)
+        else:
+            _mk_load_extra_selectors(ck, flat, who, "device", device)
+        eng.mk_rot_net_level(tree_net(depth), np.arange(B * depth, dtype=np.int32).reshape(B, depth), table_first=np.full(B, int(table_slot), np.int32),
+                             out_form=0, out_first=int(work_slot))
+        eng.mk_bootstrap_acc_level(int(work_slot) + np.arange(B, dtype=np.int32), np.arange(B + 1, dtype=np.int32), low, np.ones(B, np.int32),
+                                   out_form=2, out_wires=out_wires)
+        return eng
     eng = ck.engine(device)
     if getattr(eng, "_mk_key_extra", None) == B * depth:
         eng.mk_tgsw_expand_update(Pn, np.stack([part.public_b for part in ck._parts]), who, *flat)
